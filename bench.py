@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: LightGCN-SPEX graph convolution + BPR step on MI355X (BASELINE.json's metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline `value`, `ms_per_step`, the in-region
+`roofline`).  --full adds every other measurement below (stand-alone kernel rates and other shapes in `extra`, `roofline_hbm`,
+`cpu_baseline`, for N > 1 the strong-scaling leg).  --dump-outputs DIR writes, after the timed steps, what the last step left its
+caller: DIR/embeddings.npy (the trained table E^0, [N, 64] float32) and DIR/loss_sum.npy (the running BPR loss sum the step
+returns).  The inputs are seeded: the same arguments give the same inputs on every run.
 
 One "step" = one pass of the hot path over one batch, inputs resident in HBM:
     3-layer propagation over the normalised user-item graph (3 SpMM launches, layer mean fused)
@@ -54,6 +60,21 @@ def compulsory_bytes(nnz, n_rows, d=D):
     return nnz * 8 + n_rows * (4 + 8 * d)
 
 
+def dump_outputs(out_dir, arrays, budget=64 << 20):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32, smallest first.  An array that does not fit in what is left of
+    the budget is written as a fixed, seeded sample of its rows, their indices beside it as <name>_rows.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget - (64 << 10)                # (room for the .npy headers)
+    for name, x in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.nbytes > left:
+            keep = np.sort(np.random.default_rng(0).choice(len(x), left // (x[0].nbytes + 8), replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), keep.astype(np.float64))
+            x, left = x[keep], left - keep.size * 8
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        left -= x.nbytes
+
+
 def time_events(fn, iters, finish=None):
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
@@ -71,12 +92,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: stand-alone kernel rates and other shapes, roofline_hbm, "
+                         "cpu_baseline, the N > 1 strong-scaling leg (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-hbm-roofline", action="store_true")
     ap.add_argument("--no-standalone", action="store_true")
     ap.add_argument("--hbm-log2-nodes", type=int, default=24)     # the scaled roofline graph is N = 2^24
     ap.add_argument("--no-strong-scaling", action="store_true")   # N > 1: skip the strong-scaling leg on the 2^24-node graph
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # The contract is ONE JSON line on stdout.  RCCL prints a version banner on stdout when its first communicator is created (the
     # N > 1 runs; the world-size-1 communicator of `extra.partitioned_one_call_steps_world1`): keep the real stdout for the line and
     # point file descriptor 1 at stderr for everything a library may print in between.
@@ -283,21 +311,22 @@ def main():
     gc.collect()
     gc.freeze()
 
-    # ---- stand-alone rates of the pieces (same process, same data).  They run BEFORE the timed region: every bench run
-    # makes them anyway, and in front they also bring the GPU to its steady clocks before the K timed steps (the
-    # driver's 20-step timed region is 1 ms long).
+    # ---- stand-alone rates of the pieces (--full; same process, same data) on a stepper of their own, so that the timed steps
+    # start from the seeded table with or without them.  They run BEFORE the timed region: there they also keep the GPU
+    # busy right up to the warm-up.
     aux = {}
-    if not part and not a.no_standalone:
+    if not part and a.full and not a.no_standalone:
         try:
-            for _ in range(300):                      # bring the GPU to its steady clocks first (the set-up above left it idle)
-                stepper.propagate()
-            aux["propagate_only_ms"] = time_events(stepper.propagate, 200)
+            astep = LightGCNStepper(graph, torch.from_numpy(E0_host).to(dev), n_u, n_layers=L, lr=lr)
+            for _ in range(300):
+                astep.propagate()
+            aux["propagate_only_ms"] = time_events(astep.propagate, 200)
             aux["propagate_only_edges_per_s"] = L * nnz / (aux["propagate_only_ms"] * 1e-3)
-            lo = stepper.light_out
+            lo = astep.light_out
             Tb = 1 << 20
 
             def bpr_rate(u_, p_, n_, grouped):
-                fn = lambda: ops.bpr_sgd_step(lo[:n_u], lo[n_u:], stepper.E0[:n_u], stepper.E0[n_u:], u_, p_, n_, 1e-6, 0.0,
+                fn = lambda: ops.bpr_sgd_step(lo[:n_u], lo[n_u:], astep.E0[:n_u], astep.E0[n_u:], u_, p_, n_, 1e-6, 0.0,
                                               grouped=grouped)
                 fn()
                 ms = time_events(fn, 20)
@@ -327,7 +356,7 @@ def main():
             yb = (torch.rand(256, device=dev) < 1 / 6).float()
             ub, ib = tu[:256], tp[:256]
             acc = torch.zeros(1, device=dev)
-            fn2 = lambda: stepper.step_bce(ub, ib, yb, loss_acc=acc, batch_rows_only=True)
+            fn2 = lambda: astep.step_bce(ub, ib, yb, loss_acc=acc, batch_rows_only=True)
             fn2()
             ms2 = time_events(fn2, 200)
             aux["exact_train_step_ms_B256"] = ms2
@@ -346,14 +375,14 @@ def main():
             def fn2b():
                 u_, i_, y_ = tb[state["k"] & 63]
                 state["k"] += 1
-                return stepper.step_bce(u_, i_, y_, loss_acc=acc, batch_rows_only=True)
+                return astep.step_bce(u_, i_, y_, loss_acc=acc, batch_rows_only=True)
             fn2b()
             aux["exact_train_step_ms_B256_training_batches"] = time_events(fn2b, 256)
             # the same step in the deterministic accumulation mode (SPEX_STEP_DETERMINISTIC: no float atomics, all-pull backward)
-            stepper.deterministic = True
+            astep.deterministic = True
             fn2b()
             aux["exact_train_step_ms_B256_training_batches_deterministic"] = time_events(fn2b, 256)
-            stepper.deterministic = False
+            astep.deterministic = False
             fn2b()
             # the same step under the reference's recommended edge dropout (`--dropout 1 --keepprob 0.3`, README.md:119-123): a fresh
             # in-kernel (Philox) mask per step on the forward handle and on the transposed handle with its edge-id permutation
@@ -362,7 +391,7 @@ def main():
                 from spex_amd.trainer import edge_dropout_mask
                 t_rp, t_c, t_v, t_eid = csr_transpose(rowptr, col, val, n_nodes)
                 graph_tr = SpexGraph(t_rp, t_c, t_v, n_cols=n_nodes, edge_id=t_eid, device=dev)
-                dstp = LightGCNStepper(graph, stepper.E0.clone(), n_u, n_layers=L, lr=lr, graph_t=graph_tr)
+                dstp = LightGCNStepper(graph, astep.E0.clone(), n_u, n_layers=L, lr=lr, graph_t=graph_tr)
                 kd = {"k": 0}
 
                 def fn2d():
@@ -634,11 +663,26 @@ def main():
     bracket_ms, bracket_launches = graph.read_timer(per_launch=False)
     graph.detach_timer()
 
+    # ---- what the timed path handed its caller after the last step: the trained table E^0 (updated in place; all ranks' rows in
+    #      global order) and the running loss sum the step returns (every warm-up and timed step, the tuning steps of N > 1 too)
+    if a.dump_outputs:
+        if not part:
+            table, loss_sum = stepper.E0, stepper.loss_acc
+        else:
+            padded = P.all_gather_rows(E0_local, out=torch.empty_like(P.gathered))        # every rank takes part
+            mr = P.part.max_rows
+            table = torch.cat([padded[r * mr: r * mr + int(n)] for r, n in enumerate(P.part.rows)])
+            loss_sum = loss_acc                                   # (every rank scores the whole batch: the same sum on each)
+            del padded
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"embeddings": table.cpu().numpy(), "loss_sum": loss_sum.cpu().numpy()})
+        del table, loss_sum
+
     # ---- N > 1: STRONG scaling on the one size where a row partition can win: the 2^24-node graph (450 M stored
     #      entries, a 4.3 GB table) partitioned over the N ranks — 18.7 / N ms of SpMM per layer against the all-gather of the
     #      4.3 GB table.  Reported in `extra` (the headline `value` stays the weak-scaling figure the contract names).
     strong = None
-    if part and not a.no_strong_scaling:
+    if part and a.full and not a.no_strong_scaling:
         try:
             from spex_amd.datasets import scaled_graph
             del P, E0_local
@@ -738,7 +782,7 @@ def main():
 
     if not part:
         # ---- HBM-resident graph: where the roofline fraction is meaningful
-        if not a.no_hbm_roofline:
+        if a.full and not a.no_hbm_roofline:
             try:
                 from spex_amd.datasets import scaled_graph
                 del stepper
@@ -810,7 +854,7 @@ def main():
                 out["roofline_hbm"] = {"error": repr(e)}
 
         # ---- CPU baseline: the C restatement on the host cores, same step, bounded samples
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             try:
                 from oracle import oracle as O
                 cores = min(len(os.sched_getaffinity(0)), 16)   # a 1-GPU box's CPU share is 16 cores

@@ -325,18 +325,19 @@ def test_two_ranks_dual_task_training_matches_the_reference_epinion2(tmp_path, g
     assert int(d[0]["r1"]) == int(d[1]["r0"]) and int(d[1]["r1"]) == 3186 + 12407
 
 
-def test_bench_multi_rank_path_rehearsal():
-    """bench.py's N > 1 code path exactly as the driver launches it (python -m torch.distributed.run, one process per
+def test_bench_multi_rank_path_rehearsal(tmp_path):
+    """bench.py --full's N > 1 code path as the driver launches it (python -m torch.distributed.run, one process per
     rank), rehearsed with two ranks sharing the test box's one GPU (SPEX_BENCH_SHARE_GPU=1, collectives through gloo;
     the driver's runs use one GPU per rank over RCCL): it must print one well-formed JSON line with the whole-job
-    figures."""
+    figures, and --dump-outputs writes the whole trained table, both ranks' rows in global order."""
     import json
     import subprocess
     import sys
     env = dict(os.environ, SPEX_BENCH_SHARE_GPU="1", SPEX_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--hbm-log2-nodes", "17"]                    # (the strong-scaling leg on a 2^17-node graph here; 2^24 in the driver's runs)
+           "--full", "--hbm-log2-nodes", "17",          # (the strong-scaling leg on a 2^17-node graph here; 2^24 in the driver's runs)
+           "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=REPO, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -350,18 +351,33 @@ def test_bench_multi_rank_path_rehearsal():
     ss = out["extra"]["strong_scaling_hbm_graph"]
     assert "error" not in ss, ss
     assert ss["propagation_ms"] > 0 and ss["edges_per_s"] > 0 and ss["local_rows"] > 0 and ss["layers"] == 3
+    assert sorted(os.listdir(tmp_path / "out")) == ["embeddings.npy", "loss_sum.npy"]
+    E = np.load(tmp_path / "out" / "embeddings.npy")
+    loss_sum = np.load(tmp_path / "out" / "loss_sum.npy")
+    assert loss_sum.dtype == np.float32 and loss_sum.shape == (1,) and loss_sum[0] > 0
+    # the bench's seeded table and triples: rows no triple touches keep their seeded values, in global row order
+    from spex_amd.datasets import epinion2_replicated, xavier_uniform_np
+    _, _, n_user, m_item = epinion2_replicated(2, seed=2020)
+    rng = np.random.default_rng(2020)
+    W0 = np.concatenate([xavier_uniform_np(n_user + 1, 64, rng), xavier_uniform_np(m_item, 64, rng)])
+    trng = np.random.default_rng(2021)
+    tu, tp, tn = trng.integers(0, n_user, 2048), trng.integers(0, m_item, 2048), trng.integers(0, m_item, 2048)
+    touched = np.zeros(len(W0), bool)
+    touched[np.concatenate([tu, n_user + 1 + tp, n_user + 1 + tn])] = True
+    assert E.dtype == np.float32 and E.shape == W0.shape and np.isfinite(E).all()
+    assert np.array_equal(E[~touched], W0[~touched]) and not np.array_equal(E[touched], W0[touched])
 
 
 def test_bench_partitioned_path_through_the_nccl_backend_and_the_native_exchange():
     """bench.py's N > 1 code path forced at world size 1 (SPEX_BENCH_FORCE_PARTITIONED=1) through the REAL `nccl` backend: the
     row partition, torch.distributed's RCCL collectives, the selection among the exchanges — where the library's own
     communicator (spex_comm_*: "native" and "native-p2p") is built, verified against the torch.distributed table and timed —
-    and the strong-scaling leg.  With one rank nothing crosses a link, but every call of the driver's multi-GPU run is made."""
+    and (--full) the strong-scaling leg.  With one rank nothing crosses a link, but every call of the driver's multi-GPU run is made."""
     import json
     import subprocess
     import sys
     env = dict(os.environ, SPEX_BENCH_FORCE_PARTITIONED="1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--hbm-log2-nodes", "17"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--hbm-log2-nodes", "17"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=REPO, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -407,13 +423,13 @@ def test_bench_multi_rank_rehearsal_verifies_the_native_exchange_with_real_data(
 
 
 def test_bench_single_gpu_line_is_well_formed():
-    """bench.py as the driver runs it at N = 1 (here with the auxiliary measurements and the 2^24-node graph switched off, a
+    """bench.py --full at N = 1 (here with the auxiliary measurements and the 2^24-node graph switched off, a
     short CPU-baseline leg left on): ONE JSON line carrying the contract's keys, `roofline` and `cpu_baseline` objects with
     consistent figures."""
     import json
     import subprocess
     import sys
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--no-hbm-roofline", "--no-standalone"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-hbm-roofline", "--no-standalone"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=REPO, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -439,6 +455,57 @@ def test_bench_single_gpu_line_is_well_formed():
     cb = out["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == "edges/s" and "sample" in cb
     assert out["value"] > 20 * cb["value"]                  # (a sanity bound, not a target)
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_what_they_computed(tmp_path, oracle):
+    """A plain bench.py run (no --full) measures the headline only, times exactly --steps steps, and --dump-outputs writes what
+    the last step left its caller: the trained table E^0 and the running loss sum, equal to the same seeded warm-up + timed
+    BPR-SGD steps replayed on the CPU oracle."""
+    import json
+    import subprocess
+    import sys
+    from spex_amd.datasets import epinion2_replicated, xavier_uniform_np
+    from spex_amd.graph import lightgcn_norm_adj
+    steps, warmup = 3, 1
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=REPO, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["warmup"] == warmup and out["ms_per_step"] > 0 and out["dtype"] == "f32"
+    assert abs(out["value"] - 3 * 418608 * steps / (out["ms_per_step"] * steps * 1e-3)) <= 1e-6 * out["value"]
+    assert "cpu_baseline" not in out and "roofline_hbm" not in out and "propagate_only_ms" not in out["extra"]
+    assert sorted(os.listdir(tmp_path / "out")) == ["embeddings.npy", "loss_sum.npy"]
+    E = np.load(tmp_path / "out" / "embeddings.npy")
+    loss_sum = np.load(tmp_path / "out" / "loss_sum.npy")
+    assert E.dtype == np.float32 and E.shape == (15593, 64) and loss_sum.dtype == np.float32 and loss_sum.shape == (1,)
+    # the bench's seeded inputs, and its warm-up + timed steps on the CPU
+    uu, ii, n_user, m_item = epinion2_replicated(1, seed=2020)
+    csr = lightgcn_norm_adj(uu.numpy(), ii.numpy(), n_user, m_item)
+    n_u = n_user + 1
+    rng = np.random.default_rng(2020)
+    W0 = np.concatenate([xavier_uniform_np(n_u, 64, rng), xavier_uniform_np(m_item, 64, rng)])
+    trng = np.random.default_rng(2021)
+    tu, tp, tn = trng.integers(0, n_user, 2048), trng.integers(0, m_item, 2048), trng.integers(0, m_item, 2048)
+    W, want_loss = W0, 0.0
+    for _ in range(warmup + steps):
+        lo = oracle.propagate_mean(*csr, W, 3)
+        loss, Un, In = oracle.bpr_sgd(lo[:n_u], lo[n_u:], W[:n_u], W[n_u:], tu, tp, tn, lr=1e-3, reg=0.0)
+        W = np.concatenate([Un, In]).astype(np.float32)
+        want_loss += loss * 2048
+    # the loss sum counts every step (one step more or less is 25 % of it)
+    assert abs(float(loss_sum[0]) - want_loss) <= 1e-5 * want_loss, (float(loss_sum[0]), want_loss)
+    # rows no triple touches keep their seeded values bit for bit
+    touched = np.zeros(len(W0), bool)
+    touched[np.concatenate([tu, n_u + tp, n_u + tn])] = True
+    assert np.array_equal(E[~touched], W0[~touched])
+    # a step moves a row by less than one float32 ulp (the gradient carries 1 / T), so the table is compared by the size of the
+    # update: an untouched table would be off by all of it; float32 rounding of the update leaves ~0.2 of it
+    upd = np.linalg.norm((W - W0).astype(np.float64))
+    off = np.linalg.norm((E - W).astype(np.float64)) / upd
+    assert upd > 0 and off <= 0.5, off
 
 
 def _peer_worker(rank, world, port, out_dir):

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has bench; then
   echo "== kernel trace of bench.py" | tee -a $OUT/log.txt
-  timeout -k 10 560 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 $R/bench.py --steps 300 --warmup 30 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2>> $OUT/log.txt || echo "bench trace failed" >> $OUT/log.txt
+  timeout -k 10 560 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 $R/bench.py --steps 300 --warmup 30 --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2>> $OUT/log.txt || echo "bench trace failed" >> $OUT/log.txt
 fi
 if has steps; then
   echo "== kernel trace of the steps" | tee -a $OUT/log.txt
@@ -42,7 +42,7 @@ if has ngcf; then
 fi
 if has misc; then
   echo "== bench as the driver runs it (--steps 20 --warmup 5) and the default" | tee -a $OUT/log.txt
-  (cd $R && timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_steps20.json 2>> $OUT/log.txt) || echo "bench steps20 failed" >> $OUT/log.txt
-  (cd $R && timeout -k 10 500 python3 bench.py > $OUT/bench.json 2>> $OUT/log.txt) || echo "bench default failed" >> $OUT/log.txt
+  (cd $R && timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_steps20.json 2>> $OUT/log.txt) || echo "bench steps20 failed" >> $OUT/log.txt
+  (cd $R && timeout -k 10 500 python3 bench.py --full > $OUT/bench.json 2>> $OUT/log.txt) || echo "bench default failed" >> $OUT/log.txt
 fi
 echo done | tee -a $OUT/log.txt
