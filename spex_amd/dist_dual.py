@@ -25,6 +25,7 @@ from torch import nn
 
 from . import ops as _default_ops
 from .dist import PartitionedLightGCN
+from .trainer import _DualTaskArena
 
 
 class _PropagateAndUserBlock(torch.autograd.Function):
@@ -141,7 +142,7 @@ class PartitionedDualTask(nn.Module):
                 dist.all_reduce(p.grad, group=self.group)
 
 
-class PartitionedDualTaskStepper:
+class PartitionedDualTaskStepper(_DualTaskArena):
     """The dual-task training step on the row partition as ONE native call (spex_partitioned_dual_task_step_f32) — what
     DualTaskStepper is to the single-GPU model: no autograd, no allocation, no host work between the launches; the exchanges go
     through the model's NativeComm (spex_comm_*, RCCL bound inside the library).  main_auto_expert_s.py:53-91.
@@ -155,7 +156,7 @@ class PartitionedDualTaskStepper:
 
     def __init__(self, model, path_capacity, path_len, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, n_rec=5, batch_capacity=256,
                  exchange="native-p2p", two_streams=True, deterministic=False, fixed_task_weights=False, comm=None, fast=True):
-        from . import _lib, ops
+        from . import ops
         core, P = model.core, model.P
         dev = model.E0_local.device
         assert dev.type == "cuda", "PartitionedDualTaskStepper: GPU only (no CPU fallback)"
@@ -174,68 +175,16 @@ class PartitionedDualTaskStepper:
         P.set_allgather(exchange)
         self._side = torch.cuda.Stream(device=dev) if two_streams else None
         n_loc = P.n_local
-        Pn = ops.trust_param_count(n_heads, d)
-        self.n_trust = Pn
-        total = n_loc * d + Pn + 512 + 4
+        self._init_arena((model.E0_local,), core, batch_capacity)
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
-        self.arena, self.m, self.v = z(total), z(total), z(total)
-        off = 0
-
-        def place(param, n):
-            nonlocal off
-            view = self.arena[off: off + n].view(param.shape)
-            view.copy_(param.data)
-            param.data = view
-            off += n
-
-        place(model.E0_local, n_loc * d)
-        for t in core._trust_param_tensors():
-            place(t, t.numel())
-        assert off == n_loc * d + Pn
-        place(core.att_exp1, 256); place(core.att_exp2, 256); place(core.task_weights, 2)
         self.light, self.g_prop, self.g_raw, self.gs, self.g_E0 = (z(n_loc, d) for _ in range(5))
         self.gathered0 = z(P.part.n_padded, d)
         self.user_table = z(self.n_u, d)
-        self.g_user, self.g_small = z(self.n_u, d), z(Pn + 512)
-        T = self.path_capacity
-        self.a2 = z(T, d)
-        self.trust_ws = z(max(1, int(_lib.load().spex_trust_workspace_floats(T, self.path_len, d, n_heads, self.n_u))))
-        self.dscore, self.loss_b = z(T, self.n_u - 1), z(T)
-        self.loss, self.loss_acc, self.precision = z(2), z(2), z(2, 2)
-        self.t = 0
-        self.slot_capacity = 0
-        self._desc = None
-        self._slots(2 * int(batch_capacity))
-        self.refresh_precision()
 
     def _slots(self, n):
         if self.slot_capacity < n:
-            from . import _lib
-            z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.dev)
-            self.rows = z(2 * n, self.d)
-            self.mixed_slots, self.grad_slots, self.g_prop_slots, self.g_raw_slots = (z(n, self.d) for _ in range(4))
-            self.loss_rows = z(n)
-            self.att_parts = z(int(_lib.load().spex_expert_gate_rows_bwd_parts(n)) * 512)
-            self.arange = torch.arange(n, dtype=torch.int64, device=self.dev)
-            self.slot_capacity = n
-            self._release()
-
-    def _release(self):
-        d = self._desc
-        self._desc = None
-        if d is not None and (d.ev_fork or d.ev_join):
-            try:
-                torch.cuda.synchronize()
-                from . import _lib
-                _lib.release_step_events(d)
-            except Exception:
-                pass
-
-    def __del__(self):
-        self._release()
-
-    def refresh_precision(self):
-        self.precision[(self.t + 1) & 1] = torch.exp(-2.0 * self.model.core.task_weights.detach())
+            self.rows = torch.zeros((2 * n, self.d), dtype=torch.float32, device=self.dev)     # the batch's fetched rows
+            super()._slots(n)
 
     def positions(self, users, items):
         pu, pi = self.P.padded_index(users.to(self.dev).long(), items.to(self.dev).long())

@@ -667,6 +667,17 @@ def test_deep_one_call_step_equals_the_launch_by_launch_step(golden, ngcf_data_r
                 losses.append(acc.item() - before)
             assert (getattr(st, "_deep_desc", None) is not None) == native and st.t == 4 and model.dropout_step == 4
             res.append((losses, {n: p.detach().clone() for n, p in model.named_parameters()}))
+            if native:
+                # a launch-by-launch step on a larger batch reallocates the per-slot buffers: no native descriptor may keep the old ones
+                st._one_call_ok = lambda *a: False
+                u = torch.from_numpy(brng.integers(0, data.n_users, 512)).to(DEV)
+                i = torch.from_numpy(brng.integers(0, data.n_items, 512)).to(DEV)
+                y = torch.from_numpy((brng.random(512) < 1 / 6).astype(np.float32)).to(DEV)
+                st.step(u, i, y, loss_acc=acc)
+                assert st._desc is None and st._deep_desc is None
+                del st._one_call_ok
+                st.step(u, i, y, loss_acc=acc)
+                assert st._deep_desc is not None and st.t == 6
         (l_a, p_a), (l_b, p_b) = res
         assert np.abs(np.asarray(l_a) - np.asarray(l_b)).max() <= 2e-3, (l_a, l_b)        # differences of a running fp32 sum near 1 700: ulp 1.2e-4
         for n in p_a:

@@ -619,37 +619,54 @@ def test_partition_push_structure_is_the_block_of_the_transpose_read_by_column(e
         assert push.edge_id is None
 
 
+class _EpochData:
+    """A training-data stand-in: every ng_sample draws a fresh epoch from NumPy's global generator (logged as "S" in `log`)."""
+    def __init__(self, log=None):
+        self.n, self.log = 1000, log
+    def ng_sample(self):
+        if self.log is not None:
+            self.log.append("S")
+        self.users_fill = np.random.randint(0, 50, self.n).astype(np.int64)
+        self.items_fill = np.random.randint(0, 70, self.n).astype(np.int64)
+        self.labels_fill_np = (np.random.random(self.n) < 0.2).astype(np.float32)
+    def __len__(self):
+        return self.n
+
+
+class _RecordingStepper:
+    """A LightGCNStepper stand-in that records every step's batch (logged as "." in `log`)."""
+    def __init__(self, log=None):
+        self.E0 = torch.zeros(1)
+        self.graph = self.graph_t = None
+        self.seen, self.log = [], log
+    def _one_call_ok(self, *a):
+        return False                                     # (no native epoch on the CPU: the Python loop around step_bce)
+    def step_bce(self, users, items, labels, loss_acc=None, batch_rows_only=False):
+        if self.log is not None:
+            self.log.append(".")
+        self.seen.append((users.numpy().copy(), items.numpy().copy(), labels.numpy().copy()))
+        loss_acc += float(len(users))
+
+
+class _MaskRecordingGraph:
+    """A graph-handle stand-in for edge dropout: nnz entries on the CPU, every set_edge_mask call recorded."""
+    nnz, device = 300, "cpu"
+    def __init__(self):
+        self.masks = []
+    def set_edge_mask(self, mode, keep=None, *rest):
+        self.masks.append((mode, None if keep is None else keep.numpy().copy()))
+
+
 def test_train_epochs_draws_the_generators_like_a_sequential_loop():
     """Host logic of trainer.train_epochs (no GPU: a recording stand-in for the stepper): the next epoch's negatives (the train data's
     ng_sample: NumPy's global generator) and shuffle (dataloader_epoch_order: torch's global generator) are drawn on a second thread
     while the current epoch is being issued — and must come out exactly as a sequential `ng_sample(); train_epoch()` loop draws them
     (main_rec.py:25-31): the same batches in the same order, epoch after epoch."""
     from spex_amd.trainer import train_epoch, train_epochs
-
-    class Data:
-        def __init__(self):
-            self.n = 1000
-        def ng_sample(self):
-            self.users_fill = np.random.randint(0, 50, self.n).astype(np.int64)
-            self.items_fill = np.random.randint(0, 70, self.n).astype(np.int64)
-            self.labels_fill_np = (np.random.random(self.n) < 0.2).astype(np.float32)
-        def __len__(self):
-            return self.n
-
-    class Recorder:
-        def __init__(self):
-            self.E0 = torch.zeros(1)
-            self.graph = self.graph_t = None
-            self.seen = []
-        def _one_call_ok(self, *a):
-            return False                                     # (no native epoch on the CPU: the Python loop around step_bce)
-        def step_bce(self, users, items, labels, loss_acc=None, batch_rows_only=False):
-            self.seen.append((users.numpy().copy(), items.numpy().copy(), labels.numpy().copy()))
-            loss_acc += float(len(users))
     runs = []
     for overlapped in (True, False):
         np.random.seed(5); torch.manual_seed(5)
-        rec, td = Recorder(), Data()
+        rec, td = _RecordingStepper(), _EpochData()
         if overlapped:
             totals = train_epochs(rec, td, 3, batch_size=256)
         else:
@@ -660,6 +677,43 @@ def test_train_epochs_draws_the_generators_like_a_sequential_loop():
     for x, y in zip(a, b):
         assert all(np.array_equal(p, q) for p, q in zip(x, y))
     assert not np.array_equal(a[0][0], a[4][0])                                       # (the epochs do differ)
+
+
+def test_train_epochs_with_host_drawn_edge_dropout_masks_is_a_sequential_loop():
+    """Under the "reference" edge-dropout stream every step draws its mask on the host — `torch.rand(nnz)` (model.py:50) from torch's
+    global generator, the one the next epoch's shuffle comes from.  trainer.train_epochs then prepares nothing beside the current
+    epoch: the order of ng_sample and steps, the batches and the masks set on both handles are a sequential
+    `ng_sample(); train_epoch()` loop's."""
+    from spex_amd.trainer import train_epoch, train_epochs
+
+    class Stepper(_RecordingStepper):
+        def set_edge_dropout(self, mask=None):
+            for g in (self.graph, self.graph_t):
+                g.set_edge_mask(*((0,) if mask is None else mask))
+    edge_dropout = (0.5, "reference")
+    runs = []
+    for overlapped in (True, False):
+        np.random.seed(5); torch.manual_seed(5)
+        log = []
+        st, td = Stepper(log), _EpochData(log)
+        st.graph, st.graph_t = _MaskRecordingGraph(), _MaskRecordingGraph()
+        if overlapped:
+            totals = train_epochs(st, td, 3, batch_size=256, edge_dropout=edge_dropout)
+        else:
+            totals = [float(train_epoch(st, td, batch_size=256, edge_dropout=edge_dropout)) for _ in range(3)]
+        runs.append((log, st.seen, st.graph.masks, st.graph_t.masks, totals))
+    (la, a, ma, mta, ta), (lb, b, mb, mtb, tb) = runs
+    assert "".join(la) == "".join(lb) == "S....S....S...." and ta == tb
+    assert len(a) == len(b) == 3 * 4
+    for x, y in zip(a, b):
+        assert all(np.array_equal(p, q) for p, q in zip(x, y))
+    assert len(ma) == len(mb) == len(mta) == len(mtb) == 3 * (4 + 1)                 # a mask per step, cleared after each epoch
+    for masks in (mb, mta, mtb):
+        for (mode_a, keep_a), (mode_b, keep_b) in zip(ma, masks):
+            assert mode_a == mode_b and (keep_a is None) == (keep_b is None)
+            assert keep_a is None or np.array_equal(keep_a, keep_b)
+    assert [m[0] for m in ma] == ([1] * 4 + [0]) * 3
+    assert not np.array_equal(ma[0][1], ma[1][1])                                    # (a fresh mask per step)
 
 
 def test_ngcf_blocked_sampler_replay_is_random_sample_draw_for_draw(epinion2):
