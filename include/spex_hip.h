@@ -109,7 +109,7 @@ int spex_graph_set_edge_mask(spex_graph_t *g, int mode /*0 off, 1 injected, 2 sa
 int spex_spmm_f32(const spex_graph_t *g, const float *X, float *Y, const float *add_in, float add_div,
                   const float *acc_in, float *acc_out, float acc_div, int32_t d, void *stream);
 
-/* The same product for a LIST of rows only (d == 64, no edge dropout):
+/* The same product for a LIST of rows only (d = 64, 128 or 256, no edge dropout):
  *   for r in { idx_a[k] + off_a : k < n_a } + { idx_b[k] + off_b : k < n_b }:
  *     y = sum_e val[e] X[col[e],:];   Y[r,:] = y (if Y);   acc_out[r,:] = (acc_in[r,:] + y) / acc_div (if acc_out)
  * Other rows of Y / acc_out are left untouched.  idx_*: device int64 (a batch's users and items as the DataLoader
@@ -118,7 +118,7 @@ int spex_spmm_f32(const spex_graph_t *g, const float *X, float *Y, const float *
  * [0, n_rows) is skipped.
  * The training step reads the last propagation layer (model.py:91-95) at the batch's rows only (model.py:115-116):
  * this replaces that layer's launch over the whole matrix.  Rows of up to 1024 entries are summed in the order
- * spex_spmm_f32 uses (bit-identical results).
+ * spex_spmm_f32 uses at the same d (bit-identical results).  d > 64: X / Y / acc_in / acc_out 16-byte aligned.
  */
 int spex_spmm_rowlist_f32(const spex_graph_t *g, const float *X, const int64_t *idx_a, int32_t n_a, int64_t off_a,
                           const int64_t *idx_b, int32_t n_b, int64_t off_b, float *Y, const float *acc_in, float *acc_out,
@@ -347,7 +347,7 @@ int spex_unique_rows_i32(const int64_t *idx_a, int32_t n_a, int64_t off_a, const
 int spex_spmm_push_rows_f32(const spex_graph_t *g, const int32_t *list, const int32_t *count, int32_t max_count,
                             const float *src, int32_t src_indexed, const float *add, int32_t add_indexed, float scale,
                             float *out, int32_t d, void *stream);
-/* The same product driven by the batch itself (d == 64), EVERY slot contributing its own row: for slot k with row
+/* The same product driven by the batch itself (d = 64, 128 or 256), EVERY slot contributing its own row: for slot k with row
  * r = idx_a[k] + off_a (k < n_a) or idx_b[k - n_a] + off_b:
  *   out[col[e], :] += scale * val[e] * src[k, :]  over the stored entries e of row r;   out[r, :] += scale * add[k, :] (if add)
  * src / add are COMPACT per-slot arrays (row strides ld_src / ld_add) — the per-sample gradient rows
@@ -360,14 +360,15 @@ int spex_spmm_push_batch_f32(const spex_graph_t *g, const int64_t *idx_a, int32_
                              int32_t n_b, int64_t off_b, const float *src, int32_t ld_src, const float *add, int32_t ld_add,
                              float scale, float *out, int32_t d, void *stream);
 
-/* The batch-sized middle of the exact LightGCN training step (L >= 2, d == 64) as ONE launch (under edge dropout — a mask set on the
+/* The batch-sized middle of the exact LightGCN training step (L >= 2, d = 64, 128 or 256) as ONE launch (under edge dropout — a mask set on the
  * handle with spex_graph_set_edge_mask — the last layer at the batch's rows and the push apply the handle's keep rule entry by entry,
  * exactly as spex_spmm_f32 does: kept values / keep_prob, dropped entries contribute nothing): what the
  * sequence spex_spmm_rowlist_f32 -> spex_score_bce_slots_f32 -> spex_spmm_push_batch_f32 computes, i.e. for sample b with
  * rows u = users[b], i = items[b] + n_user_rows (utility1/model.py:91-97 at the batch's rows, :111-121, and autograd's first
  * backward product):
  *   light_r = (acc_in[r] + (A X)[r]) / acc_div   for r in {u, i}   — the last layer + layer mean at the two rows (same segment
- *                                                                     order as spex_spmm_rowlist_f32: bit-identical rows)
+ *                                                                     order as spex_spmm_rowlist_f32: bit-identical rows,
+ *                                                                     and for rows of <= 1 024 entries spex_spmm_f32's at this d)
  *   x = <light_u, light_i>;   loss_b = BCEWithLogits(x, labels[b]);   dg = (sigmoid(x) - labels[b]) * grad_scale
  *   loss_per_sample[b] = loss_b (plain store) if loss_per_sample != NULL, else *loss_sum += loss_b (one atomic per sample)
  *   g_u = dg * light_i,  g_i = dg * light_u
@@ -377,7 +378,8 @@ int spex_spmm_push_batch_f32(const spex_graph_t *g, const int64_t *idx_a, int32_
  *                                                                    the rows of A — (A^T g)[c] = sum_r A[r, c] g[r]
  * g_out and G are accumulated into: zero them first (the step's Adam pass does).  Samples with an index out of range are
  * skipped (loss 0).  Up to SPEX_BATCH_PARTS workgroups (default 3) share a sample whose rows are long (their pushes' atomics
- * then come from several CUs).
+ * then come from several CUs).  d = 128 / 256 (X, acc_in 16-byte aligned): a lane gathers 2 / 4 consecutive columns, a segment's
+ * gathers are in flight 32 / 16 at a time, the push issues 2 / 4 256-byte atomics per stored entry.
  */
 int spex_lightgcn_batch_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div,
                             const int64_t *users, const int64_t *items, const float *labels, int32_t B, int32_t n_user_rows,
@@ -390,7 +392,7 @@ int spex_lightgcn_batch_slots_f32(const spex_graph_t *g, const float *X, const f
                                   const int64_t *items, const float *labels, int32_t B, int32_t n_user_rows, float grad_scale,
                                   float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream);
 
-/* Deterministic accumulation of a batch's per-slot rows into a dense [n_rows, 64] table — replaces the float atomics of the row-
+/* Deterministic accumulation of a batch's per-slot rows into a dense [n_rows, d] table — replaces the float atomics of the row-
  * sparse backward where results must repeat bit for bit (and follows the order of the reference's CPU `index_put_(accumulate)` /
  * index_select backward, LightGCN_SPEX/code/utility1/model.py:115-116 and NGCF_SPEX/code/main_rec.py:89-90 under autograd):
  *   slot k names row r_k = idx_a[k] + off_a (k < n_a) or idx_b[k - n_a] + off_b;
@@ -398,7 +400,7 @@ int spex_lightgcn_batch_slots_f32(const spex_graph_t *g, const float *X, const f
  *   mode 0: out[r] is overwritten (rows no slot names are left alone);  mode 1: out[r] += the sum (plain read-modify-write: the
  *   wave that holds the lowest slot of a row owns it).  slots == NULL: the named rows are set to zero (clears what mode 0 wrote).
  * Rows out of range are skipped.  The duplicate scan is quadratic in the batch (n^2 * 8 bytes of cached reads): a validation-mode
- * kernel for the reference's batches of 256, not a throughput path.  d == 64. */
+ * kernel for the reference's batches of 256, not a throughput path.  d = 64, 128 or 256. */
 int spex_reduce_slots_f32(const int64_t *idx_a, int32_t n_a, int64_t off_a, const int64_t *idx_b, int32_t n_b, int64_t off_b,
                           int32_t n_rows, const float *slots, int32_t ld_slots, float scale, float *out, int32_t mode, int32_t d,
                           void *stream);
@@ -633,7 +635,8 @@ int spex_trust_head_train_f32(const float *table, int64_t n_rows, const float *p
  *                            L == 1: spex_spmm_rowlist_f32 -> spex_score_bce_slots_f32 -> one pull-form product instead)
  *   L-1 x spex_spmm_f32 on A^T (g/(L+1) fused) -> spex_adam_step_f32 over the whole table (which clears g_out again).
  * 2 L + 1 launches (seven for L = 3).
- * The descriptor holds the step's device buffers (all caller-owned, N = graph rows, d == 64):
+ * The descriptor holds the step's device buffers (all caller-owned, N = graph rows; d = 64, 128 or 256 — any other width is
+ * rejected; at d > 64 every table 16-byte aligned):
  *   E0, m, v, light_out, lo_batch, g_out, grad_E0: [N, d];  ws_fwd: [2, N, d];  ws_bwd: [3, N, d];
  *   grad_slots: [slot_capacity, d] with slot_capacity >= 2B (the batch's per-sample gradient rows).
  * g_out and the first [N, d] of ws_bwd must be all-zero before the first call (every call leaves them all-zero: the Adam

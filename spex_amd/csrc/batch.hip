@@ -284,6 +284,180 @@ __global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_batch_kernel(
     STAMP(6);
 }
 
+// lightgcn_batch_kernel for wider embeddings, d = 64 V (V = 2, 4; V = 1 is the kernel above, kept as its own source like the
+// d == 64 SpMM).  In the forward a lane owns V consecutive columns: a gathered row and a running-sum row are one coalesced
+// 256 V-byte wave load each; behind the layer mean it owns columns lane, lane + 64, ..  Same workgroup shape, same dealing of segments to virtual waves and of push runs to (part, wave):
+//   1. a segment's gathers are in flight 64 / V at a time (segment_sum_wide: 64 result registers at every width — the workgroup
+//      has 16 waves, i.e. 128 VGPRs per lane); every column's chain runs in entry order and the segment sums are added in segment
+//      order, so a row of <= 1 024 entries is bit-identical to the row spex_spmm_f32 (spmm_chunk_wide_kernel) and
+//      spex_spmm_rowlist_f32 produce at this width;
+//   2. the dot product is a lane's V products in ascending column order (one fmaf chain) and then the fixed DPP tree over the lanes;
+//   3. the push issues V 256-byte atomics per stored entry (the V column blocks of the 256 V-byte row).
+// LDS: segment partials [2][16][64 V] (column-major per lane: conflict-free) + the two light rows: 8.5 V KB.
+template <bool PUSH, int V>
+__global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_batch_wide_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int n_rows,
+    int n_user_rows, const float *__restrict__ X, const float *__restrict__ acc_in, float acc_div,
+    const int64_t *__restrict__ users, const int64_t *__restrict__ items, const float *__restrict__ labels, int parts,
+    float grad_scale, float push_scale, float *loss_sum, float *__restrict__ loss_rows, float *g_out, float *G, int runs_per_part,
+    float *__restrict__ grad_slots, int B, const float *__restrict__ acc2, const float *__restrict__ acc3, const spex::EdgeDrop drop)
+{
+    typedef typename spex::WideVec<V>::T vec;
+    constexpr int kRow = kWave * V;
+    __shared__ float s_part[2][kWgWaves][kRow];   // [row: user, item][virtual wave][column block j][lane]
+    __shared__ float s_light[2][kRow];            // the two light rows, by column
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int b = blockIdx.x / parts, part = blockIdx.x % parts;
+    const int64_t u64 = users[b], i64 = items[b];
+    if (u64 < 0 || u64 >= n_user_rows || i64 < 0 || i64 + n_user_rows >= n_rows) {   // workgroup-uniform: never gather out of range
+        if (loss_rows && part == 0 && threadIdx.x == 0) loss_rows[b] = 0.0f;
+        if (!PUSH && wave < 2) {
+#pragma unroll
+            for (int c = 0; c < V; ++c) grad_slots[(size_t)(wave * B + b) * kRow + c * kWave + lane] = 0.0f;
+        }
+        return;
+    }
+    const int row[2] = {(int)u64, (int)i64 + n_user_rows};
+    const int beg[2] = {rowptr[row[0]], rowptr[row[1]]};
+    const int deg[2] = {rowptr[row[0] + 1] - beg[0], rowptr[row[1] + 1] - beg[1]};
+    const float y_lab = labels[b];
+    // the running layer sum at the batch's rows — or E^0 (+ E^1 + E^2) of the plain-form forward, added in the fused epilogues' order
+    vec run = (vec)(0.0f);
+    if (wave < 2) {
+        const size_t o = (size_t)row[wave] * kRow + lane * V;
+        run = *reinterpret_cast<const vec *>(acc_in + o);
+        vec r2 = (vec)(0.0f), r3 = (vec)(0.0f);
+        if (acc2) r2 = *reinterpret_cast<const vec *>(acc2 + o);
+        if (acc3) r3 = *reinterpret_cast<const vec *>(acc3 + o);
+        if (acc2) run = run + r2;
+        if (acc3) run = run + r3;
+    }
+    // the push's runs of 16 entries (the forward's rows again), dealt over (part, wave); the first kPre are loaded ahead of the forward
+    const int n_run0 = (deg[0] + 15) >> 4, n_runs = n_run0 + ((deg[1] + 15) >> 4);
+    const int want = (n_runs + runs_per_part - 1) / runs_per_part;
+    const int act = !PUSH ? 1 : (want < parts ? (want < 1 ? 1 : want) : parts);
+    if (part >= act) return;
+    const int q_step = act * kWgWaves;
+    int q = part * kWgWaves + wave;
+    int p_col[kPre], p_cnt[kPre], p_side[kPre];
+    float p_val[kPre];
+    auto load_runs = [&](int q0) {
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {
+            const int qq = q0 + p * q_step;
+            p_col[p] = 0;
+            p_val[p] = 0.0f;
+            p_cnt[p] = 0;
+            p_side[p] = 0;
+            if (qq < n_runs) {
+                const int side = qq >= n_run0, rr = side ? qq - n_run0 : qq;
+                const int base = beg[side] + rr * 16, left = deg[side] - rr * 16;
+                p_side[p] = side;
+                p_cnt[p] = left < 16 ? left : 16;
+                if (lane < p_cnt[p]) {
+                    p_col[p] = col[base + lane];
+                    p_val[p] = val[base + lane];
+                    if (drop.mode != 0) p_val[p] = spex::edge_kept(drop, base + lane) ? p_val[p] / drop.keep_prob : 0.0f;   // the forward's mask
+                }
+            }
+        }
+    };
+    if (PUSH) load_runs(q);
+    // ---- 1. last layer at both rows: segments to virtual waves v = segment mod 16, the two rows' virtual waves dealt to the 16 waves
+    const int nseg[2] = {(deg[0] + kTaskEntries - 1) / kTaskEntries, (deg[1] + kTaskEntries - 1) / kTaskEntries};
+    const int nv0 = nseg[0] < kWgWaves ? nseg[0] : kWgWaves, nv = nv0 + (nseg[1] < kWgWaves ? nseg[1] : kWgWaves);
+    const float *__restrict__ Xl = X + lane * V;
+    for (int j = wave; j < nv; j += kWgWaves) {
+        const int side = j >= nv0, v = side ? j - nv0 : j;
+        vec acc = (vec)(0.0f);
+        for (int sgi = v; sgi < nseg[side]; sgi += kWgWaves) {
+            const int left = deg[side] - sgi * kTaskEntries;
+            const int cnt = left < kTaskEntries ? left : kTaskEntries;
+            if (drop.mode != 0) acc = spex::segment_sum_wide<V, true>(col, val, Xl, beg[side] + sgi * kTaskEntries, cnt, lane, acc, drop);
+            else acc = spex::segment_sum_wide<V, false>(col, val, Xl, beg[side] + sgi * kTaskEntries, cnt, lane, acc, drop);
+        }
+#pragma unroll
+        for (int c = 0; c < V; ++c) s_part[side][v][c * kWave + lane] = acc[c];
+    }
+    __syncthreads();
+    // ---- 2. layer mean at both rows (waves 0 and 1), the score, both gradient rows
+    if (wave < 2) {
+        const int lim = nseg[wave] < kWgWaves ? nseg[wave] : kWgWaves;
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+            float y = lim > 0 ? s_part[wave][0][c * kWave + lane] : 0.0f;
+            for (int w = 1; w < lim; ++w) y = y + s_part[wave][w][c * kWave + lane];   // segment order
+            float s = run[c] + y;
+            if (acc_div != 1.0f) s = s / acc_div;
+            s_light[wave][lane * V + c] = s;                                  // by column: what follows owns columns lane + 64 c
+        }
+    }
+    __syncthreads();
+    // (from here on a lane owns columns lane, lane + 64, ...: every store and every atomic below covers 256 contiguous bytes)
+    vec lu, li;
+    float dot = 0.0f;
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+        lu[c] = s_light[0][c * kWave + lane];
+        li[c] = s_light[1][c * kWave + lane];
+        dot = fmaf(lu[c], li[c], dot);                                        // the lane's columns in ascending order (spex_score_bce_slots_f32's
+    }                                                                         // chain), then the fixed tree over the lanes
+    const float x = wave_sum_f32(dot);
+    const float dg = (sigmoid_f(x) - y_lab) * grad_scale;
+    const vec g2[2] = {dg * li, dg * lu};                                    // d loss / d light at the user row, at the item row
+    if (part == 0 && wave < 2) {
+        if (wave == 0 && lane == 0) {
+            const float bce = fmaxf(x, 0.0f) - x * y_lab + log1pf(expf(-fabsf(x)));
+            if (loss_rows) loss_rows[b] = bce;
+            else atomicAdd(loss_sum, bce);
+        }
+        const vec gw = wave ? g2[1] : g2[0];
+        if (!PUSH) {
+#pragma unroll
+            for (int c = 0; c < V; ++c) grad_slots[(size_t)(wave * B + b) * kRow + c * kWave + lane] = gw[c];
+        } else {
+            const size_t o = (size_t)row[wave] * kRow + lane;
+#pragma unroll
+            for (int c = 0; c < V; ++c) {
+                if (g_out) atomicAdd(g_out + o + c * kWave, gw[c]);           // dense d loss / d light_out; NULL: nobody reads it (L == 3 step)
+                atomicAdd(G + o + c * kWave, push_scale * gw[c]);             // the `g` of (g + A^T g) / (L + 1)
+            }
+        }
+    }
+    if (!PUSH) return;
+    // ---- 3. push over both rows' entries (lightgcn_batch_kernel's loop: lane 0 of every loaded run is read before the first atomic)
+    float *out_l = G + lane;
+    const vec gs2[2] = {push_scale * g2[0], push_scale * g2[1]};
+    for (;;) {
+        int c0[kPre];
+        float v0[kPre];
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {
+            c0[p] = __builtin_amdgcn_readlane(p_col[p], 0);
+            v0[p] = lane_bcast(p_val[p], 0);
+        }
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {
+            const vec gs = p_side[p] ? gs2[1] : gs2[0];
+            if (p_cnt[p] > 0) {
+#pragma unroll
+                for (int c = 0; c < V; ++c) atomicAdd(out_l + (size_t)c0[p] * kRow + c * kWave, v0[p] * gs[c]);
+            }
+#pragma unroll 1
+            for (int j = 1; j < p_cnt[p]; ++j) {
+                const int cc = __builtin_amdgcn_readlane(p_col[p], j);
+                const float v = lane_bcast(p_val[p], j);
+#pragma unroll
+                for (int c = 0; c < V; ++c) atomicAdd(out_l + (size_t)cc * kRow + c * kWave, v * gs[c]);
+            }
+        }
+        q += kPre * q_step;
+        if (q >= n_runs) break;
+        load_runs(q);
+    }
+}
+
 
 // The dual-task model's rec branch has the expert gate between the layer mean and the score (utility1/model_expert_s.py:154-168),
 // so its batch-sized middle cannot include the push (the gate's backward comes first).  Its FORWARD half is one launch of the
@@ -764,6 +938,12 @@ __global__ __launch_bounds__(kWave *kWgWaves) void rows_train_push_kernel(
 
 }  // namespace
 
+// The wide batch kernels move rows as dwordx2 / dwordx4 per lane: their source tables must be 16-byte aligned.
+static bool wide_aligned(const float *a, const float *b, const float *c, const float *d)
+{
+    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
+}
+
 static spex::EdgeDrop edge_drop_of(const spex_graph_t *g)
 {
     return spex::EdgeDrop{g->keep, g->edge_id, g->mask_mode, g->keep_prob, (uint32_t)g->seed, (uint32_t)(g->seed >> 32)};
@@ -863,14 +1043,20 @@ int spex::lightgcn_batch_slots_layers(const spex_graph_t *g, const float *X, con
                    "spex_lightgcn_batch_slots_f32: NULL argument");
     SPEX_CHECK_ARG(B >= 0 && n_user_rows >= 0 && n_user_rows <= g->n_rows, "spex_lightgcn_batch_slots_f32: B=%d n_user_rows=%d", B, n_user_rows);
     SPEX_CHECK_ARG(g->n_rows == g->n_cols, "spex_lightgcn_batch_slots_f32: square graph");
-    if (d != kWave) {
-        spex::set_error("spex_lightgcn_batch_slots_f32: d == 64 only (got %d)", d);
+    if (d != kWave && d != 2 * kWave && d != 4 * kWave) {
+        spex::set_error("spex_lightgcn_batch_slots_f32: d = 64, 128 or 256 only (got %d)", d);
         return SPEX_ERR_UNSUPPORTED;
     }
+    SPEX_CHECK_ARG(d == kWave || wide_aligned(X, acc_in, acc2, acc3), "spex_lightgcn_batch_slots_f32: X / acc_in must be 16-byte aligned at d > 64");
     if (B == 0 || g->n_rows == 0) return SPEX_OK;
-    hipLaunchKernelGGL(lightgcn_batch_kernel<false>, dim3((unsigned)B), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col,
-                       g->val, g->n_rows, n_user_rows, X, acc_in, acc_div, users, items, labels, 1, grad_scale, 0.0f, loss_sum,
-                       loss_per_sample, nullptr, nullptr, 1, grad_slots, B, acc2, acc3, edge_drop_of(g));
+#define SPEX_GO(KERNEL)                                                                                                                    \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)B), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val, g->n_rows,   \
+                       n_user_rows, X, acc_in, acc_div, users, items, labels, 1, grad_scale, 0.0f, loss_sum, loss_per_sample, nullptr,    \
+                       nullptr, 1, grad_slots, B, acc2, acc3, edge_drop_of(g))
+    if (d == kWave) SPEX_GO(lightgcn_batch_kernel<false>);
+    else if (d == 2 * kWave) SPEX_GO((lightgcn_batch_wide_kernel<false, 2>));
+    else SPEX_GO((lightgcn_batch_wide_kernel<false, 4>));
+#undef SPEX_GO
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }
@@ -894,15 +1080,21 @@ int spex::lightgcn_batch_layers(const spex_graph_t *g, const float *X, const flo
                    "spex_lightgcn_batch_f32: NULL argument");
     SPEX_CHECK_ARG(B >= 0 && n_user_rows >= 0 && n_user_rows <= g->n_rows, "spex_lightgcn_batch_f32: B=%d n_user_rows=%d", B, n_user_rows);
     SPEX_CHECK_ARG(g->n_rows == g->n_cols, "spex_lightgcn_batch_f32: square graph");
-    if (d != kWave) {
-        spex::set_error("spex_lightgcn_batch_f32: d == 64 only (got %d)", d);
+    if (d != kWave && d != 2 * kWave && d != 4 * kWave) {
+        spex::set_error("spex_lightgcn_batch_f32: d = 64, 128 or 256 only (got %d)", d);
         return SPEX_ERR_UNSUPPORTED;
     }
+    SPEX_CHECK_ARG(d == kWave || wide_aligned(X, acc_in, acc2, acc3), "spex_lightgcn_batch_f32: X / acc_in must be 16-byte aligned at d > 64");
     if (B == 0 || g->n_rows == 0) return SPEX_OK;
     constexpr int runs_per_part = kBatchRunsPerPart, parts = kBatchParts;
-    hipLaunchKernelGGL(lightgcn_batch_kernel<true>, dim3((unsigned)B * parts), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr,
-                       g->col, g->val, g->n_rows, n_user_rows, X, acc_in, acc_div, users, items, labels, parts, grad_scale, push_scale,
-                       loss_sum, loss_per_sample, g_out, G, runs_per_part, nullptr, B, acc2, acc3, edge_drop_of(g));
+#define SPEX_GO(KERNEL)                                                                                                                    \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)B * parts), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val,      \
+                       g->n_rows, n_user_rows, X, acc_in, acc_div, users, items, labels, parts, grad_scale, push_scale, loss_sum,          \
+                       loss_per_sample, g_out, G, runs_per_part, nullptr, B, acc2, acc3, edge_drop_of(g))
+    if (d == kWave) SPEX_GO(lightgcn_batch_kernel<true>);
+    else if (d == 2 * kWave) SPEX_GO((lightgcn_batch_wide_kernel<true, 2>));
+    else SPEX_GO((lightgcn_batch_wide_kernel<true, 4>));
+#undef SPEX_GO
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

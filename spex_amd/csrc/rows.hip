@@ -138,6 +138,67 @@ __global__ __launch_bounds__(kWave *kPushWaves) void spmm_push_batch_kernel(
     if (add && part == 0 && wave == 0) atomicAdd(out + (size_t)r * kWave + lane, scale * add[(size_t)k * ld_add + lane]);
 }
 
+// spmm_push_batch_kernel at d = 64 V (V = 2, 4): the same dealing of 16-entry runs, every lane owning columns lane, lane + 64, ..
+// — V 256-byte atomics per stored entry (the V column blocks of the row).
+template <int V>
+__global__ __launch_bounds__(kWave *kPushWaves) void spmm_push_batch_wide_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int n_rows,
+    const int64_t *__restrict__ idx_a, int n_a, int64_t off_a, const int64_t *__restrict__ idx_b, int n_b, int64_t off_b,
+    const float *__restrict__ src, int ld_src, const float *__restrict__ add, int ld_add, float scale, float *out)
+{
+    constexpr int kRow = kWave * V;
+    const int k = blockIdx.x / kPushParts, part = blockIdx.x % kPushParts;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const long long r = batch_row(idx_a, n_a, off_a, idx_b, off_b, k);
+    if (r < 0 || r >= n_rows) return;
+    const int beg = rowptr[r], end = rowptr[r + 1];
+    float g[V];
+#pragma unroll
+    for (int c = 0; c < V; ++c) g[c] = scale * src[(size_t)k * ld_src + c * kWave + lane];
+    const int w16 = part * kPushWaves + wave;
+    constexpr int kStride = kPushParts * kPushWaves * 16, kPre = 4;
+    float *out_l = out + lane;
+    for (int base0 = beg + w16 * 16; base0 < end; base0 += kPre * kStride) {
+        int my_col[kPre], c0[kPre];
+        float my_val[kPre], v0[kPre];
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {
+            const int base = base0 + p * kStride;
+            my_col[p] = 0;
+            my_val[p] = 0.0f;
+            if (base + lane < end && lane < 16) {
+                my_col[p] = col[base + lane];
+                my_val[p] = val[base + lane];
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {          // lane 0 of every run before the first atomic: see spmm_push_batch_kernel
+            c0[p] = __builtin_amdgcn_readlane(my_col[p], 0);
+            v0[p] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val[p]), 0));
+        }
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {
+            const int base = base0 + p * kStride;
+            const int cnt = end - base < 16 ? end - base : 16;           // (<= 0 past the row's end)
+            if (cnt > 0) {
+#pragma unroll
+                for (int c = 0; c < V; ++c) atomicAdd(out_l + (size_t)c0[p] * kRow + c * kWave, v0[p] * g[c]);
+            }
+#pragma unroll 1
+            for (int j = 1; j < cnt; ++j) {
+                const int cc = __builtin_amdgcn_readlane(my_col[p], j);
+                const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val[p]), j));
+#pragma unroll
+                for (int c = 0; c < V; ++c) atomicAdd(out_l + (size_t)cc * kRow + c * kWave, v * g[c]);
+            }
+        }
+    }
+    if (add && part == 0 && wave == 0) {
+#pragma unroll
+        for (int c = 0; c < V; ++c) atomicAdd(out + (size_t)r * kRow + c * kWave + lane, scale * add[(size_t)k * ld_add + c * kWave + lane]);
+    }
+}
+
 // Deterministic accumulation of a batch's per-slot rows into a dense table — the atomic-free alternative to the float
 // atomics above (SPEX_STEP_DETERMINISTIC).  out[r] = scale * (slots[k1] + slots[k2] + ...) over the slots k1 < k2 < ... that
 // name row r, in ASCENDING slot order — the order in which the reference's CPU index backward (index_put_ with accumulate,
@@ -183,6 +244,52 @@ __global__ __launch_bounds__(kWave *kReduceWaves) void reduce_slots_kernel(
     *o = mode == 1 ? *o + acc : acc;
 }
 
+// reduce_slots_kernel at d = 64 V (V = 2, 4): one wave per slot, every lane owning columns lane, lane + 64, ..; the same scan, the
+// same ascending slot order per row, the same clear form.
+template <int V>
+__global__ __launch_bounds__(kWave *kReduceWaves) void reduce_slots_wide_kernel(
+    const int64_t *__restrict__ idx_a, int n_a, int64_t off_a, const int64_t *__restrict__ idx_b, int n_b, int64_t off_b,
+    int n_rows, const float *__restrict__ slots, int ld_slots, float scale, float *out, int mode)
+{
+    constexpr int kRow = kWave * V;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int k = blockIdx.x * kReduceWaves + (threadIdx.x >> 6);
+    const int n = n_a + n_b;
+    if (k >= n) return;
+    const long long r = batch_row(idx_a, n_a, off_a, idx_b, off_b, k);
+    if (r < 0 || r >= n_rows) return;
+    float *o = out + (size_t)r * kRow + lane;
+    if (!slots) {                                              // clear form: every slot zeroes its row (idempotent)
+#pragma unroll
+        for (int c = 0; c < V; ++c) o[c * kWave] = 0.0f;
+        return;
+    }
+    for (int base = 0; base < k; base += kWave) {              // a lower-numbered slot with this row owns it
+        const int kk = base + lane;
+        const bool match = kk < k && batch_row(idx_a, n_a, off_a, idx_b, off_b, kk) == r;
+        if (__ballot(match)) return;
+    }
+    float acc[V];
+#pragma unroll
+    for (int c = 0; c < V; ++c) acc[c] = slots[(size_t)k * ld_slots + c * kWave + lane];
+    for (int base = k & ~(kWave - 1); base < n; base += kWave) {
+        const int kk = base + lane;
+        const bool match = kk > k && kk < n && batch_row(idx_a, n_a, off_a, idx_b, off_b, kk) == r;
+        unsigned long long m = __ballot(match);
+        while (m) {                                            // ascending slot order
+            const int j = (int)__builtin_ctzll(m);
+            m &= m - 1;
+#pragma unroll
+            for (int c = 0; c < V; ++c) acc[c] = acc[c] + slots[(size_t)(base + j) * ld_slots + c * kWave + lane];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+        const float a = scale != 1.0f ? acc[c] * scale : acc[c];
+        o[c * kWave] = mode == 1 ? o[c * kWave] + a : a;
+    }
+}
+
 // out[0] (+)= x[0] + x[1] + ... + x[n - 1], added in index order by one thread-free wave pattern: lane j sums x[j], x[j + 64], ...
 // and the 64 partials are combined by the fixed DPP tree — the same order adam_kernel uses for a step's per-sample losses.
 __global__ __launch_bounds__(kWave) void sum_ordered_kernel(const float *__restrict__ x, int n, float scale, float *out, int accumulate)
@@ -213,14 +320,19 @@ extern "C" int spex_reduce_slots_f32(const int64_t *idx_a, int32_t n_a, int64_t 
     SPEX_CHECK_ARG(n_a >= 0 && n_b >= 0 && (n_a == 0 || idx_a) && (n_b == 0 || idx_b), "spex_reduce_slots_f32: bad index lists");
     SPEX_CHECK_ARG(out && n_rows >= 0 && (mode == 0 || mode == 1) && (!slots || ld_slots >= d), "spex_reduce_slots_f32: out=%p mode=%d ld=%d",
                    (void *)out, mode, ld_slots);
-    if (d != kWave) {
-        spex::set_error("spex_reduce_slots_f32: d == 64 only (got %d)", d);
+    if (d != kWave && d != 2 * kWave && d != 4 * kWave) {
+        spex::set_error("spex_reduce_slots_f32: d = 64, 128 or 256 only (got %d)", d);
         return SPEX_ERR_UNSUPPORTED;
     }
     const int n = n_a + n_b;
     if (n == 0 || n_rows == 0) return SPEX_OK;
-    hipLaunchKernelGGL(reduce_slots_kernel, dim3((unsigned)((n + kReduceWaves - 1) / kReduceWaves)), dim3(kWave * kReduceWaves), 0,
-                       (hipStream_t)stream, idx_a, n_a, off_a, idx_b, n_b, off_b, n_rows, slots, ld_slots, scale, out, mode);
+#define SPEX_GO(KERNEL)                                                                                                                \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)((n + kReduceWaves - 1) / kReduceWaves)), dim3(kWave * kReduceWaves), 0, (hipStream_t)stream, \
+                       idx_a, n_a, off_a, idx_b, n_b, off_b, n_rows, slots, ld_slots, scale, out, mode)
+    if (d == kWave) SPEX_GO(reduce_slots_kernel);
+    else if (d == 2 * kWave) SPEX_GO(reduce_slots_wide_kernel<2>);
+    else SPEX_GO(reduce_slots_wide_kernel<4>);
+#undef SPEX_GO
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }
@@ -276,14 +388,19 @@ extern "C" int spex_spmm_push_batch_f32(const spex_graph_t *g, const int64_t *id
     SPEX_CHECK_ARG(g && src && out, "spex_spmm_push_batch_f32: NULL argument");
     SPEX_CHECK_ARG(n_a >= 0 && n_b >= 0 && (n_a == 0 || idx_a) && (n_b == 0 || idx_b), "spex_spmm_push_batch_f32: bad index lists");
     SPEX_CHECK_ARG(g->mask_mode == 0, "spex_spmm_push_batch_f32: edge dropout is not supported in push form");
-    if (d != kWave) {
-        spex::set_error("spex_spmm_push_batch_f32: d == 64 only (got %d)", d);
+    if (d != kWave && d != 2 * kWave && d != 4 * kWave) {
+        spex::set_error("spex_spmm_push_batch_f32: d = 64, 128 or 256 only (got %d)", d);
         return SPEX_ERR_UNSUPPORTED;
     }
     SPEX_CHECK_ARG(ld_src >= d && (!add || ld_add >= d), "spex_spmm_push_batch_f32: ld_src=%d ld_add=%d", ld_src, ld_add);
     if (n_a + n_b == 0 || g->n_rows == 0) return SPEX_OK;
-    hipLaunchKernelGGL(spmm_push_batch_kernel, dim3((unsigned)(n_a + n_b) * kPushParts), dim3(kWave * kPushWaves), 0, (hipStream_t)stream,
-                       g->rowptr, g->col, g->val, g->n_rows, idx_a, n_a, off_a, idx_b, n_b, off_b, src, ld_src, add, ld_add, scale, out);
+#define SPEX_GO(KERNEL)                                                                                                                   \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)(n_a + n_b) * kPushParts), dim3(kWave * kPushWaves), 0, (hipStream_t)stream, g->rowptr, g->col, \
+                       g->val, g->n_rows, idx_a, n_a, off_a, idx_b, n_b, off_b, src, ld_src, add, ld_add, scale, out)
+    if (d == kWave) SPEX_GO(spmm_push_batch_kernel);
+    else if (d == 2 * kWave) SPEX_GO(spmm_push_batch_wide_kernel<2>);
+    else SPEX_GO(spmm_push_batch_wide_kernel<4>);
+#undef SPEX_GO
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

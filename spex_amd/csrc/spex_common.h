@@ -177,6 +177,63 @@ __device__ __forceinline__ bool edge_kept(const EdgeDrop &dr, int entry)
 }
 }  // namespace spex
 
+// Wide embeddings on the batch-sized kernels (d = 64 V, V = 2 / 4; batch.hip, the row-list kernel of spmm.hip): a lane owns V
+// CONSECUTIVE columns, so a gathered row is one coalesced 256 V-byte wave load (dwordx2 / dwordx4 per lane), as in
+// spmm_chunk_wide_kernel.  Tables must be 16-byte aligned (any row of a contiguous fp32 [*, 64 V] tensor is).
+namespace spex {
+template <int V>
+struct WideVec {
+    typedef float T __attribute__((ext_vector_type(V)));
+};
+
+// One 64-entry segment [e0, e0 + cnt) of a row at width 64 V — segment_sum / segment_sum_masked of batch.hip with V columns per
+// lane.  The d == 64 form keeps the segment's 64 gathered floats in registers; at the same 64 result registers a wave here keeps
+// 64 / V gathers in flight (32 rows of 512 B, 16 rows of 1 KB: 16 KB per wave at every width) and walks the segment in V passes —
+// the kernels run 1 024-thread workgroups, i.e. 4 waves per SIMD and at most 128 VGPRs.  Every column's fmaf chain runs in entry
+// order, a dropped entry (MASKED: the handle's edge-dropout rule) contributes fmaf(0, 0, acc) = acc at its place in the chain:
+// the sums are spmm_chunk_wide_kernel's, bit for bit.  Xl = X + lane * V.
+template <int V, bool MASKED>
+__device__ __forceinline__ typename WideVec<V>::T segment_sum_wide(const int32_t *__restrict__ col, const float *__restrict__ val,
+                                                                   const float *__restrict__ Xl, int e0, int cnt, int lane,
+                                                                   typename WideVec<V>::T acc, const EdgeDrop &dr)
+{
+    typedef typename WideVec<V>::T vec;
+    constexpr int kRow = kWave * V, kFly = kTaskEntries / V;
+    int my_col = 0;
+    float my_val = 0.0f;
+    bool dropped = false;
+    if (lane < cnt) {
+        my_col = col[e0 + lane];
+        my_val = val[e0 + lane];
+        if (MASKED) {
+            const bool kept = edge_kept(dr, e0 + lane);
+            my_val = kept ? my_val / dr.keep_prob : 0.0f;
+            dropped = !kept;
+        }
+    }
+    const unsigned long long dbits = MASKED ? __ballot(dropped) : 0ull;
+    const int last_col = __builtin_amdgcn_readlane(my_col, (cnt - 1) & 63);
+    if (lane >= cnt) my_col = last_col;                    // padding: value 0 on a row already being fetched
+#pragma unroll
+    for (int p = 0; p < V; ++p) {
+        if (p * kFly < cnt) {
+            vec x[kFly];
+#pragma unroll
+            for (int k = 0; k < kFly; ++k)
+                x[k] = *reinterpret_cast<const vec *>(Xl + (size_t)(uint32_t)__builtin_amdgcn_readlane(my_col, p * kFly + k) * kRow);
+#pragma unroll
+            for (int k = 0; k < kFly; ++k) {
+                const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val), p * kFly + k));
+                const bool gone = MASKED && ((dbits >> (p * kFly + k)) & 1ull);
+#pragma unroll
+                for (int j = 0; j < V; ++j) acc[j] = fmaf(a, gone ? 0.0f : x[k][j], acc[j]);
+            }
+        }
+    }
+    return acc;
+}
+}  // namespace spex
+
 // A batch as two device index lists with offsets (users; items + n_user_rows): slot k's row.
 namespace spex {
 __device__ __forceinline__ long long batch_row(const int64_t *idx_a, int n_a, int64_t off_a, const int64_t *idx_b, int64_t off_b,

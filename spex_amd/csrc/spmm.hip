@@ -710,7 +710,7 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_wide_kernel(
     }
 }
 
-// Row-list SpMM (d == 64): y[r] = sum_e val[e] X[col[e]] for the listed rows only, with the running-sum epilogue.
+// Row-list SpMM (d == 64; d = 128 / 256: spmm_rowlist_wide_kernel below): y[r] = sum_e val[e] X[col[e]] for the listed rows only, with the running-sum epilogue.
 // The exact training step reads the last forward layer at the batch's <= 2 B rows only; computing just those replaces
 // a 15 us launch over the whole matrix by a ~6 us one.  One 16-wave workgroup per listed row: wave w takes the row's
 // 64-entry segment w (w + 16, ... for rows beyond 1024 entries) straight from the CSR arrays — lane k loads entry k —
@@ -769,6 +769,57 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_rowlist_kernel(
             float s = acc_in[o] + y;
             if (acc_div != 1.0f) s = s / acc_div;
             acc_out[o] = s;
+        }
+    }
+}
+
+// The row-list kernel at d = 64 V (V = 2, 4): a lane owns V consecutive columns, a segment's gathers are in flight 64 / V at a time
+// (segment_sum_wide, spex_common.h), the segment sums are added in segment order — for rows of up to 1 024 entries the row
+// spmm_chunk_wide_kernel produces, bit for bit.
+template <int V>
+__global__ __launch_bounds__(kWave *kWgWaves) void spmm_rowlist_wide_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+    const float *__restrict__ X, const int64_t *__restrict__ idx_a, int n_a, int64_t off_a,
+    const int64_t *__restrict__ idx_b, int64_t off_b, int32_t n_rows, float *__restrict__ Y,
+    const float *acc_in, float *acc_out, float acc_div)
+{
+    typedef typename spex::WideVec<V>::T vec;
+    constexpr int kRow = kWave * V;
+    __shared__ float s_part[kWgWaves][kRow];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r64 = (int)blockIdx.x < n_a ? idx_a[blockIdx.x] + off_a : idx_b[blockIdx.x - n_a] + off_b;
+    if (r64 < 0 || r64 >= n_rows) return;                         // workgroup-uniform: never index out of range
+    const int r = (int)r64;
+    const int beg = rowptr[r], deg = rowptr[r + 1] - beg;
+    const int nseg = (deg + kTaskEntries - 1) / kTaskEntries;
+    const float *__restrict__ Xl = X + lane * V;
+    const spex::EdgeDrop no_drop{nullptr, nullptr, 0, 1.0f, 0u, 0u};
+    vec acc = (vec)(0.0f);
+    for (int sgi = wave; sgi < nseg; sgi += kWgWaves) {
+        const int left = deg - sgi * kTaskEntries;
+        acc = spex::segment_sum_wide<V, false>(col, val, Xl, beg + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc, no_drop);
+    }
+    if (nseg > 1) {
+        if (wave != 0 && wave < nseg) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) s_part[wave][j * kWave + lane] = acc[j];   // column-major per lane: conflict-free
+        }
+        __syncthreads();
+    }
+    if (wave == 0) {
+        vec y = acc;
+        const int lim = nseg < kWgWaves ? nseg : kWgWaves;
+        for (int w = 1; w < lim; ++w) {                            // segment order
+#pragma unroll
+            for (int j = 0; j < V; ++j) y[j] = y[j] + s_part[w][j * kWave + lane];
+        }
+        const size_t o = (size_t)r * kRow + lane * V;
+        if (Y) *reinterpret_cast<vec *>(Y + o) = y;
+        if (acc_out) {
+            vec s = *reinterpret_cast<const vec *>(acc_in + o) + y;
+            if (acc_div != 1.0f) s = s / acc_div;
+            *reinterpret_cast<vec *>(acc_out + o) = s;
         }
     }
 }
@@ -1008,14 +1059,21 @@ extern "C" int spex_spmm_rowlist_f32(const spex_graph_t *g, const float *X, cons
     SPEX_CHECK_ARG(Y || acc_out, "spex_spmm_rowlist_f32: neither Y nor acc_out given");
     SPEX_CHECK_ARG(!acc_out || (acc_in && acc_div != 0.0f), "spex_spmm_rowlist_f32: acc_out needs acc_in and acc_div != 0");
     SPEX_CHECK_ARG(X != Y && X != acc_out, "spex_spmm_rowlist_f32: X must not alias an output");
-    if (d != 64 || g->mask_mode != 0) {
-        spex::set_error("spex_spmm_rowlist_f32: d == 64 without edge dropout only (d = %d, mask mode %d): use spex_spmm_f32", d,
+    if ((d != 64 && d != 128 && d != 256) || g->mask_mode != 0) {
+        spex::set_error("spex_spmm_rowlist_f32: d = 64, 128 or 256 without edge dropout only (d = %d, mask mode %d): use spex_spmm_f32", d,
                         g->mask_mode);
         return SPEX_ERR_UNSUPPORTED;
     }
+    SPEX_CHECK_ARG(d == 64 || ((((uintptr_t)X) | ((uintptr_t)Y) | ((uintptr_t)acc_in) | ((uintptr_t)acc_out)) & 15) == 0,
+                   "spex_spmm_rowlist_f32: X / Y / acc_in / acc_out must be 16-byte aligned at d > 64");
     if (n_a + n_b == 0 || g->n_rows == 0) return SPEX_OK;
-    hipLaunchKernelGGL(spmm_rowlist_kernel, dim3((unsigned)(n_a + n_b)), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr,
-                       g->col, g->val, X, idx_a, n_a, off_a, idx_b, off_b, g->n_rows, Y, acc_in, acc_out, acc_div);
+#define SPEX_GO(KERNEL)                                                                                                             \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)(n_a + n_b)), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val, \
+                       X, idx_a, n_a, off_a, idx_b, off_b, g->n_rows, Y, acc_in, acc_out, acc_div)
+    if (d == 64) SPEX_GO(spmm_rowlist_kernel);
+    else if (d == 128) SPEX_GO(spmm_rowlist_wide_kernel<2>);
+    else SPEX_GO(spmm_rowlist_wide_kernel<4>);
+#undef SPEX_GO
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

@@ -27,7 +27,8 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
     const spex_graph *g = s->graph, *gt = s->graph_t;
     const int32_t L = s->L, d = s->d, n_u = s->n_user_rows;
     SPEX_CHECK_ARG(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_rows, "spex_lightgcn_step_bce_f32: square graphs of one size");
-    SPEX_CHECK_ARG(L >= 1 && d == 64 && n_u >= 0 && n_u <= g->n_rows, "spex_lightgcn_step_bce_f32: L=%d d=%d n_user_rows=%d (needs L >= 1, d == 64)", L, d, n_u);
+    SPEX_CHECK_ARG(L >= 1 && (d == 64 || d == 128 || d == 256) && n_u >= 0 && n_u <= g->n_rows,
+                   "spex_lightgcn_step_bce_f32: L=%d d=%d n_user_rows=%d (needs L >= 1 and d = 64, 128 or 256)", L, d, n_u);
     SPEX_CHECK_ARG(s->slot_capacity >= 2 * B, "spex_lightgcn_step_bce_f32: slot capacity %d < 2 B = %d", s->slot_capacity, 2 * B);
     // edge dropout (model.py:46-55; set per step on BOTH handles with spex_graph_set_edge_mask — graph_t must then be the transposed
     // handle carrying the edge-id permutation, a masked adjacency is not symmetric): every product of the step uses the handles'

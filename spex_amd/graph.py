@@ -271,7 +271,7 @@ class SpexGraph:
 
     def spmm_rows(self, X, idx_a, idx_b=None, off_a=0, off_b=0, Y=None, acc_in=None, acc_out=None, acc_div=1.0):
         """The product for the listed rows only (idx_a + off_a, idx_b + off_b; device int64), other rows of Y / acc_out
-        untouched.  d == 64, no edge dropout.  See spex_spmm_rowlist_f32."""
+        untouched.  d = 64, 128 or 256, no edge dropout.  See spex_spmm_rowlist_f32."""
         d = X.shape[1]
         self._chk(X, self.n_cols, d, "X")
         for t, nm in ((Y, "Y"), (acc_in, "acc_in"), (acc_out, "acc_out")):

@@ -57,6 +57,17 @@ def _score_bce_table_grad(light_out, n_u, u_idx, i_idx, labels, need_grad):
     return loss_sum, grad
 
 
+WIDTHS = (64, 128, 256)     # embedding widths of the batch-sized kernels (one lane per 1 / 2 / 4 columns) and of the one-call LightGCN step
+
+
+def _width(t, name):
+    """The embedding width of a [*, d] table that a batch-sized kernel takes: d must be one of WIDTHS."""
+    d = t.shape[1] if t.dim() == 2 else -1
+    if d not in WIDTHS:
+        raise ValueError(f"{name} must be a 2-D table of width 64, 128 or 256 (got shape {tuple(t.shape)})")
+    return d
+
+
 def _idx(t, device, bound=None):
     """Indices as the reference hands them over (int64, possibly on the host: main_rec.py:33-34).  With `bound`, indices
     outside [0, bound) raise IndexError like the reference's table lookup would — checked for free while the indices are
@@ -383,38 +394,40 @@ def spmm_push_rows(graph, rows, src, out, src_indexed, add=None, add_indexed=Fal
 
 def spmm_push_batch(graph, idx_a, idx_b, off_b, src, out, add=None, scale=1.0):
     """out += scale * (A^T scatter(src) + scatter(add)), every slot of the batch contributing its own row (slot k: row
-    idx_a[k]; slot len(idx_a) + k: row idx_b[k] + off_b; src / add: per-slot [slots, 64] arrays, e.g. score_bce's
-    grad_slots), one launch, d == 64 (spex_spmm_push_batch_f32)."""
-    if out.shape != (graph.n_cols, 64) or not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()):
-        raise ValueError("spmm_push_batch: out must be a contiguous fp32 [graph.n_cols, 64] device tensor")
+    idx_a[k]; slot len(idx_a) + k: row idx_b[k] + off_b; src / add: per-slot [slots, d] arrays, e.g. score_bce's
+    grad_slots), one launch, d = out.shape[1] in WIDTHS (spex_spmm_push_batch_f32)."""
+    d = _width(out, "spmm_push_batch: out")
+    if out.shape != (graph.n_cols, d) or not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()):
+        raise ValueError(f"spmm_push_batch: out must be a contiguous fp32 [graph.n_cols, {d}] device tensor")
     for t in (idx_a, idx_b):
         if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
             raise ValueError("spmm_push_batch: the batch must be contiguous int64 tensors on the GPU")
     slots = idx_a.numel() + idx_b.numel()
     for t, nm in ((src, "src"), (add, "add")):
-        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.stride(1) == 1 and t.shape[0] >= slots and t.shape[1] >= 64):
-            raise ValueError(f"spmm_push_batch: {nm} must be an fp32 [>= slots, >= 64] device tensor with unit column stride")
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.stride(1) == 1 and t.shape[0] >= slots and t.shape[1] >= d):
+            raise ValueError(f"spmm_push_batch: {nm} must be an fp32 [>= slots, >= {d}] device tensor with unit column stride")
     _launch(out.device, "spex_spmm_push_batch_f32", graph._h, _ptr(idx_a), idx_a.numel(), 0, _ptr(idx_b), idx_b.numel(), int(off_b),
-            _ptr(src), src.stride(0), _ptr(add), 0 if add is None else add.stride(0), float(scale), _ptr(out), 64)
+            _ptr(src), src.stride(0), _ptr(add), 0 if add is None else add.stride(0), float(scale), _ptr(out), d)
     _bump(out)
     return out
 
 
 def reduce_slots(idx_a, idx_b, off_b, n_rows, slots, out, scale=1.0, accumulate=False):
-    """Deterministic accumulation of a batch's per-slot rows into a dense [n_rows, 64] table (spex_reduce_slots_f32): out[r] =
+    """Deterministic accumulation of a batch's per-slot rows into a dense [n_rows, d] table, d in WIDTHS (spex_reduce_slots_f32): out[r] =
     scale * sum of the slots naming r, in ascending slot order (overwritten, or added with accumulate); slots=None clears the
     named rows.  The atomic-free alternative to score_bce's dense gradient tables / spmm_push_batch's `add` term."""
-    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == (n_rows, 64)):
-        raise ValueError(f"reduce_slots: out must be a contiguous fp32 [{n_rows}, 64] device tensor")
+    d = _width(out, "reduce_slots: out")
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == (n_rows, d)):
+        raise ValueError(f"reduce_slots: out must be a contiguous fp32 [{n_rows}, {d}] device tensor")
     for t in (idx_a, idx_b):
         if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
             raise ValueError("reduce_slots: the batch must be contiguous int64 tensors on the GPU")
     n = idx_a.numel() + idx_b.numel()
     if slots is not None and not (slots.is_cuda and slots.dtype == torch.float32 and slots.stride(1) == 1 and slots.shape[0] >= n
-                                  and slots.shape[1] >= 64):
-        raise ValueError("reduce_slots: slots must be an fp32 [>= slots, >= 64] device tensor with unit column stride")
+                                  and slots.shape[1] >= d):
+        raise ValueError(f"reduce_slots: slots must be an fp32 [>= slots, >= {d}] device tensor with unit column stride")
     _launch(out.device, "spex_reduce_slots_f32", _ptr(idx_a), idx_a.numel(), 0, _ptr(idx_b), idx_b.numel(), int(off_b), int(n_rows),
-            _ptr(slots), 64 if slots is None else slots.stride(0), float(scale), _ptr(out), 1 if accumulate else 0, 64)
+            _ptr(slots), d if slots is None else slots.stride(0), float(scale), _ptr(out), 1 if accumulate else 0, d)
     _bump(out)
     return out
 
@@ -423,21 +436,21 @@ def lightgcn_batch_slots(graph, X, acc_in, acc_div, users, items, labels, n_user
                          loss_per_sample=None):
     """spex_lightgcn_batch_slots_f32: the batch kernel's forward + scoring with the two gradient rows of every sample written
     as per-sample slots (grad_slots[b], grad_slots[B + b]) — no push, no float atomics (the deterministic step)."""
-    n = graph.n_rows
+    n, d = graph.n_rows, _width(X, "lightgcn_batch_slots: X")
     for t, nm in ((X, "X"), (acc_in, "acc_in")):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (n, 64)):
-            raise ValueError(f"lightgcn_batch_slots: {nm} must be a contiguous fp32 [{n}, 64] device tensor")
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (n, d)):
+            raise ValueError(f"lightgcn_batch_slots: {nm} must be a contiguous fp32 [{n}, {d}] device tensor")
     B = users.numel()
     for t, dt, nm in ((users, torch.int64, "users"), (items, torch.int64, "items"), (labels, torch.float32, "labels")):
         if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == B):
             raise ValueError(f"lightgcn_batch_slots: {nm} must be a contiguous device tensor of the batch's length")
     if not (grad_slots.is_cuda and grad_slots.dtype == torch.float32 and grad_slots.is_contiguous() and grad_slots.shape[0] >= 2 * B
-            and grad_slots.shape[1] == 64):
-        raise ValueError("lightgcn_batch_slots: grad_slots must be a contiguous fp32 [>= 2B, 64] device tensor")
+            and grad_slots.shape[1] == d):
+        raise ValueError(f"lightgcn_batch_slots: grad_slots must be a contiguous fp32 [>= 2B, {d}] device tensor")
     if loss_sum is None and loss_per_sample is None:
         raise ValueError("lightgcn_batch_slots: needs loss_sum or loss_per_sample")
     _launch(X.device, "spex_lightgcn_batch_slots_f32", graph._h, _ptr(X), _ptr(acc_in), float(acc_div), _ptr(users), _ptr(items),
-            _ptr(labels), B, int(n_user_rows), float(grad_scale), _ptr(loss_sum), _ptr(loss_per_sample), _ptr(grad_slots), 64)
+            _ptr(labels), B, int(n_user_rows), float(grad_scale), _ptr(loss_sum), _ptr(loss_per_sample), _ptr(grad_slots), d)
     _bump(loss_sum, loss_per_sample, grad_slots)
 
 
@@ -446,12 +459,12 @@ def lightgcn_batch(graph, X, acc_in, acc_div, users, items, labels, n_user_rows,
     """The batch-sized middle of the exact LightGCN step as one launch (spex_lightgcn_batch_f32): last layer + layer mean at
     the batch's rows, scores + BCE, dense gradient rows added into g_out, and G += push_scale * (g + A^T g) in push form (over
     the rows of `graph` itself: A^T g in push form walks the rows of A).
-    loss_sum: fp32 [1] (accumulated) — or loss_per_sample: fp32 [B], every sample's loss stored instead; g_out, G: fp32 [N, 64]
-    (accumulated: zero them first)."""
-    n = graph.n_rows
+    loss_sum: fp32 [1] (accumulated) — or loss_per_sample: fp32 [B], every sample's loss stored instead; g_out, G: fp32 [N, d]
+    (accumulated: zero them first).  d = X.shape[1] in WIDTHS."""
+    n, d = graph.n_rows, _width(X, "lightgcn_batch: X")
     for t, nm in ((X, "X"), (acc_in, "acc_in"), (g_out, "g_out"), (G, "G")):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (n, 64)):
-            raise ValueError(f"lightgcn_batch: {nm} must be a contiguous fp32 [{n}, 64] device tensor")
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (n, d)):
+            raise ValueError(f"lightgcn_batch: {nm} must be a contiguous fp32 [{n}, {d}] device tensor")
     B = users.numel()
     for t, dt, nm in ((users, torch.int64, "users"), (items, torch.int64, "items"), (labels, torch.float32, "labels")):
         if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == B):
@@ -463,7 +476,7 @@ def lightgcn_batch(graph, X, acc_in, acc_div, users, items, labels, n_user_rows,
         raise ValueError("lightgcn_batch: needs loss_sum or loss_per_sample")
     _launch(X.device, "spex_lightgcn_batch_f32", graph._h, _ptr(X), _ptr(acc_in), float(acc_div), _ptr(users), _ptr(items),
             _ptr(labels), B, int(n_user_rows), float(grad_scale), float(push_scale), _ptr(loss_sum), _ptr(loss_per_sample), _ptr(g_out),
-            _ptr(G), 64)
+            _ptr(G), d)
     _bump(loss_sum, loss_per_sample, g_out, G)
     return loss_sum if loss_per_sample is None else loss_per_sample
 

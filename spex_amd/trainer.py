@@ -53,9 +53,16 @@ class LightGCNStepper:
     def __init__(self, graph, E0, n_user_rows, n_layers=3, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph_t=None, deterministic=None):
         """deterministic (default: SPEX_DETERMINISTIC=1 in the environment): the step takes every sum in a fixed order — no float
         atomics (spex_lightgcn_step_t.flags & SPEX_STEP_DETERMINISTIC): per-sample gradient rows added per table row in ascending
-        slot order, the whole backward in pull form.  Two runs then end in bit-identical tables; ~10 us more per step."""
+        slot order, the whole backward in pull form.  Two runs then end in bit-identical tables; ~10 us more per step.
+        The batch-sized kernels behind the fast and the fixed-order step exist for the widths ops.WIDTHS (64, 128, 256): at any
+        other width the step takes its oldest form (whole-graph layers, dense atomic scoring gradient, all-pull backward), and
+        a deterministic stepper is refused — there is no fixed-order form to give it."""
         assert E0.is_cuda and E0.dtype == torch.float32 and E0.is_contiguous()
         self.deterministic = _deterministic_default(deterministic)
+        self._wide_ok = E0.shape[1] in ops.WIDTHS
+        if self.deterministic and not self._wide_ok:
+            raise ValueError(f"LightGCNStepper(deterministic=True): the fixed-order step needs an embedding width of 64, 128 or 256 "
+                             f"(got {E0.shape[1]})")
         self.graph, self.graph_t = graph, (graph_t if graph_t is not None else graph)
         self.E0, self.n_u, self.L = E0, int(n_user_rows), int(n_layers)
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -83,9 +90,9 @@ class LightGCNStepper:
         """The propagation as the training step needs it: layers 1 .. L-1 over the whole graph, the LAST layer only at the
         batch's rows (the loss reads light_out nowhere else, model.py:115-116) — spex_spmm_rowlist_f32 instead of a
         launch over the whole matrix.  Returns a table that is valid at those rows only.  Falls back to the full propagation
-        when the row-list kernel does not apply (d != 64, L == 0)."""
+        when the row-list kernel does not apply (a width outside ops.WIDTHS, L == 0)."""
         L, g, lo = self.L, self.graph, self.light_out
-        if L == 0 or self.E0.shape[1] != 64:
+        if L == 0 or not self._wide_ok:
             return self.propagate()
         cur = self.E0
         for l in range(L - 1):
@@ -112,7 +119,7 @@ class LightGCNStepper:
         lo = self.propagate_for_batch(users, items) if batch_rows_only and not masked else self.propagate()
         B = users.numel()
         self._slots(B)
-        if self.deterministic and self.E0.shape[1] == 64:
+        if self.deterministic:
             # launch-by-launch form of the deterministic step: per-sample rows only (no dense atomics), added per table row in
             # slot order, then the all-pull backward
             _, loss_sum = ops.score_bce(lo[:self.n_u], lo[self.n_u:], users, items, labels, None, None, 1.0 / B, loss_sum=loss_acc,
@@ -149,7 +156,7 @@ class LightGCNStepper:
     # -- the whole step as one library call (spex_lightgcn_step_bce_f32): same launches, issued from native code
     def _one_call_ok(self, users, items, labels):
         masked = getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
-        return (self.L >= 1 and self.E0.shape[1] == 64 and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
+        return (self.L >= 1 and self._wide_ok and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
                 and _batch_ok(users, items, labels))
 
     def _prepare_desc(self, B):
@@ -188,7 +195,7 @@ class LightGCNStepper:
         1-element device accumulators (loss sums of the full batches / of a shorter last one).  keep_prob < 1: the in-kernel sampled
         edge mask, a fresh one per step (seed (drop_seed << 32) | step — trainer.edge_dropout_mask's "philox" stream)."""
         if not self._one_call_ok(users[:1], items[:1], labels[:1]):
-            raise ValueError("LightGCNStepper.epoch_bce: needs d == 64 and contiguous int64 / fp32 device tensors")
+            raise ValueError("LightGCNStepper.epoch_bce: needs an embedding width of 64, 128 or 256 and contiguous int64 / fp32 device tensors")
         if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
             raise ValueError("LightGCNStepper.epoch_bce: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
         d = self._prepare_desc(min(int(batch_size), users.numel()))
@@ -206,7 +213,7 @@ class LightGCNStepper:
         handle, L < 2)."""
         L, gt = self.L, self.graph_t
         self._ws0_clean = False
-        if L < 2 or self.E0.shape[1] != 64 or getattr(gt, "mask_mode", 0) != 0 or getattr(self.graph, "mask_mode", 0) != 0:
+        if L < 2 or not self._wide_ok or getattr(gt, "mask_mode", 0) != 0 or getattr(self.graph, "mask_mode", 0) != 0:
             gt.propagate_bwd(self.g_out, L, grad_E0=self.grad_E0, ws=self.ws_bwd)
             return
         inv = 1.0 / float(L + 1)
