@@ -664,12 +664,18 @@ enum {
                                          * fork / join on the critical cycle; see spex_dual_task_step_t and spex_dual_task_step_join */
 };
 /* The north-star step — LightGCN L-layer propagation + the fused BPR gather + dot + sigmoid + SGD kernel over T triples — as one
- * call of L + 1 launches: layer 1 with the running sum fused (sum1 = E^0 + E^1), layers 2 .. L in the plain form (no epilogue
- * operand, one output stream), and the BPR kernel forms the layer mean ((sum1 + E^2) + E^3) / (L + 1) — utility1/model.py:94-95, in
- * the fused epilogues' order — at its triples' rows only, the rows of the propagated table the step reads; the updates go to E^0.
- * Same results as spex_propagate_f32 followed by spex_bpr_sgd_step_f32 reading its output (bit-identical rows; float-atomic
- * updates in both).  E0, sum1: [N, 64]; ws: [2, N, 64]; users index rows [0, n_user_rows), items rows n_user_rows + i.
- * d == 64, 1 <= L <= 3, no edge dropout; *loss_sum accumulates the batch's softplus sum. */
+ * call of L + 1 launches: EVERY layer in the plain form (no epilogue operand, one output stream); the layer-1 launch also sets
+ * aside, in a tail of ceil(3 T / 1024) extra workgroups, the E^0 rows of the batch's 3 T slots (a buffer owned by the graph handle,
+ * grown on the first call at a batch size — make that call outside a stream capture), and the BPR kernel forms the layer mean
+ * (((E^0 + E^1) + E^2) + E^3) / (L + 1) — utility1/model.py:94-95, in the fused epilogues' order — at its triples' rows only, the
+ * rows of the propagated table the step reads; the updates go to E^0.  Same results as spex_propagate_f32 followed by
+ * spex_bpr_sgd_step_f32 reading its output (bit-identical rows; float-atomic updates in both).
+ * E0, sum1: [N, 64]; ws: [2, N, 64]; users index rows [0, n_user_rows), items rows n_user_rows + i.
+ * sum1 after the call: E^1.  Where the tail would push a layer launch that fits one dispatch round (<= 512 workgroups) over 512,
+ * and for T > 2^18, the step keeps layer 1 in the running-sum form instead — then sum1 = E^0 + E^1 and the kernel adds
+ * ((sum1 + E^2) + E^3): the same bits.  The schedule depends on the graph and T only.
+ * d == 64, 1 <= L <= 3, no edge dropout; *loss_sum accumulates the batch's softplus sum.  T == 0 (u, i_pos, i_neg may be NULL): the
+ * propagation runs, nothing is updated. */
 int spex_lightgcn_step_bpr_f32(const spex_graph_t *g, float *E0, float *sum1, float *ws, int32_t n_user_rows, int32_t L, int32_t d,
                                const int64_t *u, const int64_t *i_pos, const int64_t *i_neg, int64_t T, float lr, float reg,
                                float *loss_sum, void *stream);

@@ -114,8 +114,12 @@ __global__ __launch_bounds__(kWave *kScoreWaves) void score_bce_kernel(
 // of it can run without its layer-mean epilogue (spex::propagate_plain): the mean is needed at the batch's <= 3 T rows only.
 // Tables hold users first, items from row n_user_rows on; table_w (= E^0) receives the updates and is none of t0 / t1 / t2, so
 // the step stays batch-synchronous.  d == 64, one triple per wave (the step's batches are small: latency-bound by design).
+// SNAP: a COMPACT first addend in front of the tables — ts[3 T][64], triple t's rows at slots t, T + t, 2 T + t (the E^0 rows the
+// propagation's layer-1 launch set aside, spmm.hip SnapArgs; every table then holds one plain layer) — row r = (((ts + t0) + t1) + t2)
+// / div: the same additions in the same order as sum1 = E^0 + E^1 formed by the SpMM's epilogue, bit for bit.
+template <bool SNAP>
 __global__ __launch_bounds__(kWave *kScoreWaves) void bpr_layers_kernel(
-    const float *__restrict__ t0, const float *__restrict__ t1, const float *__restrict__ t2, float div, float *table_w,
+    const float *__restrict__ ts, const float *__restrict__ t0, const float *__restrict__ t1, const float *__restrict__ t2, float div, float *table_w,
     const int64_t *__restrict__ u_idx, const int64_t *__restrict__ p_idx, const int64_t *__restrict__ n_idx, int64_t T,
     int64_t n_user_rows, int64_t n_item_rows, float a_coef, float b_coef, float *loss_sum)
 {
@@ -127,10 +131,13 @@ __global__ __launch_bounds__(kWave *kScoreWaves) void bpr_layers_kernel(
         const int64_t u = u_idx[t], ip = p_idx[t], in = n_idx[t];
         if (u < 0 || u >= n_user_rows || ip < 0 || ip >= n_item_rows || in < 0 || in >= n_item_rows) continue;
         const size_t ou = (size_t)u * kWave + lane, op = (size_t)(n_user_rows + ip) * kWave + lane, on = (size_t)(n_user_rows + in) * kWave + lane;
-        float uu = t0[ou], vp = t0[op], vn = t0[on];              // every load of the triple in flight before the first add
+        float uu = 0.0f, vp = 0.0f, vn = 0.0f;                    // every load of the triple in flight before the first add
+        if (SNAP) { uu = ts[(size_t)t * kWave + lane]; vp = ts[(size_t)(T + t) * kWave + lane]; vn = ts[(size_t)(2 * T + t) * kWave + lane]; }
+        const float u0 = t0[ou], p0 = t0[op], n0 = t0[on];
         float u1 = 0.0f, p1 = 0.0f, n1 = 0.0f, u2 = 0.0f, p2 = 0.0f, n2 = 0.0f;
         if (t1) { u1 = t1[ou]; p1 = t1[op]; n1 = t1[on]; }
         if (t2) { u2 = t2[ou]; p2 = t2[op]; n2 = t2[on]; }
+        if (SNAP) { uu = uu + u0; vp = vp + p0; vn = vn + n0; } else { uu = u0; vp = p0; vn = n0; }
         if (t1) { uu = uu + u1; vp = vp + p1; vn = vn + n1; }
         if (t2) { uu = uu + u2; vp = vp + p2; vn = vn + n2; }
         if (div != 1.0f) { uu = uu / div; vp = vp / div; vn = vn / div; }
@@ -600,7 +607,7 @@ extern "C" int spex_bpr_sgd_step_f32(const float *U_read, const float *I_read, f
                                      const int64_t *i_neg, int64_t T, int32_t d, float lr, float reg, float *loss_sum,
                                      void *stream)
 {
-    SPEX_CHECK_ARG(U_read && I_read && U_w && I_w && u && i_pos && i_neg, "spex_bpr_sgd_step_f32: NULL pointer");
+    SPEX_CHECK_ARG(U_read && I_read && U_w && I_w && (T == 0 || (u && i_pos && i_neg)), "spex_bpr_sgd_step_f32: NULL pointer");   // (T == 0: no indices to read)
     SPEX_CHECK_ARG(T >= 0 && d >= 1, "spex_bpr_sgd_step_f32: T=%lld d=%d", (long long)T, d);
     if (T == 0) return SPEX_OK;
     const int per_wave = bpr_per_wave(T);
@@ -611,15 +618,19 @@ extern "C" int spex_bpr_sgd_step_f32(const float *U_read, const float *I_read, f
     return SPEX_OK;
 }
 
-int spex::bpr_sgd_layers(const float *t0, const float *t1, const float *t2, float div, float *table_w, int64_t n_user_rows,
+int spex::bpr_sgd_layers(const float *snap, const float *t0, const float *t1, const float *t2, float div, float *table_w, int64_t n_user_rows,
                          int64_t n_item_rows, const int64_t *u, const int64_t *i_pos, const int64_t *i_neg, int64_t T, float lr, float reg,
                          float *loss_sum, void *stream)
 {
-    SPEX_CHECK_ARG(t0 && table_w && u && i_pos && i_neg && T >= 0 && div != 0.0f, "bpr_sgd_layers: bad argument");
-    SPEX_CHECK_ARG(table_w != t0 && table_w != t1 && table_w != t2, "bpr_sgd_layers: the updated table must not be a read table");
+    SPEX_CHECK_ARG(t0 && table_w && T >= 0 && (T == 0 || (u && i_pos && i_neg)) && div != 0.0f, "bpr_sgd_layers: bad argument");
+    SPEX_CHECK_ARG(table_w != t0 && table_w != t1 && table_w != t2 && table_w != snap, "bpr_sgd_layers: the updated table must not be a read table");
     if (T == 0) return SPEX_OK;
-    hipLaunchKernelGGL(bpr_layers_kernel, dim3(grid_for(T)), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, t0, t1, t2, div, table_w, u,
-                       i_pos, i_neg, T, n_user_rows, n_item_rows, -lr / (float)T, -lr * reg / (float)T, loss_sum);
+    if (snap)
+        hipLaunchKernelGGL(bpr_layers_kernel<true>, dim3(grid_for(T)), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, snap, t0, t1, t2, div,
+                           table_w, u, i_pos, i_neg, T, n_user_rows, n_item_rows, -lr / (float)T, -lr * reg / (float)T, loss_sum);
+    else
+        hipLaunchKernelGGL(bpr_layers_kernel<false>, dim3(grid_for(T)), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, snap, t0, t1, t2, div,
+                           table_w, u, i_pos, i_neg, T, n_user_rows, n_item_rows, -lr / (float)T, -lr * reg / (float)T, loss_sum);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

@@ -259,6 +259,51 @@ struct DropArgs {
     uint32_t seed_lo, seed_hi;
 };
 
+// Snapshot tail of the plain launch (the one-call BPR step's layer 1): workgroups [table_wgs, gridDim.x) run no task; they copy
+// the rows of X (= E^0, the launch's gather source: already in the L2s) that the step's T triples name into the compact buffer
+// out[3 T][64] — slot j: row u[j] (j < T), n_user_rows + i_pos[j - T] (T <= j < 2 T), n_user_rows + i_neg[j - 2 T] — so that
+// the BPR kernel behind the propagation, which adds its updates into E^0 while other waves still read it, finds the OLD rows
+// there and layer 1 needs no running-sum epilogue over the whole table.  grid == table_wgs (every other launch): no tail.
+struct SnapArgs {
+    const int64_t *u, *ip, *in;
+    float *out;              // [ceil(3 T / 64) * 64][64]
+    int64_t T;
+    int32_t n_user_rows, n_item_rows;
+    int32_t table_wgs;       // workgroups of the task table (the XCD remap is evaluated against this count)
+};
+
+// One wave per 64 slots: lane k resolves slot slot0 + k, then 256-byte row loads in independent batches of kChunk, each followed
+// by its stores (the chunk loop's shape).  A slot of a triple the BPR kernel skips (an index out of range) never gathers: it
+// re-reads row 0 and stores zeros, as do the slots beyond 3 T of the last wave (the buffer is whole waves long).
+__device__ __forceinline__ void snapshot_rows(const SnapArgs &s, const float *__restrict__ X, int64_t slot0, int lane)
+{
+    const int64_t j = slot0 + lane;
+    int my_row = -1;
+    if (j < 3 * s.T) {
+        const int which = j < s.T ? 0 : (j < 2 * s.T ? 1 : 2);
+        const int64_t t = j - which * s.T;
+        const int64_t u = s.u[t], ip = s.ip[t], in = s.in[t];
+        const bool ok = u >= 0 && u < s.n_user_rows && ip >= 0 && ip < s.n_item_rows && in >= 0 && in < s.n_item_rows;
+        if (ok) my_row = which == 0 ? (int)u : s.n_user_rows + (int)(which == 1 ? ip : in);
+    }
+    const float *__restrict__ Xl = X + lane;
+    float *__restrict__ out = s.out + (size_t)slot0 * 64 + lane;
+#pragma unroll 1
+    for (int b = 0; b < kWave; b += kChunk) {      // (rolled: the tail is 4 batches of code in an instantiation whose loop it must not crowd)
+        float x[kChunk];
+#pragma unroll
+        for (int k = 0; k < kChunk; ++k) {
+            const int r = __builtin_amdgcn_readlane(my_row, b + k);
+            x[k] = Xl[(size_t)(uint32_t)(r < 0 ? 0 : r) * 64];
+        }
+#pragma unroll
+        for (int k = 0; k < kChunk; ++k) {
+            const int r = __builtin_amdgcn_readlane(my_row, b + k);
+            __builtin_nontemporal_store(r < 0 ? 0.0f : x[k], out + (size_t)(b + k) * 64);
+        }
+    }
+}
+
 // EPI 0: Y = y;  1: Y = y (optional), acc_out = (acc_in + y) / epi_div;  2: Y = (y + add_in / epi_div) / out_div.
 // ROWIDS: a task's rows are listed per entry (bin-packed tasks) instead of being adjacent from task.z.
 // FOLD: the hub fold is compiled in.  The unmasked instantiations always carry it (it costs their chunk loop nothing); the
@@ -272,17 +317,26 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
     int n_tasks, float *__restrict__ Y,
     const float *epi_in, float epi_div, float out_div, float *acc_out,   // may alias each other (running sum in place): no __restrict__
     float *__restrict__ partial,
-    const DropArgs drop, const int xcd_contiguous, const HubFold hf_args)
+    const DropArgs drop, const int xcd_contiguous, const HubFold hf_args, const SnapArgs snap)
 {
     __shared__ float s_part[kWgWaves][kWave];  // segment sums of the rows this workgroup combines
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    // The unmasked plain form may carry a snapshot tail (SnapArgs): whole workgroups behind the table's, decided once, here, on
+    // scalar values; they touch neither s_part nor the hub tickets.  Only these instantiations read `snap`.
+    constexpr bool kTail = EPI == 0 && !MASKED && FOLD;
+    if (kTail && (int)blockIdx.x >= snap.table_wgs) {
+        const int64_t slot0 = ((int64_t)((int)blockIdx.x - snap.table_wgs) * kWgWaves + wave) * kWave;
+        if (slot0 < 3 * snap.T) snapshot_rows(snap, X, slot0, lane);
+        return;
+    }
     // Workgroups are sorted heaviest-first and dealt round-robin over the 8 XCDs by the dispatcher, which gives every
     // XCD the same mix of weights: right for a graph that streams from HBM (+14 % on Epinion2x538 over handing XCD 0
     // all the heavy workgroups).  A graph whose whole source table sits in cache instead prefers each XCD to walk a
     // contiguous range of workgroups (user rows and item rows of the bipartite graph then gather from different
     // halves of the table in different L2s: 76 % vs 71 % L2 hits on Epinion2).  Placement is a speed matter only.
-    const int wg = xcd_contiguous ? xcd_contiguous_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int n_wg = kTail ? snap.table_wgs : (int)gridDim.x;       // (the table's workgroups: a tail does not move them)
+    const int wg = xcd_contiguous ? xcd_contiguous_block(blockIdx.x, n_wg) : (int)blockIdx.x;
     const int tid = wg * kWgWaves + wave;
     if (tid >= n_tasks) return;  // whole workgroups only (n_tasks is a multiple of kWgWaves)
     const int4 t = task[tid];
@@ -875,18 +929,18 @@ __global__ __launch_bounds__(256) void div_kernel(const float *__restrict__ in, 
 template <int EPI, int V>
 void launch_chunk_v(bool masked, bool row_ids, dim3 grid, dim3 block, hipStream_t stream, const float *X, const spex_graph *g,
                     float *Y, const float *epi_in, float epi_div, float out_div, float *acc_out, const DropArgs &da,
-                    int xcd_contig, const HubFold &hub)
+                    int xcd_contig, const HubFold &hub, const SnapArgs &snap)
 {
 #define SPEX_GO(M, R)                                                                                                  \
     do {                                                                                                               \
         if (V == 1 && (!M || hub.tag != 0u))                                                                           \
             hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, true>), grid, block, 0, stream, X, g->chunk_off,          \
                                g->chunk_val, g->chunk_mask, g->chunk_row, g->task, g->n_tasks, Y, epi_in, epi_div,     \
-                               out_div, acc_out, g->partial, da, xcd_contig, hub);                                     \
+                               out_div, acc_out, g->partial, da, xcd_contig, hub, snap);                               \
         else if (V == 1)                                                                                               \
             hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, !M>), grid, block, 0, stream, X, g->chunk_off,            \
                                g->chunk_val, g->chunk_mask, g->chunk_row, g->task, g->n_tasks, Y, epi_in, epi_div,     \
-                               out_div, acc_out, g->partial, da, xcd_contig, hub);                                     \
+                               out_div, acc_out, g->partial, da, xcd_contig, hub, snap);                               \
         else                                                                                                           \
             hipLaunchKernelGGL((spmm_chunk_wide_kernel<EPI, M, R, (V == 1 ? 2 : V)>), grid, block, 0, stream, X,       \
                                g->chunk_off, g->chunk_val, g->chunk_mask, g->chunk_row, g->task, g->n_tasks, Y, epi_in, \
@@ -911,11 +965,11 @@ void launch_chunk_v(bool masked, bool row_ids, dim3 grid, dim3 block, hipStream_
 template <int EPI>
 void launch_chunk(int d, bool masked, bool row_ids, dim3 grid, dim3 block, hipStream_t stream, const float *X,
                   const spex_graph *g, float *Y, const float *epi_in, float epi_div, float out_div, float *acc_out,
-                  const DropArgs &da, int xcd_contig, const HubFold &hub)
+                  const DropArgs &da, int xcd_contig, const HubFold &hub, const SnapArgs &snap)
 {
-    if (d == 64) launch_chunk_v<EPI, 1>(masked, row_ids, grid, block, stream, X, g, Y, epi_in, epi_div, out_div, acc_out, da, xcd_contig, hub);
-    else if (d == 128) launch_chunk_v<EPI, 2>(masked, row_ids, grid, block, stream, X, g, Y, epi_in, epi_div, out_div, acc_out, da, xcd_contig, hub);
-    else launch_chunk_v<EPI, 4>(masked, row_ids, grid, block, stream, X, g, Y, epi_in, epi_div, out_div, acc_out, da, xcd_contig, hub);
+    if (d == 64) launch_chunk_v<EPI, 1>(masked, row_ids, grid, block, stream, X, g, Y, epi_in, epi_div, out_div, acc_out, da, xcd_contig, hub, snap);
+    else if (d == 128) launch_chunk_v<EPI, 2>(masked, row_ids, grid, block, stream, X, g, Y, epi_in, epi_div, out_div, acc_out, da, xcd_contig, hub, snap);
+    else launch_chunk_v<EPI, 4>(masked, row_ids, grid, block, stream, X, g, Y, epi_in, epi_div, out_div, acc_out, da, xcd_contig, hub, snap);
 }
 
 // Profiling hook: one hipEvent pair around ALL the SpMM launches of an API call (a 3-layer propagation is one bracket
@@ -945,8 +999,15 @@ struct TimerBracket {
     }
 };
 
+// Workgroups of the chunked task table's launch: whole 16-wave workgroups, a multiple of the XCD count so the remap is a bijection.
+inline int64_t chunk_table_wgs(const spex_graph *g)
+{
+    return (((int64_t)g->n_tasks + kWgWaves - 1) / kWgWaves + 7) / 8 * 8;
+}
+
+// snap: the plain d == 64 unmasked launch also copies the triples' rows of X into snap->out (SnapArgs; table_wgs is filled in here).
 int launch_spmm(const spex_graph *g, const float *X, float *Y, const float *add_in, float add_div, const float *acc_in,
-                float *acc_out, float acc_div, int32_t d, hipStream_t stream, float out_div = 1.0f)
+                float *acc_out, float acc_div, int32_t d, hipStream_t stream, float out_div = 1.0f, const SnapArgs *snap = nullptr)
 {
     if (g->n_rows == 0) return SPEX_OK;
     SpmmParams p;
@@ -966,11 +1027,19 @@ int launch_spmm(const spex_graph *g, const float *X, float *Y, const float *add_
     const int64_t tasks = fast ? (int64_t)g->n_tasks : (int64_t)g->n_seg + g->n_rows;  // waves
     int64_t blocks = (tasks + per_block - 1) / per_block;
     blocks = (blocks + 7) / 8 * 8;  // multiple of the XCD count so the remap is a bijection
-    const dim3 grid((unsigned)blocks), block(kWave * per_block), block4(kWave * kWavesPerBlock);
+    SnapArgs sa{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, (int32_t)blocks};
+    int64_t tail = 0;
+    if (snap) {
+        SPEX_CHECK_ARG(fast && d == 64 && !masked && !acc_out && !add_in && snap->out && snap->T > 0, "launch_spmm: the snapshot tail rides on the plain d == 64 launch only");
+        sa = *snap;
+        sa.table_wgs = (int32_t)blocks;
+        tail = (3 * snap->T + (int64_t)kWgWaves * kWave - 1) / ((int64_t)kWgWaves * kWave);
+    }
+    const dim3 grid((unsigned)(blocks + tail)), block(kWave * per_block), block4(kWave * kWavesPerBlock);
     spex_timer *tm = g->timer;
     if (tm && tm->open) tm->launches[tm->used]++;
     std::unique_lock<std::mutex> scratch_lock;   // (held until the launches below are queued)
-    if (fast ? g->n_hub > 0 : g->n_long > 0) {   // this launch writes the handle's scratch: order it behind its last user
+    if ((fast ? g->n_hub > 0 : g->n_long > 0) || snap) {   // this launch writes the handle's scratch (the snapshot buffer is scratch too): order it behind its last user
         spex_graph *gm = const_cast<spex_graph *>(g);
         scratch_lock = std::unique_lock<std::mutex>(gm->scratch_mu);
         if (gm->scratch_used && gm->scratch_stream != stream) {
@@ -995,9 +1064,9 @@ int launch_spmm(const spex_graph *g, const float *X, float *Y, const float *add_
         const bool fold_env = !(fold_sw && fold_sw[0] == '0');
         hub.grp = g->hub_grp; hub.fold = g->hub_fold; hub.ticket = g->hub_ticket;
         hub.tag = (d == 64 && fold_env && g->n_hub > 0 && g->hub_grp && g->hub_ticket) ? 1u : 0u;      // (on / off)
-        if (acc_out) launch_chunk<1>(d, masked, g->row_ids, grid, block, stream, X, g, Y, acc_in, acc_div, 1.0f, acc_out, da, xcd_contig, hub);
-        else if (add_in) launch_chunk<2>(d, masked, g->row_ids, grid, block, stream, X, g, Y, add_in, add_div, out_div, nullptr, da, xcd_contig, hub);
-        else launch_chunk<0>(d, masked, g->row_ids, grid, block, stream, X, g, Y, nullptr, 1.0f, 1.0f, nullptr, da, xcd_contig, hub);
+        if (acc_out) launch_chunk<1>(d, masked, g->row_ids, grid, block, stream, X, g, Y, acc_in, acc_div, 1.0f, acc_out, da, xcd_contig, hub, sa);
+        else if (add_in) launch_chunk<2>(d, masked, g->row_ids, grid, block, stream, X, g, Y, add_in, add_div, out_div, nullptr, da, xcd_contig, hub, sa);
+        else launch_chunk<0>(d, masked, g->row_ids, grid, block, stream, X, g, Y, nullptr, 1.0f, 1.0f, nullptr, da, xcd_contig, hub, sa);
     } else if (masked) {
         hipLaunchKernelGGL((spmm_rows_kernel<true>), grid, block, 0, stream, p);
     } else {
@@ -1106,14 +1175,52 @@ extern "C" int spex_propagate_f32(const spex_graph_t *g, const float *E0, float 
     return SPEX_OK;
 }
 
+namespace {
+
+// The handle's snapshot buffer, grown on demand like `partial` (allocates: the first call at a batch size, outside any stream capture).
+int ensure_snap(spex_graph *g, int64_t floats)
+{
+    if (floats <= g->snap_cap) return SPEX_OK;
+    SPEX_HIP(hipDeviceSynchronize());
+    if (g->snap) SPEX_HIP(hipFree(g->snap));
+    g->snap = nullptr;
+    g->snap_cap = 0;
+    SPEX_HIP(hipMalloc((void **)&g->snap, (size_t)floats * sizeof(float)));
+    g->snap_cap = floats;
+    return SPEX_OK;
+}
+
+// Which schedule a one-call BPR step of T triples takes on this graph — decided from the graph and T only.  The snapshot tail adds
+// ceil(3 T / 1024) workgroups to the layer-1 launch; a launch that fits ONE dispatch round (<= 512 workgroups: two per CU) must still
+// fit it with the tail, else the step keeps the running-sum form on layer 1.  (SPEX_STEP_SNAPSHOT=0 / 1 forces either schedule where
+// both are possible: the tests and the A/B timings run both in one process.)
+constexpr int64_t kOneRoundWgs = 512;
+constexpr int64_t kSnapMaxTriples = (int64_t)1 << 18;     // 192 MiB of snapshot rows; beyond it the grouped BPR form is the caller's anyway
+bool step_takes_snapshot(const spex_graph *g, int32_t d, int64_t T)
+{
+    if (d != 64 || g->task == nullptr || g->mask_mode != 0 || g->n_rows == 0 || T <= 0 || T > kSnapMaxTriples) return false;
+    const char *sw = getenv("SPEX_STEP_SNAPSHOT");
+    if (sw && sw[0] == '0') return false;
+    if (sw && sw[0] == '1') return true;
+    const int64_t table = chunk_table_wgs(g), tail = (3 * T + (int64_t)kWgWaves * kWave - 1) / ((int64_t)kWgWaves * kWave);
+    return !(table <= kOneRoundWgs && table + tail > kOneRoundWgs);
+}
+
+}  // namespace
+
 // The propagation with the layer mean LEFT TO THE CONSUMER (the fused BPR step reads the propagated table at its triples' rows
-// only): layer 1 in the running-sum form — sum1 = E^0 + E^1, kept apart so that the consumer may update E^0 while it reads —,
-// the later layers in the PLAIN form (no epilogue operand, one output stream: 12.3 vs 14.8 us per launch on Epinion2) into the
-// two halves of ws, alternating.  tables[0..2]: what the consumer adds, in this order, before dividing by L + 1 — (sum1, E^2,
-// E^3) for L = 3, i.e. ((E^0 + E^1) + E^2) + E^3, the order of the fused epilogues.  1 <= L <= 3.  One timer bracket (the
-// profiling hook) spans the L launches like spex_propagate_f32's.
+// only, and adds its updates into E^0 while it reads): what the consumer adds, in this order, before dividing by L + 1, is reported
+// in (*snap, tables[0..2]).  1 <= L <= 3.  Two schedules (step_takes_snapshot), the same sums bit for bit:
+//   snapshot  EVERY layer in the PLAIN form (no epilogue operand, one output stream); the layer-1 launch carries a tail of
+//             workgroups that copy the E^0 rows of the step's <= 3 T slots into the handle's compact buffer (SnapArgs).  E^1 goes to
+//             sum1, E^2 / E^3 to the two halves of ws: (*snap = E^0 at the slots, E^1, E^2, E^3), i.e. ((E^0 + E^1) + E^2) + E^3.
+//   fallback  (no triples given, or the tail would push a one-round launch over 512 workgroups) layer 1 in the running-sum form —
+//             sum1 = E^0 + E^1 over the whole table, +2.9 us on Epinion2 —, the later layers plain into the halves of ws:
+//             (*snap = NULL, sum1, E^2, E^3).
+// One timer bracket (the profiling hook) spans the L launches like spex_propagate_f32's.
 int spex::propagate_plain(const spex_graph_t *g, const float *E0, float *sum1, float *ws, int32_t L, int32_t d, void *stream,
-                          const float **tables)
+                          const float **tables, const int64_t *u, const int64_t *i_pos, const int64_t *i_neg, int64_t T,
+                          int32_t n_user_rows, const float **snap)
 {
     SPEX_CHECK_ARG(g && E0 && sum1 && ws && tables, "propagate_plain: NULL argument");
     SPEX_CHECK_ARG(g->n_rows == g->n_cols && L >= 1 && L <= 3, "propagate_plain: square graph, 1 <= L <= 3 (L = %d)", L);
@@ -1121,8 +1228,26 @@ int spex::propagate_plain(const spex_graph_t *g, const float *E0, float *sum1, f
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t sz = (size_t)g->n_rows * d;
-    TimerBracket bracket(g, s);
     tables[0] = sum1; tables[1] = nullptr; tables[2] = nullptr;
+    if (snap) *snap = nullptr;
+    if (snap && u && i_pos && i_neg && n_user_rows >= 0 && n_user_rows <= g->n_rows && step_takes_snapshot(g, d, T)) {
+        const int64_t slots = (3 * T + kWave - 1) / kWave * kWave;      // whole waves: the tail stores without a row test
+        rc = ensure_snap(const_cast<spex_graph *>(g), slots * 64);
+        if (rc) return rc;
+        SnapArgs sa{u, i_pos, i_neg, g->snap, T, n_user_rows, g->n_rows - n_user_rows, 0};
+        TimerBracket bracket(g, s);
+        float *e1 = sum1, *e2 = ws, *e3 = ws + sz;
+        rc = launch_spmm(g, E0, e1, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, s, 1.0f, &sa);             // E^1, and the slots' E^0 rows
+        *snap = g->snap;
+        if (rc || L == 1) return rc;
+        rc = launch_spmm(g, e1, e2, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, s);                         // E^2
+        tables[1] = e2;
+        if (rc || L == 2) return rc;
+        rc = launch_spmm(g, e2, e3, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, s);                         // E^3
+        tables[2] = e3;
+        return rc;
+    }
+    TimerBracket bracket(g, s);
     float *e1 = ws, *e2 = ws + sz;
     rc = launch_spmm(g, E0, L > 1 ? e1 : nullptr, nullptr, 1.0f, E0, sum1, 1.0f, d, s);                     // E^1, sum1 = E^0 + E^1
     if (rc || L == 1) return rc;
