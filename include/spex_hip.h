@@ -664,7 +664,7 @@ enum {
                                          * fork / join on the critical cycle; see spex_dual_task_step_t and spex_dual_task_step_join */
 };
 /* The north-star step — LightGCN L-layer propagation + the fused BPR gather + dot + sigmoid + SGD kernel over T triples — as one
- * call of L + 1 launches: EVERY layer in the plain form (no epilogue operand, one output stream); the layer-1 launch also sets
+ * call of at most L + 1 launches: EVERY whole-graph layer in the plain form (no epilogue operand, one output stream); the layer-1 launch also sets
  * aside, in a tail of ceil(3 T / 1024) extra workgroups, the E^0 rows of the batch's 3 T slots (a buffer owned by the graph handle,
  * grown on the first call at a batch size — make that call outside a stream capture), and the BPR kernel forms the layer mean
  * (((E^0 + E^1) + E^2) + E^3) / (L + 1) — utility1/model.py:94-95, in the fused epilogues' order — at its triples' rows only, the
@@ -674,6 +674,13 @@ enum {
  * sum1 after the call: E^1.  Where the tail would push a layer launch that fits one dispatch round (<= 512 workgroups) over 512,
  * and for T > 2^18, the step keeps layer 1 in the running-sum form instead — then sum1 = E^0 + E^1 and the kernel adds
  * ((sum1 + E^2) + E^3): the same bits.  The schedule depends on the graph and T only.
+ * The LAST layer is not a whole-graph launch where it need not be: for L >= 2, on a graph whose rows all have <= 1024 entries and
+ * while 6 T <= N, the step is L launches — L - 1 whole-graph launches and one that gathers layer L at the batch's <= 3 T slot rows
+ * from the layer-(L-1) table (four triples per workgroup) and runs the BPR update on (((E^0 + E^1) + E^2) + that row) / (L + 1): the
+ * whole-graph launch's rows bit for bit.  The step then traverses (L - 1) nnz stored entries plus the batch rows' (48 % of nnz for
+ * 2048 random triples on Epinion2), and the half of ws that would receive layer L is NOT written (snapshot schedule: ws[1] for
+ * L = 3, ws[0] for L = 2).  That launch keeps a few 8-byte loss cells in the graph handle (one per 16 triples, zero between
+ * launches; grown like the snapshot buffer).  L = 1, graphs with longer rows and larger T keep the L + 1 launches above.
  * d == 64, 1 <= L <= 3, no edge dropout; *loss_sum accumulates the batch's softplus sum.  T == 0 (u, i_pos, i_neg may be NULL): the
  * propagation runs, nothing is updated. */
 int spex_lightgcn_step_bpr_f32(const spex_graph_t *g, float *E0, float *sum1, float *ws, int32_t n_user_rows, int32_t L, int32_t d,

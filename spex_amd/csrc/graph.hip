@@ -68,7 +68,7 @@ extern "C" int spex_graph_destroy(spex_graph_t *g)
     if (!g) return SPEX_OK;
     void *ptrs[] = {g->rowptr, g->col, g->val, g->edge_id, g->seg_beg, g->seg_end, g->long_row, g->long_seg0, g->partial,
                     g->task, g->chunk_off, g->chunk_val, g->chunk_mask, g->chunk_eid, g->chunk_row, g->hub_row, g->hub_seg0, g->row_of, g->tile_row, g->chunk_pad, g->wg_rows,
-                    g->hub_grp, g->hub_fold, g->hub_ticket, g->snap};
+                    g->hub_grp, g->hub_fold, g->hub_ticket, g->snap, g->loss_cell};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (g->scratch_ev) (void)hipEventDestroy(g->scratch_ev);

@@ -151,6 +151,162 @@ __global__ __launch_bounds__(kWave *kScoreWaves) void bpr_layers_kernel(
     if (loss_sum) block_loss_add(lsum, loss_sum);
 }
 
+// bpr_layers_kernel with the LAST layer's rows computed inside the launch: row r of E^L = A E^(L-1) is needed at the batch's <= 3 T
+// slots only, so the step's last whole-graph launch is dropped and its rows are gathered here, from the layer-(L-1) table Xg.
+// A 16-wave workgroup owns kFuseTriples CONSECUTIVE triples = 12 slot rows (slot 3 k + role of the workgroup: triple k's user /
+// positive / negative row).
+//   Phase A  every wave resolves the 12 rows (lane j < 12: slot j; the validity rule of bpr_layers_kernel and snapshot_rows — a
+//            skipped triple has no rows), reads their rowptr, cuts each into 64-entry segments and numbers the segments of the 12
+//            rows consecutively: S <= 192 work items.  Wave w takes items w, w + 16, ...: one fmaf chain from 0 in entry order,
+//            16 independent gathers per batch, straight from the CSR arrays (spmm_rowlist_kernel's loop); the sum goes to LDS.
+//   Phase B  behind ONE barrier that every wave reaches, wave k < kFuseTriples owns triple k: each of its rows is y = seg_0;
+//            y = y + seg_1; ... in segment order (no segment: 0) — the association of spmm_chunk_kernel / spmm_rowlist_kernel for
+//            every row of up to kWgRowMax entries, so y is the whole-graph launch's row bit for bit (graphs with longer rows keep
+//            the whole-graph schedule: spmm.hip, step_fuses_last) — and the row the kernel scores is (((ts + t0) + t1) + y) / div
+//            (SNAP; else ((t0 + t1) + y) / div; t1 may be NULL): bpr_layers_kernel's additions with y in the last table's place.
+//            The ts / t0 / t1 rows are requested in front of Phase A and arrive under its gathers.
+// Every loop bound comes from rowptr or T; no workgroup waits for another.
+// The LOSS is the one place where workgroups meet.  One same-address float atomic per workgroup — 512 of them at T = 2048, four times
+// bpr_layers_kernel's — serialises in the L2: measured +2.3 us on the 37.2 us step (Epinion2, T = 2048; +3.6 us at T = 4096), and four
+// times as many roundings of the running sum put the step's loss outside the 1e-6 the tests hold it to about one run in forty.  So the
+// kFuseGroup = 4 consecutive workgroups of 16 triples (bpr_layers_kernel's loss unit) add their partials into ONE 64-bit cell of the
+// handle (a different address per group: nothing serialises) — fixed point, 2^-24, in the low 48 bits: integer adds, the same sum in any
+// order; arrivals in the bits above — with one returning atomic each, and the group's last arrival clears the cell (every launch finds
+// the cells zero, a graph replay included) and adds the group's sum to *loss_sum: T / 16 float atomics, as in bpr_layers_kernel.
+constexpr int kFuseTriples = 4;
+constexpr int kFuseRows = 3 * kFuseTriples;
+constexpr int kFuseSegs = kFuseRows * kWgWaves;        // 192 segment sums of 256 bytes: 48 KB of LDS
+constexpr int kFuseGroup = 4;                          // workgroups per loss cell
+constexpr float kLossFixScale = 16777216.0f;           // 2^24
+constexpr float kLossFixMax = 1048576.0f;              // 2^20 per workgroup: kFuseGroup of them stay below 2^48 / 2^24
+
+__device__ __forceinline__ void group_loss_add(float wave_partial, float *loss_sum, unsigned long long *cells)
+{
+    __shared__ float s_part[kScoreWaves];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    if (lane == 0) s_part[wave] = wave_partial;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.0f;
+#pragma unroll
+        for (int w = 0; w < kFuseTriples; ++w) t += s_part[w];
+        unsigned long long fx = 0ull;
+        if (t <= kLossFixMax) fx = (unsigned long long)(t * kLossFixScale + 0.5f);     // (a softplus sum: >= 0)
+        else atomicAdd(loss_sum, t);                    // NaN, inf or beyond the fixed-point range: straight to the accumulator
+        const unsigned grp = blockIdx.x / kFuseGroup;
+        const unsigned left = gridDim.x - grp * kFuseGroup, members = left < (unsigned)kFuseGroup ? left : (unsigned)kFuseGroup;
+        const unsigned long long old = __hip_atomic_fetch_add(cells + grp, fx + (1ull << 48), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)(old >> 48) + 1u == members) {
+            __hip_atomic_store(cells + grp, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long total = (old & ((1ull << 48) - 1ull)) + fx;
+            atomicAdd(loss_sum, (float)total * (1.0f / kLossFixScale));
+        }
+    }
+}
+template <bool SNAP>
+__global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, const float *__restrict__ Xg,
+    const float *__restrict__ ts, const float *__restrict__ t0, const float *__restrict__ t1, float div, float *table_w,
+    const int64_t *__restrict__ u_idx, const int64_t *__restrict__ p_idx, const int64_t *__restrict__ n_idx, int64_t T,
+    int64_t n_user_rows, int64_t n_item_rows, float a_coef, float b_coef, float *loss_sum, unsigned long long *loss_cells)
+{
+    __shared__ float s_seg[kFuseSegs][kWave];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t t_first = (int64_t)blockIdx.x * kFuseTriples;
+    int my_row = -1, my_beg = 0, my_deg = 0;
+    if (lane < kFuseRows) {
+        const int k = lane / 3, role = lane - 3 * k;
+        const int64_t t = t_first + k;
+        if (t < T) {
+            const int64_t u = u_idx[t], ip = p_idx[t], in = n_idx[t];
+            if (u >= 0 && u < n_user_rows && ip >= 0 && ip < n_item_rows && in >= 0 && in < n_item_rows) {
+                my_row = role == 0 ? (int)u : (int)(n_user_rows + (role == 1 ? ip : in));
+                my_beg = rowptr[my_row];
+                my_deg = rowptr[my_row + 1] - my_beg;
+            }
+        }
+    }
+    int my_nseg = (my_deg + kTaskEntries - 1) / kTaskEntries;
+    if (my_nseg > kWgWaves) my_nseg = kWgWaves;        // (never on a graph the step sends here; keeps s_seg's bound local)
+    int my_pre = 0;                                    // lane j: segments of the rows in front of row j; lane 12: all of them
+#pragma unroll
+    for (int j = 0; j < kFuseRows; ++j) {
+        const int n = __builtin_amdgcn_readlane(my_nseg, j);
+        if (lane > j) my_pre += n;
+    }
+    const int S = __builtin_amdgcn_readlane(my_pre, kFuseRows);
+
+    // Phase B's operands, requested now
+    const int ru = __builtin_amdgcn_readlane(my_row, 3 * (wave & (kFuseTriples - 1)));
+    const int rp = __builtin_amdgcn_readlane(my_row, 3 * (wave & (kFuseTriples - 1)) + 1);
+    const int rn = __builtin_amdgcn_readlane(my_row, 3 * (wave & (kFuseTriples - 1)) + 2);
+    const bool own = wave < kFuseTriples && ru >= 0;   // wave-uniform
+    const size_t ou = (size_t)(own ? ru : 0) * kWave + lane, op = (size_t)(own ? rp : 0) * kWave + lane, on = (size_t)(own ? rn : 0) * kWave + lane;
+    float uu = 0.0f, vp = 0.0f, vn = 0.0f, u0 = 0.0f, p0 = 0.0f, n0 = 0.0f, u1 = 0.0f, p1 = 0.0f, n1 = 0.0f;
+    if (own) {
+        const int64_t t = t_first + wave;
+        if (SNAP) { uu = ts[(size_t)t * kWave + lane]; vp = ts[(size_t)(T + t) * kWave + lane]; vn = ts[(size_t)(2 * T + t) * kWave + lane]; }
+        u0 = t0[ou]; p0 = t0[op]; n0 = t0[on];
+        if (t1) { u1 = t1[ou]; p1 = t1[op]; n1 = t1[on]; }
+    }
+
+    const float *__restrict__ Xl = Xg + lane;
+    for (int w = wave; w < S; w += kScoreWaves) {
+        // item w belongs to row j = the number of rows 1..11 whose first item is <= w (rows without segments share their successor's)
+        const int j = __popcll(__ballot(lane >= 1 && lane < kFuseRows && my_pre <= w));
+        const int sgi = w - __builtin_amdgcn_readlane(my_pre, j);
+        const int left = __builtin_amdgcn_readlane(my_deg, j) - sgi * kTaskEntries;
+        const int e0 = __builtin_amdgcn_readlane(my_beg, j) + sgi * kTaskEntries;
+        const int cnt = left < kTaskEntries ? left : kTaskEntries;
+        int my_col = 0;
+        float my_val = 0.0f;
+        if (lane < cnt) {
+            my_col = col[e0 + lane];
+            my_val = val[e0 + lane];
+        }
+        // entries past the segment's end: value 0 on the segment's last real source row (a line already being fetched)
+        const int last_col = __builtin_amdgcn_readlane(my_col, (cnt - 1) & 63);
+        if (lane >= cnt) my_col = last_col;
+        float acc = 0.0f;
+        for (int c = 0; c * kChunk < cnt; ++c) {
+            float x[kChunk];
+#pragma unroll
+            for (int k = 0; k < kChunk; ++k)
+                x[k] = Xl[(size_t)(uint32_t)__builtin_amdgcn_readlane(my_col, c * kChunk + k) * 64];
+#pragma unroll
+            for (int k = 0; k < kChunk; ++k) acc = fmaf(lane_bcast_f(my_val, c * kChunk + k), x[k], acc);
+        }
+        s_seg[w][lane] = acc;
+    }
+    __syncthreads();
+
+    float lsum = 0.0f;
+    if (own) {
+        float y[3];
+#pragma unroll
+        for (int role = 0; role < 3; ++role) {
+            const int j = 3 * wave + role;
+            const int n = __builtin_amdgcn_readlane(my_nseg, j), first = __builtin_amdgcn_readlane(my_pre, j);
+            float v = 0.0f;
+            if (n > 0) v = s_seg[first][lane];
+            for (int i = 1; i < n; ++i) v = v + s_seg[first + i][lane];    // segment order
+            y[role] = v;
+        }
+        if (SNAP) { uu = uu + u0; vp = vp + p0; vn = vn + n0; } else { uu = u0; vp = p0; vn = n0; }
+        if (t1) { uu = uu + u1; vp = vp + p1; vn = vn + n1; }
+        uu = uu + y[0]; vp = vp + y[1]; vn = vn + y[2];
+        if (div != 1.0f) { uu = uu / div; vp = vp / div; vn = vn / div; }
+        const float x = wave_sum(uu * vn) - wave_sum(uu * vp);   // neg_score - pos_score
+        lsum = softplus_f(x);
+        const float a = a_coef * sigmoid_f(x);
+        atomicAdd(table_w + ou, a * (vn - vp) + b_coef * uu);
+        atomicAdd(table_w + op, -a * uu + b_coef * vp);
+        atomicAdd(table_w + on, a * uu + b_coef * vn);
+    }
+    if (loss_sum) group_loss_add(lsum, loss_sum, loss_cells);
+}
+
 __global__ __launch_bounds__(kWave *kScoreWaves) void bpr_kernel(
     const float *__restrict__ U_read, const float *__restrict__ I_read, float *U_w, float *I_w,
     const int64_t *__restrict__ u_idx, const int64_t *__restrict__ p_idx, const int64_t *__restrict__ n_idx, int64_t T,
@@ -631,6 +787,53 @@ int spex::bpr_sgd_layers(const float *snap, const float *t0, const float *t1, co
     else
         hipLaunchKernelGGL(bpr_layers_kernel<false>, dim3(grid_for(T)), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, snap, t0, t1, t2, div,
                            table_w, u, i_pos, i_neg, T, n_user_rows, n_item_rows, -lr / (float)T, -lr * reg / (float)T, loss_sum);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
+
+// The fused launch's loss cells (group_loss_add): one per kFuseGroup workgroups, zero between launches; grown on demand like the
+// handle's snapshot buffer (allocates: the first call at a batch size, outside any stream capture) and shared like it — one step at a
+// time per handle.
+static int ensure_loss_cells(spex_graph *g, int64_t n)
+{
+    if (n <= g->loss_cell_cap) return SPEX_OK;
+    SPEX_HIP(hipDeviceSynchronize());
+    if (g->loss_cell) SPEX_HIP(hipFree(g->loss_cell));
+    g->loss_cell = nullptr;
+    g->loss_cell_cap = 0;
+    n = (n + 1023) / 1024 * 1024;
+    SPEX_HIP(hipMalloc((void **)&g->loss_cell, (size_t)n * sizeof(unsigned long long)));
+    SPEX_HIP(hipMemset(g->loss_cell, 0, (size_t)n * sizeof(unsigned long long)));
+    SPEX_HIP(hipDeviceSynchronize());                  // (the launch may sit on a stream that does not wait for the null stream)
+    g->loss_cell_cap = n;
+    return SPEX_OK;
+}
+
+// bpr_sgd_layers with the last addend gathered in the launch: row r = (((snap +) t0 (+ t1)) + (A Xg)[r]) / div at the triples' rows.
+// The caller (spex_lightgcn_step_bpr_f32) sends only graphs whose rows all fit one workgroup (g->n_hub == 0) and no edge dropout.
+int spex::bpr_sgd_fused_last(const spex_graph_t *g, const float *Xg, const float *snap, const float *t0, const float *t1, float div,
+                             float *table_w, int64_t n_user_rows, int64_t n_item_rows, const int64_t *u, const int64_t *i_pos,
+                             const int64_t *i_neg, int64_t T, float lr, float reg, float *loss_sum, void *stream)
+{
+    SPEX_CHECK_ARG(g && Xg && t0 && table_w && T >= 0 && (T == 0 || (u && i_pos && i_neg)) && div != 0.0f, "bpr_sgd_fused_last: bad argument");
+    SPEX_CHECK_ARG(g->n_hub == 0 && g->mask_mode == 0 && n_user_rows >= 0 && n_item_rows >= 0 && n_user_rows + n_item_rows <= g->n_rows,
+                   "bpr_sgd_fused_last: a graph without hub rows or edge dropout, tables within its %d rows", g->n_rows);
+    SPEX_CHECK_ARG(table_w != Xg && table_w != t0 && table_w != t1 && table_w != snap, "bpr_sgd_fused_last: the updated table must not be a read table");
+    if (T == 0) return SPEX_OK;
+    const int64_t blocks = (T + kFuseTriples - 1) / kFuseTriples;
+    SPEX_CHECK_ARG(blocks <= 0x7fffffff, "bpr_sgd_fused_last: T = %lld", (long long)T);
+    if (loss_sum) {
+        const int rc = ensure_loss_cells(const_cast<spex_graph *>(g), (blocks + kFuseGroup - 1) / kFuseGroup);
+        if (rc) return rc;
+    }
+    if (snap)
+        hipLaunchKernelGGL(bpr_fused_last_kernel<true>, dim3((unsigned)blocks), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, g->rowptr, g->col,
+                           g->val, Xg, snap, t0, t1, div, table_w, u, i_pos, i_neg, T, n_user_rows, n_item_rows, -lr / (float)T, -lr * reg / (float)T,
+                           loss_sum, g->loss_cell);
+    else
+        hipLaunchKernelGGL(bpr_fused_last_kernel<false>, dim3((unsigned)blocks), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, g->rowptr, g->col,
+                           g->val, Xg, snap, t0, t1, div, table_w, u, i_pos, i_neg, T, n_user_rows, n_item_rows, -lr / (float)T, -lr * reg / (float)T,
+                           loss_sum, g->loss_cell);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

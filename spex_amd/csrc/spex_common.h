@@ -66,8 +66,13 @@ int score_bce_slots_rows(const float *users, const float *items, int32_t ldu, in
                          float grad_scale, float *grad_slots, int32_t ld_slots, void *stream);     // score.hip: per-sample rows + losses
 int propagate_plain(const spex_graph_t *g, const float *E0, float *sum1, float *ws, int32_t L, int32_t d, void *stream,
                     const float **tables, const int64_t *u = nullptr, const int64_t *i_pos = nullptr, const int64_t *i_neg = nullptr,
-                    int64_t T = 0, int32_t n_user_rows = 0, const float **snap = nullptr);
-                                              // spmm.hip: L launches, the layer mean left to the consumer (*snap, tables[0..2]: L + 1 addends)
+                    int64_t T = 0, int32_t n_user_rows = 0, const float **snap = nullptr, const float **last_src = nullptr);
+                                              // spmm.hip: L launches, the layer mean left to the consumer (*snap, tables[0..2]: L + 1 addends);
+                                              // *last_src != NULL on return: L - 1 launches, the consumer gathers layer L from that table
+int bpr_sgd_fused_last(const spex_graph_t *g, const float *Xg, const float *snap, const float *t0, const float *t1, float div,
+                       float *table_w, int64_t n_user_rows, int64_t n_item_rows, const int64_t *u, const int64_t *i_pos,
+                       const int64_t *i_neg, int64_t T, float lr, float reg, float *loss_sum,
+                       void *stream);             // score.hip: bpr_sgd_layers with the last addend (A Xg at the triples' rows) gathered in the launch
 int bpr_sgd_layers(const float *snap, const float *t0, const float *t1, const float *t2, float div, float *table_w, int64_t n_user_rows,
                    int64_t n_item_rows, const int64_t *u, const int64_t *i_pos, const int64_t *i_neg, int64_t T, float lr, float reg,
                    float *loss_sum, void *stream);    // score.hip: the fused BPR-SGD kernel reading rows as (((snap +) t0 + t1) + t2) / div
@@ -278,6 +283,8 @@ struct spex_graph {
     int64_t partial_cap = 0;      // floats
     float *snap = nullptr;        // [snap_cap] scratch of the one-call BPR step: the E^0 rows of its triples (spmm.hip: SnapArgs), grown on demand
     int64_t snap_cap = 0;         // floats
+    unsigned long long *loss_cell = nullptr;   // [loss_cell_cap] loss cells of the one-call BPR step's fused launch (score.hip: group_loss_add), zero between launches
+    int64_t loss_cell_cap = 0;
     // The scratch is the one piece of a handle that launches WRITE.  Calls on one stream are ordered by the stream; a call
     // on another stream first waits (event) for everything queued on the stream that used the scratch last — so two streams
     // may share a handle, and so may two HOST threads: a launch that writes the scratch holds scratch_mu from the ordering

@@ -1206,6 +1206,29 @@ bool step_takes_snapshot(const spex_graph *g, int32_t d, int64_t T)
     return !(table <= kOneRoundWgs && table + tail > kOneRoundWgs);
 }
 
+// Whether a one-call BPR step leaves its LAST layer to the BPR launch (bpr_fused_last_kernel, score.hip: layer L gathered at the
+// triples' <= 3 T slot rows from the layer-(L-1) table, inside the BPR launch) — decided from the graph, L and T only.  Never for
+// L == 1 (its last layer gathers from E^0, which that launch updates), never on a graph with hub rows (rows beyond kWgRowMax entries
+// are summed by groups in the chunk kernel: segment order would not give the same bits) or without the chunk table (the generic
+// kernel's order).  The fused launch gathers every slot's row, duplicates included, so beyond some T it does more work than a
+// whole-graph layer: it is taken while kFusedRowsPerTriple * T <= n_rows.  (SPEX_STEP_FUSED_LAST=0 / 1 forces either form wherever
+// both are legal.)  The constant is fixed from tools/fused_last_time.py on Epinion2 (15 593 rows: T <= 2 598), MI355X, both forms
+// forced, us per step whole-graph / fused (profiles/fused_last/t_sweep.jsonl):
+//   L = 3   T = 256  38.7 / 33.8   1024  39.0 / 33.5   2048  39.7 / 35.7   2304  40.1 / 38.5   2560  40.6 / 39.6   3072  41.4 / 41.9
+//           4096  42.7 / 44.1   8192  48.7 / 61.1
+//   L = 2   T = 256  27.3 / 21.5   1024  27.7 / 22.6   2048  28.5 / 24.1   2304  28.7 / 28.4   2560  29.3 / 28.6   3072  29.9 / 30.7
+//           4096  31.3 / 34.4   8192  36.9 / 49.6
+// (the step beyond T = 2048 is the fused launch's second dispatch round: more than 512 workgroups of four triples).
+constexpr int64_t kFusedRowsPerTriple = 6;
+bool step_fuses_last(const spex_graph *g, int32_t d, int32_t L, int64_t T)
+{
+    if (d != 64 || L < 2 || g->task == nullptr || g->mask_mode != 0 || g->n_hub != 0 || g->n_rows == 0 || T <= 0) return false;
+    const char *sw = getenv("SPEX_STEP_FUSED_LAST");
+    if (sw && sw[0] == '0') return false;
+    if (sw && sw[0] == '1') return true;
+    return kFusedRowsPerTriple * T <= (int64_t)g->n_rows;
+}
+
 }  // namespace
 
 // The propagation with the layer mean LEFT TO THE CONSUMER (the fused BPR step reads the propagated table at its triples' rows
@@ -1217,10 +1240,13 @@ bool step_takes_snapshot(const spex_graph *g, int32_t d, int64_t T)
 //   fallback  (no triples given, or the tail would push a one-round launch over 512 workgroups) layer 1 in the running-sum form —
 //             sum1 = E^0 + E^1 over the whole table, +2.9 us on Epinion2 —, the later layers plain into the halves of ws:
 //             (*snap = NULL, sum1, E^2, E^3).
-// One timer bracket (the profiling hook) spans the L launches like spex_propagate_f32's.
+// With last_src given and step_fuses_last() true, either schedule stops one launch short: L - 1 launches, *last_src = the layer-(L-1)
+// table (E^1 for L = 2, E^2 for L = 3), tables[] lists the L - 1 layers in front, and the consumer gathers layer L at its rows
+// (spex::bpr_sgd_fused_last).  sum1 keeps its content on both schedules.
+// One timer bracket (the profiling hook) spans the whole-graph launches like spex_propagate_f32's.
 int spex::propagate_plain(const spex_graph_t *g, const float *E0, float *sum1, float *ws, int32_t L, int32_t d, void *stream,
                           const float **tables, const int64_t *u, const int64_t *i_pos, const int64_t *i_neg, int64_t T,
-                          int32_t n_user_rows, const float **snap)
+                          int32_t n_user_rows, const float **snap, const float **last_src)
 {
     SPEX_CHECK_ARG(g && E0 && sum1 && ws && tables, "propagate_plain: NULL argument");
     SPEX_CHECK_ARG(g->n_rows == g->n_cols && L >= 1 && L <= 3, "propagate_plain: square graph, 1 <= L <= 3 (L = %d)", L);
@@ -1230,6 +1256,9 @@ int spex::propagate_plain(const spex_graph_t *g, const float *E0, float *sum1, f
     const size_t sz = (size_t)g->n_rows * d;
     tables[0] = sum1; tables[1] = nullptr; tables[2] = nullptr;
     if (snap) *snap = nullptr;
+    if (last_src) *last_src = nullptr;
+    // (the consumer gathers layer L itself: one launch fewer, on either schedule; that layer's half of ws is not written)
+    const bool fuse = last_src && u && i_pos && i_neg && n_user_rows >= 0 && n_user_rows <= g->n_rows && step_fuses_last(g, d, L, T);
     if (snap && u && i_pos && i_neg && n_user_rows >= 0 && n_user_rows <= g->n_rows && step_takes_snapshot(g, d, T)) {
         const int64_t slots = (3 * T + kWave - 1) / kWave * kWave;      // whole waves: the tail stores without a row test
         rc = ensure_snap(const_cast<spex_graph *>(g), slots * 64);
@@ -1240,9 +1269,11 @@ int spex::propagate_plain(const spex_graph_t *g, const float *E0, float *sum1, f
         rc = launch_spmm(g, E0, e1, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, s, 1.0f, &sa);             // E^1, and the slots' E^0 rows
         *snap = g->snap;
         if (rc || L == 1) return rc;
+        if (fuse && L == 2) { *last_src = e1; return rc; }
         rc = launch_spmm(g, e1, e2, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, s);                         // E^2
         tables[1] = e2;
         if (rc || L == 2) return rc;
+        if (fuse) { *last_src = e2; return rc; }
         rc = launch_spmm(g, e2, e3, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, s);                         // E^3
         tables[2] = e3;
         return rc;
@@ -1251,9 +1282,11 @@ int spex::propagate_plain(const spex_graph_t *g, const float *E0, float *sum1, f
     float *e1 = ws, *e2 = ws + sz;
     rc = launch_spmm(g, E0, L > 1 ? e1 : nullptr, nullptr, 1.0f, E0, sum1, 1.0f, d, s);                     // E^1, sum1 = E^0 + E^1
     if (rc || L == 1) return rc;
+    if (fuse && L == 2) { *last_src = e1; return rc; }
     rc = launch_spmm(g, e1, e2, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, s);                                 // E^2
     tables[1] = e2;
     if (rc || L == 2) return rc;
+    if (fuse) { *last_src = e2; return rc; }
     rc = launch_spmm(g, e2, e1, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, s);                                 // E^3 (E^1 is dead: in sum1)
     tables[2] = e1;
     return rc;

@@ -160,7 +160,15 @@ extern "C" int spex_ngcf_epoch_bce_f32(spex_ngcf_step_t *s, const int64_t *users
     return rc;
 }
 
-// The north-star step — 3-layer propagation + fused BPR-SGD over a batch of triples — as ONE call of L + 1 launches with the
+// The north-star step — 3-layer propagation + fused BPR-SGD over a batch of triples — as ONE call.  For L >= 2, on a graph without
+// rows beyond 1 024 entries and while 6 T <= N (spmm.hip: step_fuses_last; SPEX_STEP_FUSED_LAST=0 / 1 forces either form), it is L
+// launches: L - 1 whole-graph plain launches (the first with the snapshot tail described below) and ONE launch that gathers layer L
+// at the batch's <= 3 T slot rows from the layer-(L-1) table — four triples per workgroup, segment-parallel over its 16 waves — and
+// runs the BPR update on (((E^0 + E^1) + E^2) + y) / (L + 1), y the gathered row: the whole-graph launch's row bit for bit
+// (score.hip: bpr_fused_last_kernel).  The step then traverses (L - 1) nnz entries plus the batch rows' entries; the half of ws
+// that used to receive layer L is not written (L = 3: ws[1]; L = 2: ws[0]; on the running-sum fallback L = 2: ws[1], L = 3: none —
+// ws[0] keeps E^1).  sum1 is unchanged by this.  Otherwise (L = 1, hub rows, larger T) it is today's schedule:
+// ONE call of L + 1 launches with the
 // layer mean left to the BPR kernel: EVERY layer in the plain form, the layer-1 launch also setting aside the E^0 rows of the
 // batch's <= 3 T slots (a tail of workgroups inside the launch: spex::propagate_plain), and the fused gather + dot + sigmoid + SGD
 // kernel forms (((E^0 + E^1) + E^2) + E^3) / (L + 1) at its triples' rows only — the rows of the propagated table the step reads.
@@ -179,8 +187,11 @@ extern "C" int spex_lightgcn_step_bpr_f32(const spex_graph_t *g, float *E0, floa
         spex::set_error("spex_lightgcn_step_bpr_f32: d == 64 and 1 <= L <= 3 only (d = %d, L = %d): use spex_propagate_f32 + spex_bpr_sgd_step_f32", d, L);
         return SPEX_ERR_UNSUPPORTED;
     }
-    const float *tables[3], *snap = nullptr;
-    SPEX_TRY(spex::propagate_plain(g, E0, sum1, ws, L, d, stream, tables, u, i_pos, i_neg, T, n_user_rows, &snap));
+    const float *tables[3], *snap = nullptr, *last_src = nullptr;
+    SPEX_TRY(spex::propagate_plain(g, E0, sum1, ws, L, d, stream, tables, u, i_pos, i_neg, T, n_user_rows, &snap, &last_src));
+    if (last_src)
+        return spex::bpr_sgd_fused_last(g, last_src, snap, tables[0], tables[1], (float)(L + 1), E0, n_user_rows, (int64_t)g->n_rows - n_user_rows,
+                                        u, i_pos, i_neg, T, lr, reg, loss_sum, stream);
     return spex::bpr_sgd_layers(snap, tables[0], tables[1], tables[2], (float)(L + 1), E0, n_user_rows, (int64_t)g->n_rows - n_user_rows, u,
                                 i_pos, i_neg, T, lr, reg, loss_sum, stream);
 }

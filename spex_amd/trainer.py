@@ -228,12 +228,16 @@ class LightGCNStepper:
 
     def step_bpr_sgd(self, users, pos, neg, lr=None, reg=0.0):
         """Propagation + fused BPR-SGD kernel (scores from the propagated table, update on E0).  Returns the running
-        loss-sum buffer `loss_acc` (sum over every triple since it was last zeroed; no per-step allocation or sync)."""
+        loss-sum buffer `loss_acc` (sum over every triple since it was last zeroed; no per-step allocation or sync).
+        On the one-call path (d = 64, 1 <= L <= 3, no edge dropout, T below the grouped form's threshold) the step is L launches
+        where L >= 2, no row of the graph has more than 1 024 entries and 6 T <= N: the last layer is gathered at the batch's rows
+        inside the BPR launch, and the half of `ws_fwd` that layer used to fill is left untouched; L + 1 launches otherwise
+        (SPEX_STEP_FUSED_LAST=0 / 1 forces either form)."""
         T = users.numel()
         if (1 <= self.L <= 3 and self.E0.shape[1] == 64 and getattr(self.graph, "mask_mode", 0) == 0 and T < ops.GROUPED_BPR_MIN_TRIPLES
                 and all(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() for t in (users, pos, neg))):
-            # one native call, L + 1 launches: the layer mean is formed by the BPR kernel at its triples' rows only, so every
-            # whole-graph launch runs in the plain form (spex_lightgcn_step_bpr_f32).  self.light_out then holds E^1 (E^0 + E^1
+            # one native call, L or L + 1 launches: the layer mean is formed by the BPR kernel at its triples' rows only, so every
+            # whole-graph launch runs in the plain form, and the last layer need not be one (spex_lightgcn_step_bpr_f32).  self.light_out then holds E^1 (E^0 + E^1
             # where the step keeps its running-sum schedule: include/spex_hip.h), not the propagated table.
             p = lambda t: ctypes.c_void_p(t.data_ptr())
             _launch(self.E0.device, "spex_lightgcn_step_bpr_f32", self.graph._h, p(self.E0), p(self.light_out), p(self.ws_fwd), self.n_u,
