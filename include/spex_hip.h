@@ -392,6 +392,31 @@ int spex_lightgcn_batch_slots_f32(const spex_graph_t *g, const float *X, const f
                                   const int64_t *items, const float *labels, int32_t B, int32_t n_user_rows, float grad_scale,
                                   float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream);
 
+/* The batch-sized middle of the exact BPR step as ONE launch — the three-row sibling of spex_lightgcn_batch_f32, d == 64 ONLY
+ * (d = 128 / 256 are rejected: they keep the launch-by-launch form).  Triple t has rows u = users[t], p = n_user_rows + pos[t],
+ * n = n_user_rows + neg[t]:
+ *   light_r = (acc_in[r] + (A X)[r]) / acc_div for the three rows (bit-identical to spex_spmm_f32 / spex_spmm_rowlist_f32 for rows
+ *             of <= 1 024 entries, also under an edge mask on the handle)
+ *   xp = <light_u, light_p>, xn = <light_u, light_n>, z = xn - xp;  dg = sigmoid(z) * grad_scale
+ *   loss_t = max(z, 0) + log1p(exp(-|z|)) [+ 0.5 * weight_decay * (|E0[u]|^2 + |E0[p]|^2 + |E0[n]|^2) when weight_decay > 0]
+ *   loss_per_sample[t] = loss_t if loss_per_sample != NULL, else *loss_sum += loss_t (one atomic per triple)
+ *   g_u = dg (light_n - light_p), g_p = -dg light_u, g_n = dg light_u
+ *   g_out[r] += g_r where g_out != NULL;  G[r] += push_scale g_r, G[col[e]] += push_scale val[e] g_r over the stored entries of
+ *   the three rows of `g` (the push form of A^T g) where G != NULL (at least one of the two).  Both are accumulated into: zero them first.
+ *   row_counts != NULL (int32 [N]): row_counts[r] += 1 per occurrence of r in the batch — the weight of the L2 gradient
+ *   weight_decay / T * E0[r], which the caller's optimizer pass applies.  E0 may be NULL when weight_decay == 0.
+ * A triple with any index out of range is skipped whole: loss 0, no gradient, no count. */
+int spex_lightgcn_bpr_batch_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div, const int64_t *users,
+                                const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows, float grad_scale,
+                                float push_scale, float weight_decay, const float *E0, int32_t *row_counts, float *loss_sum,
+                                float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream);
+/* The same launch without the push and without any float atomic (the deterministic step):
+ *   grad_slots[t] = g_u, grad_slots[T + t] = g_p, grad_slots[2 T + t] = g_n   ([3 T, 64], plain stores; skipped triples: zeros) */
+int spex_lightgcn_bpr_batch_slots_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div, const int64_t *users,
+                                      const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows, float grad_scale,
+                                      float weight_decay, const float *E0, int32_t *row_counts, float *loss_sum, float *loss_per_sample,
+                                      float *grad_slots, int32_t d, void *stream);
+
 /* Deterministic accumulation of a batch's per-slot rows into a dense [n_rows, d] table — replaces the float atomics of the row-
  * sparse backward where results must repeat bit for bit (and follows the order of the reference's CPU `index_put_(accumulate)` /
  * index_select backward, LightGCN_SPEX/code/utility1/model.py:115-116 and NGCF_SPEX/code/main_rec.py:89-90 under autograd):
@@ -660,8 +685,11 @@ enum {
     SPEX_STEP_DETERMINISTIC = 1,        /* fixed summation order everywhere (see above) */
     SPEX_STEP_FIXED_TASK_WEIGHTS = 2,   /* dual-task step only: loss = loss1 + loss2 (LightGCN_SPEX/code/main_11.py:69) instead of the
                                          * uncertainty weighting of main_auto_expert_s.py:78-82; task_weights are left untouched */
-    SPEX_STEP_PIPELINED = 4             /* dual-task step only, with side_stream: the Adam pass split by owner over the two streams, no
+    SPEX_STEP_PIPELINED = 4,            /* dual-task step only, with side_stream: the Adam pass split by owner over the two streams, no
                                          * fork / join on the critical cycle; see spex_dual_task_step_t and spex_dual_task_step_join */
+    SPEX_STEP_BPR_DENSE = 8,            /* exact BPR step only: force the dense form of the fast path (gradient rows into g_out, all-pull
+                                         * backward) ... */
+    SPEX_STEP_BPR_PUSH = 16             /* ... or the push form, whatever T; neither flag: chosen by T (see spex_lightgcn_step_bpr_adam_f32) */
 };
 /* The north-star step — LightGCN L-layer propagation + the fused BPR gather + dot + sigmoid + SGD kernel over T triples — as one
  * call of at most L + 1 launches: EVERY whole-graph layer in the plain form (no epilogue operand, one output stream); the layer-1 launch also sets
@@ -695,6 +723,9 @@ typedef struct spex_lightgcn_step {
     float lr, beta1, beta2, eps;
     int32_t t;
     int32_t flags;                           /* SPEX_STEP_DETERMINISTIC */
+    /* appended for spex_lightgcn_step_bpr_adam_f32 / spex_lightgcn_epoch_bpr_f32 (the BCE entry points never read them): */
+    float weight_decay;                      /* >= 0: upstream LightGCN's L2 term on the E0 rows of the batch */
+    int32_t *row_counts;                     /* [2, N] int32, all-zero before the first call: per-row occurrence counts, by step parity */
 } spex_lightgcn_step_t;
 int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *step, const int64_t *users, const int64_t *items, const float *labels,
                                int32_t B, float *loss_sum, void *stream);
@@ -706,6 +737,33 @@ int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *step, const int64_t *users,
  * handles are left unmasked.  (The descriptor's graph handles are modified by that: not const here.) */
 int spex_lightgcn_epoch_bce_f32(spex_lightgcn_step_t *step, const int64_t *users, const int64_t *items, const float *labels, int64_t n,
                                 int32_t B, int64_t max_steps, float keep_prob, uint32_t drop_seed, float *loss_full, float *loss_ragged,
+                                void *stream);
+
+/* The exact BPR training step — upstream LightGCN's training semantics: BPR differentiated through the propagation, an L2 term on
+ * the E0 rows of the batch, Adam — as ONE call with the schedule of spex_lightgcn_step_bce_f32 and the triple-shaped batch kernel
+ * (spex_lightgcn_bpr_batch_f32) in the middle.  d == 64 ONLY (any other width is rejected: d = 128 / 256 keep the launch-by-launch
+ * form); the descriptor's buffers as for the BCE step, with slot_capacity >= 3 T and row_counts [2, N] int32 (all-zero before the
+ * first call; every call leaves the table of the next step's parity all-zero).
+ *   loss = mean_t softplus(xn_t - xp_t) + weight_decay * 0.5 * sum_t (|E0[u_t]|^2 + |E0[p_t]|^2 + |E0[n_t]|^2) / T
+ *   fast path: L-1 x spex_spmm_f32 (plain for L <= 3) -> spex_lightgcn_bpr_batch_f32 -> L-1 x spex_spmm_f32 on A^T (all plain at
+ *   L == 3) -> Adam (sums the per-triple losses in order, adds the L2 gradient): 2 L launches.  From 768 triples up (measured on Epinion2;
+ *   SPEX_STEP_BPR_DENSE / SPEX_STEP_BPR_PUSH force either form) the same batch launch skips the push — its gradient rows go to the
+ *   dense g_out with atomics — and spex_propagate_bwd_f32 runs the whole backward in pull form.
+ *   SPEX_STEP_DETERMINISTIC: spex_lightgcn_bpr_batch_slots_f32 -> spex_reduce_slots_f32 (users; then pos and neg) ->
+ *   spex_propagate_bwd_f32 -> Adam; no float atomic, two runs from one state are bit-identical.
+ * The L2 gradient weight_decay / T * E0[r] per occurrence of row r in the batch is not propagated: the batch kernel counts the
+ * occurrences (integer atomics) in row_counts[(t + 1) & 1] and the Adam pass adds count * E0 and clears the other table.
+ * users / pos / neg: device int64[T] (items index the item block); a triple with any index out of range is skipped whole.
+ * *loss_sum accumulates the batch's loss SUM (softplus plus the L2 share).  grad_E0 holds the step's whole gradient afterwards.
+ * Edge dropout: the rules and argument checks of the BCE step (same mask on both handles, graph_t the transposed handle, L >= 2).
+ * t is advanced only when every launch of the step was queued. */
+int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *step, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
+                                    float *loss_sum, void *stream);
+/* An epoch of pre-drawn, device-resident triples as ONE call: batch k = triples [k T, min((k+1) T, n)) through
+ * spex_lightgcn_step_bpr_adam_f32 (at most max_steps batches; < 0: all); loss_full / loss_ragged, keep_prob and the mask keying
+ * ((drop_seed << 32) | (k + 1)) as in spex_lightgcn_epoch_bce_f32; the handles are left unmasked. */
+int spex_lightgcn_epoch_bpr_f32(spex_lightgcn_step_t *step, const int64_t *users, const int64_t *pos, const int64_t *neg, int64_t n,
+                                int32_t T, int64_t max_steps, float keep_prob, uint32_t drop_seed, float *loss_full, float *loss_ragged,
                                 void *stream);
 
 /* The single-layer NGCF training step (NGCF_SPEX/code/main_rec.py:122-128 with the default --layer_size [64]) as one call:

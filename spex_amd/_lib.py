@@ -75,6 +75,10 @@ SIGNATURES = {
                                                c_vp, c_i32, c_vp]),
     "spex_lightgcn_batch_slots_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp,
                                                      c_i32, c_vp]),
+    "spex_lightgcn_bpr_batch_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp,
+                                                   c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "spex_lightgcn_bpr_batch_slots_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp,
+                                                         c_vp, c_vp, c_vp, c_i32, c_vp]),
     "spex_reduce_slots_f32": (ctypes.c_int, [c_vp, c_i32, c_i64, c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_f32, c_vp, c_i32, c_i32, c_vp]),
     "spex_expert_gate_rows_bwd_parts": (c_i32, [c_i32]),
     "spex_expert_gate_rows_bwd_det_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i32, c_i64, c_i64, c_i64, c_i32,
@@ -113,6 +117,9 @@ SIGNATURES = {
     "spex_lightgcn_step_bce_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "spex_lightgcn_epoch_bce_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_f32, ctypes.c_uint32, c_vp, c_vp,
                                                    c_vp]),
+    "spex_lightgcn_step_bpr_adam_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "spex_lightgcn_epoch_bpr_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_f32, ctypes.c_uint32, c_vp, c_vp,
+                                                   c_vp]),
     "spex_ngcf_step_bce_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "spex_ngcf_epoch_bce_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "spex_dual_task_step_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
@@ -142,12 +149,15 @@ class LightGCNStepDesc(ctypes.Structure):
     _fields_ = ([(n, c_vp) for n in ("graph", "graph_t", "E0", "m", "v", "light_out", "ws_fwd", "lo_batch", "g_out", "ws_bwd",
                                      "grad_E0", "grad_slots")]
                 + [(n, c_i32) for n in ("slot_capacity", "n_user_rows", "L", "d")]
-                + [(n, c_f32) for n in ("lr", "beta1", "beta2", "eps")] + [("t", c_i32), ("flags", c_i32)])
+                + [(n, c_f32) for n in ("lr", "beta1", "beta2", "eps")] + [("t", c_i32), ("flags", c_i32)]
+                + [("weight_decay", c_f32), ("row_counts", c_vp)])      # the exact BPR step's (spex_lightgcn_step_bpr_adam_f32)
 
 
 STEP_DETERMINISTIC = 1          # spex_hip.h: SPEX_STEP_DETERMINISTIC
 STEP_FIXED_TASK_WEIGHTS = 2     # spex_hip.h: SPEX_STEP_FIXED_TASK_WEIGHTS
 STEP_PIPELINED = 4              # spex_hip.h: SPEX_STEP_PIPELINED
+STEP_BPR_DENSE = 8              # spex_hip.h: SPEX_STEP_BPR_DENSE
+STEP_BPR_PUSH = 16              # spex_hip.h: SPEX_STEP_BPR_PUSH
 
 
 class NGCFStepDesc(ctypes.Structure):

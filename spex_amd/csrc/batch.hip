@@ -284,6 +284,190 @@ __global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_batch_kernel(
     STAMP(6);
 }
 
+// The batch-sized middle of the exact BPR step (BPR differentiated through the propagation, Adam: upstream LightGCN's training
+// semantics) as one launch: lightgcn_batch_kernel with THREE rows per workgroup.  d == 64 only (d = 128 / 256 keep the
+// launch-by-launch form).  Workgroup (triple t, part p), rows ru = u[t], rp = n_user_rows + pos[t], rn = n_user_rows + neg[t]:
+//   1. last layer at the three rows: each row's 64-entry segments go to its virtual waves v = segment mod 16, the three rows' virtual
+//      waves numbered jointly and dealt to the 16 waves, segment sums added in segment order through LDS — a row of <= 1 024 entries is
+//      the spex_spmm_f32 / spex_spmm_rowlist_f32 row bit for bit, also under an edge mask;
+//   2. light_r = (running sum + y_r) / (L + 1);  xp = <light_u, light_p>, xn = <light_u, light_n>, z = xn - xp;
+//      loss_t = softplus(z) [+ weight_decay / 2 * (|E0[ru]|^2 + |E0[rp]|^2 + |E0[rn]|^2)];  dg = sigmoid(z) * grad_scale;
+//      g_u = dg (light_n - light_p), g_p = -dg light_u, g_n = dg light_u;
+//   3. PUSH: G[r] += push_scale g_r, G[col[e]] += push_scale val[e] g_r over the stored entries of the three rows (runs of 16 entries
+//      numbered jointly over the rows and dealt over (part, wave), the first kPre requested before step 1), g_out[r] += g_r where the
+//      caller wants the dense rows (G == NULL: those only, no push — the step's dense form for large T);  !PUSH: grad_slots[t] = g_u, [T + t] = g_p, [2 T + t] = g_n with plain stores, no float atomic.
+// The L2 term's gradient weight_decay / T * E0[r] per occurrence of r is NOT formed here: the kernel counts the occurrences
+// (row_counts[r] += 1, an integer atomic: order-independent) and the Adam pass, which reads E0 anyway, adds count * E0.
+// A triple with any index out of range is skipped whole (loss 0, zero slots, no count, nothing gathered).
+// Up to kBprBatchParts workgroups share a triple whose rows hold more than kBprBatchRunsPerPart runs per part, as in
+// lightgcn_batch_kernel.  Measured on Epinion2, T = 256, L = 3 (uniformly drawn users), us per one-call step, two rounds over
+// library builds (profiles/bpr_exact/parts_probe.txt): 1 part 71.8 / 71.7, 2 parts 73.0 / 73.1, 3 parts 71.8 / 71.4 (24 runs per
+// part 71.3 / 71.4, 8 runs 72.4 / 72.5), 4 parts 83.3 / 82.9 — the two-row kernel's constants stay.
+#ifndef SPEX_BPR_BATCH_PARTS            // (-D overrides: how those builds were made)
+#define SPEX_BPR_BATCH_PARTS 3
+#endif
+#ifndef SPEX_BPR_BATCH_RUNS_PER_PART
+#define SPEX_BPR_BATCH_RUNS_PER_PART 16
+#endif
+constexpr int kBprBatchParts = SPEX_BPR_BATCH_PARTS, kBprBatchRunsPerPart = SPEX_BPR_BATCH_RUNS_PER_PART;
+
+__device__ __forceinline__ int sel3(int k, int a, int b, int c) { return k == 0 ? a : (k == 1 ? b : c); }
+__device__ __forceinline__ float sel3f(int k, float a, float b, float c) { return k == 0 ? a : (k == 1 ? b : c); }
+
+template <bool PUSH>
+__global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_bpr_batch_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int n_rows, int n_user_rows,
+    const float *__restrict__ X, const float *__restrict__ acc_in, float acc_div, const int64_t *__restrict__ users,
+    const int64_t *__restrict__ pos, const int64_t *__restrict__ neg, int parts, float grad_scale, float push_scale, float *loss_sum,
+    float *__restrict__ loss_rows, float *g_out, float *G, int runs_per_part, float *__restrict__ grad_slots, int T,
+    const float *__restrict__ acc2, const float *__restrict__ acc3, float weight_decay, const float *__restrict__ E0,
+    int32_t *row_counts, const spex::EdgeDrop drop)
+{
+    __shared__ float s_part[3][kWgWaves][kWave];   // [row: user, positive, negative][virtual wave of the row-list kernel][column]
+    __shared__ float s_light[3][kWave];
+    __shared__ float s_norm[3];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int t = blockIdx.x / parts, part = blockIdx.x % parts;
+    const int64_t u64 = users[t], p64 = pos[t], n64 = neg[t];
+    const int64_t n_items = (int64_t)n_rows - n_user_rows;
+    if (u64 < 0 || u64 >= n_user_rows || p64 < 0 || p64 >= n_items || n64 < 0 || n64 >= n_items) {   // workgroup-uniform
+        if (loss_rows && part == 0 && threadIdx.x == 0) loss_rows[t] = 0.0f;
+        if (!PUSH && wave < 3) grad_slots[((size_t)wave * T + t) * kWave + lane] = 0.0f;
+        return;
+    }
+    const int r0 = (int)u64, r1 = (int)p64 + n_user_rows, r2 = (int)n64 + n_user_rows;
+    const int beg0 = rowptr[r0], beg1 = rowptr[r1], beg2 = rowptr[r2];
+    const int deg0 = rowptr[r0 + 1] - beg0, deg1 = rowptr[r1 + 1] - beg1, deg2 = rowptr[r2 + 1] - beg2;
+    const int my_row = sel3(wave, r0, r1, r2);             // (waves 0 .. 2 own a row each behind the forward)
+    // the running layer sum at the three rows, formed as lightgcn_batch_kernel forms it: ((E^0 + E^1) + E^2) + y
+    float run = 0.0f, e0v = 0.0f;
+    if (wave < 3) {
+        const size_t o = (size_t)my_row * kWave + lane;
+        run = acc_in[o];
+        float q2 = 0.0f, q3 = 0.0f;
+        if (acc2) q2 = acc2[o];
+        if (acc3) q3 = acc3[o];
+        if (weight_decay > 0.0f) e0v = E0[o];
+        if (acc2) run = run + q2;
+        if (acc3) run = run + q3;
+    }
+    // the push's runs of 16 entries, the three rows' runs numbered jointly and dealt over (part, wave)
+    const int n_run0 = (deg0 + 15) >> 4, n_run1 = (deg1 + 15) >> 4, n_run2 = (deg2 + 15) >> 4, n_runs = n_run0 + n_run1 + n_run2;
+    const bool push = PUSH && G != nullptr;                 // (G == NULL: the dense form — gradient rows into g_out only, no push)
+    const int want = (n_runs + runs_per_part - 1) / runs_per_part;
+    const int act = !push ? 1 : (want < parts ? (want < 1 ? 1 : want) : parts);
+    if (part >= act) return;
+    const int q_step = act * kWgWaves;
+    int q = part * kWgWaves + wave;
+    int p_col[kPre], p_cnt[kPre], p_side[kPre];
+    float p_val[kPre];
+    auto load_runs = [&](int q0) {
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {
+            const int qq = q0 + p * q_step;
+            p_col[p] = 0;
+            p_val[p] = 0.0f;
+            p_cnt[p] = 0;
+            p_side[p] = 0;
+            if (qq < n_runs) {
+                const int side = (qq >= n_run0) + (qq >= n_run0 + n_run1), rr = qq - sel3(side, 0, n_run0, n_run0 + n_run1);
+                const int base = sel3(side, beg0, beg1, beg2) + rr * 16, left = sel3(side, deg0, deg1, deg2) - rr * 16;
+                p_side[p] = side;
+                p_cnt[p] = left < 16 ? left : 16;
+                if (lane < p_cnt[p]) {
+                    p_col[p] = col[base + lane];
+                    p_val[p] = val[base + lane];
+                    if (drop.mode != 0) p_val[p] = spex::edge_kept(drop, base + lane) ? p_val[p] / drop.keep_prob : 0.0f;   // the forward's mask
+                }
+            }
+        }
+    };
+    if (push) load_runs(q);
+    // ---- 1. last layer at the three rows
+    const int nseg0 = (deg0 + kTaskEntries - 1) / kTaskEntries, nseg1 = (deg1 + kTaskEntries - 1) / kTaskEntries,
+              nseg2 = (deg2 + kTaskEntries - 1) / kTaskEntries;
+    const int nv0 = nseg0 < kWgWaves ? nseg0 : kWgWaves, nv1 = nseg1 < kWgWaves ? nseg1 : kWgWaves, nv2 = nseg2 < kWgWaves ? nseg2 : kWgWaves;
+    const int nv = nv0 + nv1 + nv2;
+    const float *__restrict__ Xl = X + lane;
+    for (int j = wave; j < nv; j += kWgWaves) {
+        const int side = (j >= nv0) + (j >= nv0 + nv1), v = j - sel3(side, 0, nv0, nv0 + nv1);
+        const int s_beg = sel3(side, beg0, beg1, beg2), s_deg = sel3(side, deg0, deg1, deg2), s_nseg = sel3(side, nseg0, nseg1, nseg2);
+        float acc = 0.0f;
+        for (int sgi = v; sgi < s_nseg; sgi += kWgWaves) {
+            const int left = s_deg - sgi * kTaskEntries;
+            if (drop.mode != 0)
+                acc = segment_sum_masked(col, val, Xl, s_beg + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc, drop);
+            else
+                acc = segment_sum(col, val, Xl, s_beg + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc);
+        }
+        s_part[side][v][lane] = acc;
+    }
+    __syncthreads();
+    // ---- 2. layer mean at the three rows (waves 0 .. 2), the two scores, the three gradient rows
+    if (wave < 3) {
+        const int lim = sel3(wave, nv0, nv1, nv2);
+        float y = lim > 0 ? s_part[wave][0][lane] : 0.0f;
+        for (int w = 1; w < lim; ++w) y = y + s_part[wave][w][lane];          // segment order
+        float s = run + y;
+        if (acc_div != 1.0f) s = s / acc_div;
+        s_light[wave][lane] = s;
+        if (weight_decay > 0.0f) {
+            const float nrm = wave_sum_f32(e0v * e0v);
+            if (lane == 0) s_norm[wave] = nrm;
+        }
+    }
+    __syncthreads();
+    const float lu = s_light[0][lane], lp = s_light[1][lane], ln = s_light[2][lane];
+    const float xp = wave_sum_f32(fmaf(lu, lp, 0.0f)), xn = wave_sum_f32(fmaf(lu, ln, 0.0f));
+    const float z = xn - xp;
+    const float dg = sigmoid_f(z) * grad_scale;
+    const float gn = dg * lu;
+    const float g3[3] = {dg * (ln - lp), -gn, gn};                           // d loss / d light at the user, the positive, the negative row
+    if (part == 0 && wave < 3) {
+        if (wave == 0 && lane == 0) {
+            float loss = fmaxf(z, 0.0f) + log1pf(expf(-fabsf(z)));
+            if (weight_decay > 0.0f) loss = loss + 0.5f * weight_decay * ((s_norm[0] + s_norm[1]) + s_norm[2]);
+            if (loss_rows) loss_rows[t] = loss;
+            else atomicAdd(loss_sum, loss);
+        }
+        if (row_counts && lane == 0) atomicAdd(row_counts + my_row, 1);       // occurrences of the row in the batch: the L2 gradient's weight
+        const float gw = sel3f(wave, g3[0], g3[1], g3[2]);
+        if (!PUSH) {
+            grad_slots[((size_t)wave * T + t) * kWave + lane] = gw;           // per-triple rows; summed per table row in slot order later
+        } else {
+            if (g_out) atomicAdd(g_out + (size_t)my_row * kWave + lane, gw);
+            if (push) atomicAdd(G + (size_t)my_row * kWave + lane, push_scale * gw);    // the `g` of (g + A^T g) / (L + 1)
+        }
+    }
+    if (!push) return;
+    // ---- 3. push over the three rows' entries (lightgcn_batch_kernel's loop: lane 0 of every loaded run is read before the first atomic)
+    float *out_l = G + lane;
+    for (;;) {
+        int c0[kPre];
+        float v0[kPre];
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {
+            c0[p] = __builtin_amdgcn_readlane(p_col[p], 0);
+            v0[p] = lane_bcast(p_val[p], 0);
+        }
+#pragma unroll
+        for (int p = 0; p < kPre; ++p) {
+            const float gs = push_scale * sel3f(p_side[p], g3[0], g3[1], g3[2]);
+            if (p_cnt[p] > 0) atomicAdd(out_l + (size_t)c0[p] * kWave, v0[p] * gs);
+#pragma unroll 1
+            for (int j = 1; j < p_cnt[p]; ++j) {
+                const int c = __builtin_amdgcn_readlane(p_col[p], j);
+                const float v = lane_bcast(p_val[p], j);
+                atomicAdd(out_l + (size_t)c * kWave, v * gs);
+            }
+        }
+        q += kPre * q_step;
+        if (q >= n_runs) break;
+        load_runs(q);
+    }
+}
+
 // lightgcn_batch_kernel for wider embeddings, d = 64 V (V = 2, 4; V = 1 is the kernel above, kept as its own source like the
 // d == 64 SpMM).  In the forward a lane owns V consecutive columns: a gathered row and a running-sum row are one coalesced
 // 256 V-byte wave load each; behind the layer mean it owns columns lane, lane + 64, ..  Same workgroup shape, same dealing of segments to virtual waves and of push runs to (part, wave):
@@ -1095,6 +1279,81 @@ int spex::lightgcn_batch_layers(const spex_graph_t *g, const float *X, const flo
     else if (d == 2 * kWave) SPEX_GO((lightgcn_batch_wide_kernel<true, 2>));
     else SPEX_GO((lightgcn_batch_wide_kernel<true, 4>));
 #undef SPEX_GO
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
+
+// ---- the BPR triple form (d == 64 only)
+static int bpr_batch_check(const char *who, const spex_graph_t *g, const float *X, const float *acc_in, const int64_t *users,
+                           const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows, float weight_decay, const float *E0,
+                           int32_t d)
+{
+    SPEX_CHECK_ARG(g && X && acc_in && T >= 0 && (T == 0 || (users && pos && neg)), "%s: NULL argument or T < 0", who);
+    SPEX_CHECK_ARG(n_user_rows >= 0 && n_user_rows <= g->n_rows && g->n_rows == g->n_cols, "%s: n_user_rows=%d on a %d x %d graph", who,
+                   n_user_rows, g->n_rows, g->n_cols);
+    SPEX_CHECK_ARG(weight_decay >= 0.0f && (weight_decay == 0.0f || E0), "%s: weight_decay %g needs E0 (and must not be negative)", who,
+                   (double)weight_decay);
+    if (d != kWave) {
+        spex::set_error("%s: d == 64 only (got %d); d = 128 / 256 take the launch-by-launch form", who, d);
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    return SPEX_OK;
+}
+
+extern "C" int spex_lightgcn_bpr_batch_slots_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div,
+                                                 const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
+                                                 int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0,
+                                                 int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *grad_slots,
+                                                 int32_t d, void *stream)
+{
+    return spex::lightgcn_bpr_batch_slots_layers(g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg, T, n_user_rows, grad_scale,
+                                                 weight_decay, E0, row_counts, loss_sum, loss_per_sample, grad_slots, d, stream);
+}
+
+int spex::lightgcn_bpr_batch_slots_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
+                                          float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
+                                          int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0, int32_t *row_counts,
+                                          float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream)
+{
+    const char *who = "spex_lightgcn_bpr_batch_slots_f32";
+    int rc = bpr_batch_check(who, g, X, acc_in, users, pos, neg, T, n_user_rows, weight_decay, E0, d);
+    if (rc != SPEX_OK) return rc;
+    SPEX_CHECK_ARG((loss_sum || loss_per_sample) && grad_slots && acc_div != 0.0f && (!acc3 || acc2),
+                   "%s: needs loss_sum or loss_per_sample, grad_slots, acc_div != 0 (and acc2 with acc3)", who);
+    if (T == 0 || g->n_rows == 0) return SPEX_OK;
+    hipLaunchKernelGGL(lightgcn_bpr_batch_kernel<false>, dim3((unsigned)T), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col,
+                       g->val, g->n_rows, n_user_rows, X, acc_in, acc_div, users, pos, neg, 1, grad_scale, 0.0f, loss_sum, loss_per_sample,
+                       nullptr, nullptr, 1, grad_slots, T, acc2, acc3, weight_decay, E0, row_counts, edge_drop_of(g));
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
+
+extern "C" int spex_lightgcn_bpr_batch_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div, const int64_t *users,
+                                           const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows, float grad_scale,
+                                           float push_scale, float weight_decay, const float *E0, int32_t *row_counts, float *loss_sum,
+                                           float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream)
+{
+    return spex::lightgcn_bpr_batch_layers(g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg, T, n_user_rows, grad_scale, push_scale,
+                                           weight_decay, E0, row_counts, loss_sum, loss_per_sample, g_out, G, d, stream);
+}
+
+int spex::lightgcn_bpr_batch_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
+                                    float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
+                                    int32_t n_user_rows, float grad_scale, float push_scale, float weight_decay, const float *E0,
+                                    int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d,
+                                    void *stream)
+{
+    const char *who = "spex_lightgcn_bpr_batch_f32";
+    int rc = bpr_batch_check(who, g, X, acc_in, users, pos, neg, T, n_user_rows, weight_decay, E0, d);
+    if (rc != SPEX_OK) return rc;
+    SPEX_CHECK_ARG((loss_sum || loss_per_sample) && (G || g_out) && G != g_out && acc_div != 0.0f && (!acc3 || acc2),
+                   "%s: needs loss_sum or loss_per_sample, G and / or g_out (two tables), acc_div != 0 (and acc2 with acc3)", who);
+    if (T == 0 || g->n_rows == 0) return SPEX_OK;
+    const int parts = G ? kBprBatchParts : 1, runs_per_part = kBprBatchRunsPerPart;     // (no push: one workgroup per triple)
+    SPEX_CHECK_ARG((int64_t)T * parts < (int64_t)1 << 31, "%s: T=%d is too many triples for one launch", who, T);
+    hipLaunchKernelGGL(lightgcn_bpr_batch_kernel<true>, dim3((unsigned)T * parts), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr,
+                       g->col, g->val, g->n_rows, n_user_rows, X, acc_in, acc_div, users, pos, neg, parts, grad_scale, push_scale, loss_sum,
+                       loss_per_sample, g_out, G, runs_per_part, nullptr, T, acc2, acc3, weight_decay, E0, row_counts, edge_drop_of(g));
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

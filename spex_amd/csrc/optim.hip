@@ -24,13 +24,16 @@ __device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, flo
 
 // (g and zero_buf carry no __restrict__: the caller may pass the gradient buffer itself to be cleared — every element is
 // read before the same thread clears it)
+// L2: the exact BPR step's pass — gradient += l2.scale * l2.count[row] * p[row] (rows of 64 parameters: 16 float4 steps), the other
+// parity's count table cleared by the thread that holds a row's first columns, and the whole gradient stored to l2.g_store.
+template <bool L2>
 __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *g,
                                                    float *__restrict__ m, float *__restrict__ v, int64_t n4,
                                                    int64_t rem, float w1, float beta2, float w2, float bc2_sqrt,
                                                    float eps, float step_size, float *zero_buf, float *zero_buf2,
                                                    const float *__restrict__ loss_rows, int n_loss, float *loss_sum,
                                                    const spex::SmallAdam small, const int main_blocks, const float *add_g,
-                                                   const float add_div)
+                                                   const float add_div, const spex::L2Rows l2)
 {
     // A second, small parameter block rides in the same launch (the NGCF step's layer weights: 8 320 parameters whose gradient
     // arrives as partial blocks — a launch of their own cost the step ~5 us of ramp for 33 workgroups): the blocks behind the
@@ -72,6 +75,15 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
             const float4 A = reinterpret_cast<const float4 *>(add_g)[i];
             G.x = G.x + A.x / add_div; G.y = G.y + A.y / add_div; G.z = G.z + A.z / add_div; G.w = G.w + A.w / add_div;
         }
+        if constexpr (L2) {
+            const int64_t row = i >> 4;
+            if (l2.count) {
+                const float c = l2.scale * (float)l2.count[row];
+                G.x = G.x + c * P.x; G.y = G.y + c * P.y; G.z = G.z + c * P.z; G.w = G.w + c * P.w;
+            }
+            if (l2.clear && (i & 15) == 0) l2.clear[row] = 0;
+            if (l2.g_store) reinterpret_cast<float4 *>(l2.g_store)[i] = G;
+        }
         float4 M = reinterpret_cast<float4 *>(m)[i];
         float4 V = reinterpret_cast<float4 *>(v)[i];
         adam1(P.x, G.x, M.x, V.x, w1, beta2, w2, bc2_sqrt, eps, step_size);
@@ -99,8 +111,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
 // Internal form with a second buffer to clear (the one-call training step keeps its push target all-zero this way).
 int spex::adam_step_z2(float *p, const float *g, float *m, float *v, int64_t n, int32_t t, float lr, float beta1, float beta2,
                        float eps, float *zero_buf, float *zero_buf2, void *stream, const float *loss_rows, int32_t n_loss, float *loss_sum,
-                       const spex::SmallAdam *small_in, const float *add_g, float add_div)
+                       const spex::SmallAdam *small_in, const float *add_g, float add_div, const spex::L2Rows *l2_in)
 {
+    spex::L2Rows l2{};
+    if (l2_in) l2 = *l2_in;
+    SPEX_CHECK_ARG(!l2_in || (n % 64 == 0 && (((uintptr_t)l2.g_store) & 15) == 0 && l2.g_store != p && l2.g_store != m && l2.g_store != v),
+                   "spex_adam_step_f32: the L2 form takes whole rows of 64 and a 16-byte aligned gradient store");
     SPEX_CHECK_ARG(!add_g || ((((uintptr_t)add_g) & 15) == 0 && add_div != 0.0f), "spex_adam_step_f32: add_g unaligned or add_div == 0");
     spex::SmallAdam small{};
     if (small_in) small = *small_in;
@@ -123,9 +139,13 @@ int spex::adam_step_z2(float *p, const float *g, float *m, float *v, int64_t n, 
     if (blocks < 1) blocks = 1;
     if (blocks > 2048) blocks = 2048;
     const int64_t small_blocks = (small.n + 255) / 256;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(blocks + small_blocks)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, rem,
-                       1.0f - beta1, beta2, 1.0f - beta2, bc2_sqrt, eps, step_size, zero_buf, zero_buf2, loss_rows, (int)n_loss, loss_sum,
-                       small, (int)blocks, add_g, add_div);
+#define SPEX_ADAM_GO(KERNEL)                                                                                                              \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)(blocks + small_blocks)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, rem,          \
+                       1.0f - beta1, beta2, 1.0f - beta2, bc2_sqrt, eps, step_size, zero_buf, zero_buf2, loss_rows, (int)n_loss, loss_sum, \
+                       small, (int)blocks, add_g, add_div, l2)
+    if (l2_in) SPEX_ADAM_GO(adam_kernel<true>);
+    else SPEX_ADAM_GO(adam_kernel<false>);
+#undef SPEX_ADAM_GO
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

@@ -18,9 +18,16 @@ struct SmallAdam {          // a second, small parameter block updated by the sa
     int64_t stride = 0;
     int32_t n = 0;
 };
+struct L2Rows {             // the exact BPR step's L2 term, applied by its Adam launch: gradient += scale * count[row] * p[row], rows of 64
+    const int32_t *count = nullptr;   // occurrences of every table row in this step's batch (written by the batch kernel)
+    int32_t *clear = nullptr;         // the OTHER step parity's count table, cleared here (no thread clears a cell another still reads)
+    float scale = 0.0f;               // weight_decay / T
+    float *g_store = nullptr;         // receives the step's whole gradient (product + add_g share + L2 term); may be g itself
+};
 int adam_step_z2(float *p, const float *g, float *m, float *v, int64_t n, int32_t t, float lr, float beta1, float beta2, float eps,
                  float *zero_buf, float *zero_buf2, void *stream, const float *loss_rows = nullptr, int32_t n_loss = 0,
-                 float *loss_sum = nullptr, const SmallAdam *small = nullptr, const float *add_g = nullptr, float add_div = 1.0f);
+                 float *loss_sum = nullptr, const SmallAdam *small = nullptr, const float *add_g = nullptr, float add_div = 1.0f,
+                 const L2Rows *l2 = nullptr);
                                                // add_g: gradient = g + add_g / add_div (add_g may be zero_buf: read, then cleared);   // optim.hip: spex_adam_step_f32 with a second buffer to clear and the step's
                                                // per-sample losses to fold into an accumulator
 
@@ -46,6 +53,15 @@ int lightgcn_batch_slots_layers(const spex_graph_t *g, const float *X, const flo
                                 float acc_div, const int64_t *users, const int64_t *items, const float *labels, int32_t B,
                                 int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d,
                                 void *stream);
+// (the exact BPR step's batch-sized middle, three rows per triple, d == 64: batch.hip)
+int lightgcn_bpr_batch_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
+                              float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows,
+                              float grad_scale, float push_scale, float weight_decay, const float *E0, int32_t *row_counts,
+                              float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream);
+int lightgcn_bpr_batch_slots_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
+                                    float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
+                                    int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0, int32_t *row_counts,
+                                    float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream);
 int gated_batch_fwd_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3, float acc_div,
                            const float *raw, const float *att_u, const float *att_i, const int64_t *users, const int64_t *items,
                            const float *labels, int32_t B, int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample,

@@ -143,6 +143,150 @@ extern "C" int spex_lightgcn_epoch_bce_f32(spex_lightgcn_step_t *s, const int64_
     return rc;
 }
 
+// The exact BPR training step — BPR differentiated through the propagation, an L2 term on the E0 rows of the batch, Adam: upstream
+// LightGCN's training semantics — as ONE call.  The schedule is spex_lightgcn_step_bce_f32's with the triple-shaped batch kernel
+// (batch.hip: lightgcn_bpr_batch_kernel, three rows per workgroup) in the middle; d == 64 only.
+//   fast path:      L - 1 whole-graph launches (plain for L <= 3) -> spex_lightgcn_bpr_batch_f32 (last layer at the 3 T rows, scores,
+//                   loss, gradient rows, (g + A^T g) / (L + 1) in push form) -> L - 1 pull products on A^T (all plain at L == 3:
+//                   A^T (A^T P) + P) -> Adam, which sums the per-triple losses in order and adds the L2 gradient: 2 L launches
+//   deterministic:  slots kernel -> spex_reduce_slots_f32 twice (users over slots [0, T), then (pos, neg) over [T, 3 T) — user rows and
+//                   item rows never coincide for valid triples; the second call accumulates, so that the all-zero slots of a skipped
+//                   triple whose negative item index lands among the user rows clobber nothing) -> spex_propagate_bwd_f32 -> Adam;
+//                   no float atomic
+//   L == 1 runs the same schedule (no whole-graph forward launch, the push target is the whole gradient).
+// L2 term: loss += weight_decay / 2 * (|E0[u]|^2 + |E0[p]|^2 + |E0[n]|^2) per triple (in the batch kernel); its gradient
+// weight_decay / T * E0[r] per occurrence of r is not propagated: the batch kernel counts occurrences in row_counts[t_next & 1] and
+// the Adam pass adds count * E0 and clears the other parity's table.  grad_E0 holds the step's whole gradient afterwards.
+// From this many triples up the fast path takes the dense form (see below): the push's cost grows with the batch rows' stored
+// entries, a third pull product's does not.  Measured on Epinion2, L = 3, us per step push / dense, both forced, alternating
+// (tools/bpr_exact_step_time.py --sweep, profiles/bpr_exact/form_sweep.jsonl): T = 256: 71.8 / 80.2, 512: 84.1 / 86.9,
+// 768: 95.2 / 92.5, 1 024: 105.9 / 98.8, 1 536: 127.3 / 108.8, 2 048: 150.3 / 120.3, 4 096: 241.0 / 167.6.
+constexpr int32_t kBprStepDenseMinTriples = 768;
+
+extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const int64_t *users, const int64_t *pos, const int64_t *neg,
+                                               int32_t T, float *loss_sum, void *stream)
+{
+    const char *who = "spex_lightgcn_step_bpr_adam_f32";
+    SPEX_CHECK_ARG(s && s->graph && s->graph_t && s->E0 && s->m && s->v && s->light_out && s->ws_fwd && s->lo_batch && s->g_out
+                       && s->ws_bwd && s->grad_E0 && s->grad_slots && s->row_counts,
+                   "%s: NULL field in the step descriptor (row_counts included)", who);
+    SPEX_CHECK_ARG(users && pos && neg && loss_sum && T >= 1, "%s: NULL batch pointer or T < 1", who);
+    const spex_graph *g = s->graph, *gt = s->graph_t;
+    const int32_t L = s->L, d = s->d, n_u = s->n_user_rows;
+    SPEX_CHECK_ARG(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_rows, "%s: square graphs of one size", who);
+    if (d != 64) {
+        spex::set_error("%s: d == 64 only (got %d); d = 128 / 256 take the launch-by-launch form", who, d);
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    SPEX_CHECK_ARG(L >= 1 && n_u >= 0 && n_u <= g->n_rows, "%s: L=%d n_user_rows=%d (needs L >= 1)", who, L, n_u);
+    SPEX_CHECK_ARG(T <= INT32_MAX / 3 && s->slot_capacity >= 3 * T, "%s: slot capacity %d < 3 T = %lld", who, s->slot_capacity, 3LL * T);
+    SPEX_CHECK_ARG(s->weight_decay >= 0.0f, "%s: weight_decay %g", who, (double)s->weight_decay);
+    // edge dropout: the BCE step's rules
+    SPEX_CHECK_ARG(g->mask_mode == gt->mask_mode && (g->mask_mode == 0 || (g->keep_prob == gt->keep_prob && g->seed == gt->seed && g->keep == gt->keep)),
+                   "%s: graph and graph_t must carry the same edge-dropout mask", who);
+    SPEX_CHECK_ARG(g->mask_mode == 0 || (gt != g && L >= 2),
+                   "%s: edge dropout needs L >= 2 and graph_t = the transposed handle (with its edge-id permutation)", who);
+    const size_t sz = (size_t)g->n_rows * d;
+    const bool det = (s->flags & SPEX_STEP_DETERMINISTIC) != 0;
+    const int32_t t_next = s->t + 1;
+    const float wd = s->weight_decay;
+    int32_t *cnt = s->row_counts + (size_t)(t_next & 1) * g->n_rows, *cnt_other = s->row_counts + (size_t)((t_next + 1) & 1) * g->n_rows;
+    spex::L2Rows l2;
+    l2.count = wd > 0.0f ? cnt : nullptr;
+    l2.clear = cnt_other;
+    l2.scale = wd / (float)T;
+    l2.g_store = s->grad_E0;
+    // ---- forward: layers 0 .. L-2 over the whole graph (plain for L <= 3), the last layer at the batch's rows only
+    const bool plain = L >= 2 && L <= 3;
+    const float *cur = s->E0;
+    for (int32_t l = 0; l + 1 < L; ++l) {
+        float *nxt = s->ws_fwd + (size_t)(l & 1) * sz;
+        if (plain) SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
+        else SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, l == 0 ? s->E0 : s->light_out, s->light_out, 1.0f, d, stream));
+        cur = nxt;
+    }
+    const float *sum0 = plain || L == 1 ? s->E0 : s->light_out;
+    const float *sum1 = plain ? s->ws_fwd : nullptr, *sum2 = plain && L == 3 ? s->ws_fwd + sz : nullptr;
+    if (det) {
+        float *loss_rows = s->lo_batch;
+        SPEX_TRY(spex::lightgcn_bpr_batch_slots_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u, 1.0f / (float)T, wd,
+                                                       s->E0, l2.count ? cnt : nullptr, nullptr, loss_rows, s->grad_slots, d, stream));
+        SPEX_TRY(spex_reduce_slots_f32(users, T, 0, nullptr, 0, 0, g->n_rows, s->grad_slots, d, 1.0f, s->g_out, 0, d, stream));
+        SPEX_TRY(spex_reduce_slots_f32(pos, T, n_u, neg, T, n_u, g->n_rows, s->grad_slots + (size_t)T * d, d, 1.0f, s->g_out, 1, d, stream));
+        SPEX_TRY(spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream));
+        SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, t_next, s->lr, s->beta1, s->beta2, s->eps, s->g_out,
+                                    s->ws_bwd /* keeps the fast path's push target all-zero */, stream, loss_rows, T, loss_sum, nullptr,
+                                    nullptr, 1.0f, &l2));
+        s->t = t_next;
+        return SPEX_OK;
+    }
+    const bool dense = (s->flags & SPEX_STEP_BPR_DENSE) != 0 || ((s->flags & SPEX_STEP_BPR_PUSH) == 0 && T >= kBprStepDenseMinTriples);
+    if (dense) {
+        // ---- large batches: the same launch with the push skipped — the gradient rows go to the dense g_out with atomics — and the
+        //      whole backward in pull form (L products: their cost does not grow with T, the push's does)
+        SPEX_TRY(spex::lightgcn_bpr_batch_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u, 1.0f / (float)T, 0.0f, wd,
+                                                 s->E0, l2.count ? cnt : nullptr, nullptr, s->grad_slots, s->g_out, nullptr, d, stream));
+        SPEX_TRY(spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream));
+        SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, t_next, s->lr, s->beta1, s->beta2, s->eps, s->g_out,
+                                    s->ws_bwd /* propagate_bwd's scaled gradient: the push target stays all-zero */, stream, s->grad_slots, T,
+                                    loss_sum, nullptr, nullptr, 1.0f, &l2));
+        s->t = t_next;
+        return SPEX_OK;
+    }
+    // ---- the batch-sized middle as one launch (g_out and G are all-zero here: the Adam pass clears them), then the L - 1 pull-form
+    //      products G_l = g / (L+1) + A^T G_{l+1}: the last one plain (the Adam pass adds its g / (L+1) share), at L == 3 both plain
+    //      with the push target P added instead — A^T (A^T P) + P, the identity derived at spex_lightgcn_step_bce_f32
+    float *G = s->ws_bwd;
+    const bool no_dense = L == 3 || L == 1;        // nothing reads the dense d loss / d light_out then: it is not formed
+    SPEX_TRY(spex::lightgcn_bpr_batch_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u, 1.0f / (float)T,
+                                             1.0f / (float)(L + 1), wd, s->E0, l2.count ? cnt : nullptr, nullptr,
+                                             s->grad_slots /* per-triple losses, summed by the Adam pass */, no_dense ? nullptr : s->g_out, G,
+                                             d, stream));
+    const float *c2 = G;
+    for (int32_t l = L - 2; l >= 0; --l) {
+        float *nxt = l == 0 ? s->grad_E0 : s->ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;
+        if (l == 0 || L == 3) SPEX_TRY(spex_spmm_f32(gt, c2, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
+        else SPEX_TRY(spex_spmm_f32(gt, c2, nxt, s->g_out, (float)(L + 1), nullptr, nullptr, 1.0f, d, stream));
+        c2 = nxt;
+    }
+    // (L == 1: the push target IS the gradient — read, stored to grad_E0 and cleared by the same pass)
+    SPEX_TRY(spex::adam_step_z2(s->E0, L == 1 ? G : s->grad_E0, s->m, s->v, (int64_t)sz, t_next, s->lr, s->beta1, s->beta2, s->eps,
+                                no_dense ? nullptr : s->g_out, s->ws_bwd, stream, s->grad_slots, T, loss_sum, nullptr,
+                                L == 1 ? nullptr : (L == 3 ? G : s->g_out), L == 3 ? 1.0f : (float)(L + 1), &l2));
+    s->t = t_next;
+    return SPEX_OK;
+}
+
+// An epoch of pre-drawn, device-resident triples as ONE call: batch k = triples [k T, min((k+1) T, n)) through
+// spex_lightgcn_step_bpr_adam_f32; loss sums, max_steps and the per-step sampled edge mask as in spex_lightgcn_epoch_bce_f32.
+extern "C" int spex_lightgcn_epoch_bpr_f32(spex_lightgcn_step_t *s, const int64_t *users, const int64_t *pos, const int64_t *neg, int64_t n,
+                                           int32_t T, int64_t max_steps, float keep_prob, uint32_t drop_seed, float *loss_full,
+                                           float *loss_ragged, void *stream)
+{
+    SPEX_CHECK_ARG(s && s->graph && s->graph_t, "spex_lightgcn_epoch_bpr_f32: NULL step descriptor or graph");
+    SPEX_CHECK_ARG(users && pos && neg && loss_full && loss_ragged && n >= 0 && T >= 1, "spex_lightgcn_epoch_bpr_f32: NULL pointer, n < 0 or T < 1");
+    SPEX_CHECK_ARG(keep_prob > 0.0f && keep_prob <= 1.0f, "spex_lightgcn_epoch_bpr_f32: keep_prob %g", keep_prob);
+    spex_graph *g = const_cast<spex_graph *>(s->graph), *gt = const_cast<spex_graph *>(s->graph_t);
+    const bool drop = keep_prob < 1.0f;
+    int rc = SPEX_OK;
+    int64_t k = 0;
+    for (int64_t b0 = 0; b0 < n && rc == SPEX_OK && (max_steps < 0 || k < max_steps); b0 += T, ++k) {
+        const int32_t nb = (int32_t)(n - b0 < T ? n - b0 : T);
+        if (drop) {
+            const uint64_t seed = ((uint64_t)drop_seed << 32) | (uint64_t)(uint32_t)(k + 1);
+            rc = spex_graph_set_edge_mask(g, 2, nullptr, keep_prob, seed);
+            if (rc == SPEX_OK && gt != g) rc = spex_graph_set_edge_mask(gt, 2, nullptr, keep_prob, seed);
+            if (rc != SPEX_OK) break;
+        }
+        rc = spex_lightgcn_step_bpr_adam_f32(s, users + b0, pos + b0, neg + b0, nb, nb == T ? loss_full : loss_ragged, stream);
+    }
+    if (drop) {
+        (void)spex_graph_set_edge_mask(g, 0, nullptr, 1.0f, 0);
+        if (gt != g) (void)spex_graph_set_edge_mask(gt, 0, nullptr, 1.0f, 0);
+    }
+    return rc;
+}
+
 // train() of NGCF_SPEX/code/main_rec.py:116-131 over a whole pre-shuffled, device-resident epoch as ONE call: batch k = samples
 // [k B, min((k+1) B, n)) through spex_ngcf_step_bce_f32 (the default one-layer model; the step advances its own Adam and dropout
 // counters) — the host issues the launches and nothing else.  Loss sums as in spex_lightgcn_epoch_bce_f32.

@@ -50,8 +50,11 @@ def _drop_desc(stepper):
 
 
 class LightGCNStepper:
-    def __init__(self, graph, E0, n_user_rows, n_layers=3, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph_t=None, deterministic=None):
-        """deterministic (default: SPEX_DETERMINISTIC=1 in the environment): the step takes every sum in a fixed order — no float
+    def __init__(self, graph, E0, n_user_rows, n_layers=3, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph_t=None, deterministic=None,
+                 weight_decay=0.0):
+        """weight_decay: the L2 coefficient of step_bpr_exact / epoch_bpr (upstream LightGCN's `decay`: weight_decay / 2 * the squared
+        norms of the batch's E0 rows, over T, added to the mean BPR loss); the BCE steps do not read it.
+        deterministic (default: SPEX_DETERMINISTIC=1 in the environment): the step takes every sum in a fixed order — no float
         atomics (spex_lightgcn_step_t.flags & SPEX_STEP_DETERMINISTIC): per-sample gradient rows added per table row in ascending
         slot order, the whole backward in pull form.  Two runs then end in bit-identical tables; ~10 us more per step.
         The batch-sized kernels behind the fast and the fixed-order step exist for the widths ops.WIDTHS (64, 128, 256): at any
@@ -66,6 +69,9 @@ class LightGCNStepper:
         self.graph, self.graph_t = graph, (graph_t if graph_t is not None else graph)
         self.E0, self.n_u, self.L = E0, int(n_user_rows), int(n_layers)
         self.lr, self.betas, self.eps = lr, betas, eps
+        self.weight_decay = float(weight_decay)
+        self.bpr_backward = None      # the one-call exact BPR step's fast-path form: None (chosen by T), "push" or "dense"
+        self.row_counts = None        # the exact BPR step's per-row occurrence counts [2, N] (by step parity), allocated on first use
         n, d = E0.shape
         dev = E0.device
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
@@ -136,10 +142,11 @@ class LightGCNStepper:
                       zero=self.g_out)
         return None if loss_acc is not None else loss_sum / B
 
-    def _slots(self, B):
-        """The batch's per-sample gradient rows (operands of the push-form first backward product)."""
-        if self.grad_slots is None or self.grad_slots.shape[0] < 2 * B:
-            self.grad_slots = torch.zeros((2 * B, self.E0.shape[1]), dtype=torch.float32, device=self.E0.device)
+    def _slots(self, B, rows_per_sample=2):
+        """The batch's per-sample gradient rows (operands of the push-form first backward product): two per BCE sample, three per
+        BPR triple."""
+        if self.grad_slots is None or self.grad_slots.shape[0] < rows_per_sample * B:
+            self.grad_slots = torch.zeros((rows_per_sample * B, self.E0.shape[1]), dtype=torch.float32, device=self.E0.device)
             self._desc = None
         return self.grad_slots
 
@@ -159,11 +166,14 @@ class LightGCNStepper:
         return (self.L >= 1 and self._wide_ok and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
                 and _batch_ok(users, items, labels))
 
-    def _prepare_desc(self, B):
+    def _prepare_desc(self, B, rows_per_sample=2):
         """The one-call step's descriptor for batches of up to B samples (built once, refreshed per call)."""
         if self.lo_batch is None:
             self.lo_batch = torch.zeros_like(self.light_out)
-        self._slots(B)
+        self._slots(B, rows_per_sample)
+        if rows_per_sample == 3 and self.row_counts is None:
+            self.row_counts = torch.zeros((2, self.E0.shape[0]), dtype=torch.int32, device=self.E0.device)
+            self._desc = None
         if not self._ws0_clean:                          # another path used the workspace: restore the all-zero push target
             self.ws_bwd[0].zero_()
             self._ws0_clean = True
@@ -178,6 +188,9 @@ class LightGCNStepper:
         d = self._desc
         d.t, d.lr = self.t, self.lr
         d.flags = _lib.STEP_DETERMINISTIC if self.deterministic else 0
+        d.flags |= {None: 0, "push": _lib.STEP_BPR_PUSH, "dense": _lib.STEP_BPR_DENSE}[self.bpr_backward]     # (the BCE step ignores them)
+        d.weight_decay = self.weight_decay
+        d.row_counts = None if self.row_counts is None else self.row_counts.data_ptr()
         return d
 
     def _step_bce_one_call(self, users, items, labels, loss_acc):
@@ -250,19 +263,70 @@ class LightGCNStepper:
                          self.lr if lr is None else lr, reg, loss_sum=self.loss_acc)
         return self.loss_acc
 
-    def step_bpr_exact(self, users, pos, neg):
-        """BPR loss differentiated through the propagation, Adam update (upstream LightGCN training semantics)."""
+    def step_bpr_exact(self, users, pos, neg, loss_acc=None, batch_rows_only=False):
+        """BPR loss differentiated through the propagation, Adam update (upstream LightGCN training semantics):
+        loss = mean softplus(<u, neg> - <u, pos>) + weight_decay / 2 * (|E0[u]|^2 + |E0[pos]|^2 + |E0[neg]|^2) summed over the batch / T.
+        Returns the mean loss (device tensor).  Launch by launch: whole-graph propagation, dense scoring gradient, all-pull backward,
+        Adam; with weight_decay > 0 the L2 term's loss share and its gradient weight_decay / T * count[row] * E0[row] (not
+        propagated) are added with plain torch ops on the device.
+        With `loss_acc` (a 1-element device buffer) and batch_rows_only=True the step is ONE library call
+        (spex_lightgcn_step_bpr_adam_f32: last layer at the triples' rows, the batch-sized middle in one launch, 2 L launches) where
+        that applies — width 64, contiguous int64 device indices, the mask rules of the BCE step; the batch's loss SUM is accumulated
+        into loss_acc and None is returned.  Otherwise loss_acc, if given, still receives the loss sum."""
+        if batch_rows_only and loss_acc is not None and self._one_call_bpr_ok(users, pos, neg):
+            return self._step_bpr_one_call(users, pos, neg, loss_acc)
         self.propagate()
         T = users.numel()
         lo = self.light_out
         loss_sum = ops.bpr_loss_grad(lo[:self.n_u], lo[self.n_u:], users, pos, neg, self.g_out[:self.n_u],
                                      self.g_out[self.n_u:], 1.0 / T)
         self._ws0_clean = False
+        if self.row_counts is not None:
+            self.row_counts.zero_()              # (the one-call step's count tables go by step parity: this step advances t without them)
         self.graph_t.propagate_bwd(self.g_out, self.L, grad_E0=self.grad_E0, ws=self.ws_bwd)
+        if self.weight_decay > 0:
+            dev = self.E0.device
+            rows = torch.cat([users.to(dev), pos.to(dev) + self.n_u, neg.to(dev) + self.n_u])
+            count = torch.bincount(rows, minlength=self.E0.shape[0]).to(torch.float32)
+            self.grad_E0.add_(self.E0 * (count * (self.weight_decay / T)).unsqueeze(1))
+            loss_sum = loss_sum + (0.5 * self.weight_decay) * (self.E0[rows] ** 2).sum()
         self.t += 1
         ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps,
                       zero=self.g_out)          # invariant of both exact steps: g_out is all-zero between steps
+        if loss_acc is not None:
+            loss_acc += loss_sum
+            return None
         return loss_sum / T
+
+    # -- the exact BPR step as one library call (spex_lightgcn_step_bpr_adam_f32) and the native epoch over it
+    def _one_call_bpr_ok(self, users, pos, neg):
+        masked = getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
+        return (self.L >= 1 and self.E0.shape[1] == 64 and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
+                and all(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() for t in (users, pos, neg))
+                and users.numel() == pos.numel() == neg.numel() >= 1)
+
+    def _step_bpr_one_call(self, users, pos, neg, loss_acc):
+        T = users.numel()
+        d = self._prepare_desc(T, 3)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        _launch(self.E0.device, "spex_lightgcn_step_bpr_adam_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), T, vp(loss_acc))
+        self.t = d.t
+        _bump(self.E0, self.m, self.v, self.grad_E0, loss_acc)
+        return None
+
+    def epoch_bpr(self, users, pos, neg, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
+        """A whole epoch of pre-drawn, device-resident triples as ONE native call (spex_lightgcn_epoch_bpr_f32): batch k = triples
+        [k T, (k+1) T) through the one-call exact BPR step.  loss_full / loss_ragged, keep_prob and drop_seed as in epoch_bce."""
+        if not self._one_call_bpr_ok(users[:1], pos[:1], neg[:1]):
+            raise ValueError("LightGCNStepper.epoch_bpr: needs an embedding width of 64 and contiguous int64 device tensors")
+        if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
+            raise ValueError("LightGCNStepper.epoch_bpr: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
+        d = self._prepare_desc(min(int(batch_size), users.numel()), 3)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        _launch(self.E0.device, "spex_lightgcn_epoch_bpr_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), users.numel(), int(batch_size),
+                -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
+        self.t = d.t
+        _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged)
 
 
 def dataloader_epoch_order(n):
@@ -453,6 +517,92 @@ def train_epoch(stepper, train_data, batch_size=256, resample=True, pause_gc=Tru
                 if stream is not None:
                     stepper.set_edge_dropout(None)
     return _sum_of_batch_means(acc, min(n, len(starts) * batch_size), batch_size)
+
+
+def bpr_epoch_triples(train_pairs, n_users, n_items, rng):
+    """One epoch of BPR triples with upstream LightGCN's uniform-sampling semantics, vectorised NumPy over `rng` (a
+    numpy.random.Generator — the only generator it touches).  As many draws as there are training interactions; each draw is a user
+    uniform over the users that have a positive, a positive uniform over that user's positives, and a negative uniform over the items,
+    redrawn while it is one of that user's positives.  train_pairs: int array [n, 2] of (user, item).  Returns (users, pos, neg), three
+    int64 arrays in the order drawn."""
+    pairs = np.asarray(train_pairs, dtype=np.int64).reshape(-1, 2)
+    if len(pairs) == 0:
+        e = np.empty(0, np.int64)
+        return e, e.copy(), e.copy()
+    if pairs[:, 0].min() < 0 or pairs[:, 0].max() >= n_users or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= n_items:
+        raise ValueError("bpr_epoch_triples: a training pair is out of range")
+    keys = np.unique(pairs[:, 0] * np.int64(n_items) + pairs[:, 1])        # sorted (user, item) keys, duplicates removed
+    ku, ki = keys // n_items, keys % n_items
+    active, start, count = np.unique(ku, return_index=True, return_counts=True)
+    if count.max() >= n_items:
+        raise ValueError("bpr_epoch_triples: a user has every item as a positive: no negative to draw")
+    n = len(pairs)
+    k = rng.integers(0, len(active), n)
+    users = active[k]
+    pos = ki[start[k] + (rng.random(n) * count[k]).astype(np.int64).clip(max=count[k] - 1)]
+    neg = rng.integers(0, n_items, n)
+    todo = np.flatnonzero(_is_positive(keys, users, neg, n_items))
+    while len(todo):
+        neg[todo] = rng.integers(0, n_items, len(todo))
+        todo = todo[_is_positive(keys, users[todo], neg[todo], n_items)]
+    return users.astype(np.int64), pos.astype(np.int64), neg.astype(np.int64)
+
+
+def _is_positive(keys, users, items, n_items):
+    """Membership of (users, items) in the sorted key set of the training pairs."""
+    q = users * np.int64(n_items) + items
+    at = np.searchsorted(keys, q)
+    return (at < len(keys)) & (keys[np.minimum(at, len(keys) - 1)] == q)
+
+
+def train_epoch_bpr(stepper, triples_or_sampler, batch_size=2048, pause_gc=True, edge_dropout=None, max_steps=None, step_losses=None):
+    """One epoch of exact BPR training (upstream LightGCN: BPR through the propagation, L2 on the batch's E0 rows, Adam) over pre-drawn
+    triples: (users, pos, neg) host arrays, or a callable returning them (e.g. lambda: bpr_epoch_triples(train, n_users, n_items, rng)).
+    The epoch is moved to the device once and runs as ONE native call (LightGCNStepper.epoch_bpr) where nothing has to happen on the
+    host between two steps; otherwise (step_losses wanted, a host-drawn "reference" mask, a width other than 64) step by step through
+    step_bpr_exact.  edge_dropout, max_steps, step_losses as in train_epoch.  Returns the epoch's sum of per-batch mean losses."""
+    arrays = triples_or_sampler() if callable(triples_or_sampler) else triples_or_sampler
+    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
+    if stream is not None and stepper.graph_t is stepper.graph:
+        raise ValueError("train_epoch_bpr(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation")
+    dev = stepper.E0.device
+    users, pos, neg = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev) for a in arrays)
+    n = users.numel()
+    starts = _batch_starts(n, batch_size, max_steps)
+    acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
+    native = (step_losses is None and stream in (None, "philox") and n > 0 and stepper._one_call_bpr_ok(users[:1], pos[:1], neg[:1])
+              and (stream is None or stepper.L >= 2))
+    with _gc_paused(pause_gc):
+        if native:
+            stepper.epoch_bpr(users, pos, neg, batch_size, acc[0], acc[1], max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed)
+        else:
+            try:
+                for k, s in enumerate(starts):
+                    e = min(s + batch_size, n)
+                    slot = acc[0] if e - s == batch_size else acc[1]
+                    tmp = torch.zeros(1, dtype=torch.float32, device=dev) if step_losses is not None else None
+                    if stream is not None:
+                        stepper.set_edge_dropout(edge_dropout_mask(stepper.graph, keep_prob, stream, seed, k + 1))
+                    stepper.step_bpr_exact(users[s:e], pos[s:e], neg[s:e], loss_acc=slot if tmp is None else tmp, batch_rows_only=True)
+                    if tmp is not None:
+                        step_losses.append(tmp.item() / (e - s))
+                        slot += tmp
+            finally:
+                if stream is not None:
+                    stepper.set_edge_dropout(None)
+    return _sum_of_batch_means(acc, min(n, len(starts) * batch_size), batch_size)
+
+
+def train_epochs_bpr(stepper, sampler, n_epochs, batch_size=2048, edge_dropout=None, after_epoch=None):
+    """n_epochs x train_epoch_bpr, the NEXT epoch's triples drawn by `sampler()` on a second host thread while the current epoch runs
+    as one native call (_run_epochs).  The sampler must use only its own generator (bpr_epoch_triples over a numpy.random.Generator
+    does): the hazard of train_epochs — the global torch generator drawn by both threads — does not arise then, and the draws come in
+    the order of a sequential loop.  Not under the "reference" edge-dropout stream, whose masks the training thread draws from torch's
+    global generator per step: that loop runs sequentially.  Returns the per-epoch loss sums."""
+    totals = _run_epochs(n_epochs, sampler,
+                         lambda arrays: train_epoch_bpr(stepper, arrays, batch_size=batch_size, edge_dropout=edge_dropout),
+                         after_epoch, overlap=_edge_dropout_args(edge_dropout)[1] != "reference")
+    return [float(t) for t in totals]
 
 
 class NGCFStepper:
