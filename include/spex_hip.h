@@ -548,6 +548,35 @@ int spex_expert_gate_rows_bwd_det_f32(const float *raw, const float *prop, const
 int spex_sample_negatives(const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows, const int64_t *d_pos_user,
                           int64_t n_pos, int32_t num_ng, int32_t num_item, uint64_t seed, int64_t *d_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------ BPR triple sampler
+ * One epoch's (user, positive, negative) triples drawn on the device — what trainer.bpr_epoch_triples draws on the host (law, not
+ * stream).  d_rowptr int32[n_user_rows + 1] / d_items int32: CSR of R on the device, every row ascending without duplicates;
+ * d_active int32[n_active]: the users with at least one stored item; num_item: catalogue size.  d_users / d_pos / d_neg: int64[n]
+ * (the one-call BPR step's index type).  One thread per slot i in [0, n):
+ *   mode 0, "by user" (upstream LightGCN's law):  user uniform over d_active, positive uniform over the user's stored items
+ *   mode 1, "by interaction":  a stored entry e uniform over [0, nnz), nnz = d_rowptr[n_user_rows]; user = the row that holds e
+ *                              (the last u with d_rowptr[u] <= e), positive = d_items[e] — users weighted by their degree
+ *   negative (both modes): uniform over the items that are not among the user's stored items.
+ * Randomness: standard Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85, ten rounds).
+ *   key     = (seed & 0xFFFFFFFF, seed >> 32)
+ *   counter = (i & 0xFFFFFFFF, i >> 32, epoch, stage)                 -> output words w0 w1 w2 w3
+ *   a word w maps to [0, m) as floor(w * m / 2^32) (multiply-high)
+ *   stage 0:  w0 -> the user's position in d_active (mode 0, m = n_active) or the entry e (mode 1, m = nnz)
+ *             w1 -> the positive's position in the user's row (mode 0, m = the row's length; mode 1 does not read it)
+ *             w2, w3 -> negative candidates 0 and 1 (m = num_item)
+ *   stage 1:  w0 .. w3 -> negative candidates 2 .. 5; computed only when candidates 0 and 1 were both stored items of the user
+ *   stage 2:  computed only when all six candidates were: w0 -> k (m = num_item - the row's length), the negative is the k-th item
+ *             in ascending order that is not in the row (w1 .. w3 unused)
+ *   The negative is the first candidate, in the order 0 .. 5, that is not in the user's row.
+ * Slot i of (seed, epoch) is a function of i, seed, epoch and the tables alone — not of n, nor of the launch's shape: a draw of
+ * n' < n slots is the first n' of the draw of n.  A user whose row holds every item has no negative: 0 is written (the tables of
+ * trainer.bpr_sampler_tables exclude the case); an entry of d_active outside [0, n_user_rows) counts as a user with an empty row
+ * (positive 0).  Returns SPEX_ERR_INVALID before any launch for a NULL pointer, n < 0, n > 0 with n_active < 1, num_item < 1,
+ * n_user_rows < 0 or a mode other than 0 / 1; n == 0 launches nothing. */
+int spex_sample_bpr_triples(const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows, const int32_t *d_active,
+                            int32_t n_active, int32_t num_item, int64_t n, int32_t mode, uint64_t seed, uint32_t epoch,
+                            int64_t *d_users, int64_t *d_pos, int64_t *d_neg, void *stream);
+
 /* ------------------------------------------------------------------------------------------------ learned edge values
  * the Diffnet++ social / interest diffusion — the same SpMM on user x user, user x item and item x user
  * graphs whose stored values are LEARNED (a per-edge parameter pushed through a row softmax), so the values change
@@ -765,6 +794,25 @@ int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *step, const int64_t *u
 int spex_lightgcn_epoch_bpr_f32(spex_lightgcn_step_t *step, const int64_t *users, const int64_t *pos, const int64_t *neg, int64_t n,
                                 int32_t T, int64_t max_steps, float keep_prob, uint32_t drop_seed, float *loss_full, float *loss_ragged,
                                 void *stream);
+/* A sampled epoch with nothing crossing the host: ONE spex_sample_bpr_triples launch (tables, num_item, n, mode, seed, epoch as
+ * there) into the caller-owned index buffers users / pos / neg (device int64[n] each), then exactly the loop of
+ * spex_lightgcn_epoch_bpr_f32 over them (T, max_steps, keep_prob, drop_seed, loss_full, loss_ragged as there; drop_seed is used as
+ * given).  The arguments of both are checked before anything is launched (the descriptor's fields are the step's to check: a
+ * descriptor it rejects ends the call after the draw, with no step run); n == 0 launches nothing. */
+int spex_lightgcn_epoch_bpr_sampled_f32(spex_lightgcn_step_t *step, const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows,
+                                        const int32_t *d_active, int32_t n_active, int32_t num_item, int64_t n, int32_t mode, uint64_t seed,
+                                        uint32_t epoch, int32_t T, int64_t max_steps, float keep_prob, uint32_t drop_seed, int64_t *users,
+                                        int64_t *pos, int64_t *neg, float *loss_full, float *loss_ragged, void *stream);
+/* n_epochs sampled epochs (epoch numbers epoch0 .. epoch0 + n_epochs - 1, modulo 2^32) back to back on one stream, no host thread
+ * and no synchronisation between them: epoch e's loss sums accumulate into loss_epochs[2 e] (full batches) and loss_epochs[2 e + 1]
+ * (the ragged last batch); loss_epochs: device float[2 n_epochs].  One set of index buffers serves every epoch: stream order puts
+ * the sampler of epoch e + 1 behind the last step of epoch e.  Under edge dropout (keep_prob < 1) epoch number E runs with the mask
+ * seed  drop_seed + 0x9E3779B9 * E  (modulo 2^32)  in place of drop_seed, so that no two epochs replay one mask sequence (epoch 0:
+ * drop_seed itself); step k of that epoch is keyed (that seed << 32) | (k + 1) as in spex_lightgcn_epoch_bpr_f32. */
+int spex_lightgcn_train_bpr_sampled_f32(spex_lightgcn_step_t *step, const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows,
+                                        const int32_t *d_active, int32_t n_active, int32_t num_item, int64_t n, int32_t mode, uint64_t seed,
+                                        uint32_t epoch0, int32_t n_epochs, int32_t T, int64_t max_steps, float keep_prob, uint32_t drop_seed,
+                                        int64_t *users, int64_t *pos, int64_t *neg, float *loss_epochs, void *stream);
 
 /* The single-layer NGCF training step (NGCF_SPEX/code/main_rec.py:122-128 with the default --layer_size [64]) as one call:
  *   spex_spmm_f32 (side = A ego) -> spex_ngcf_layer_fwd_f32 -> spex_ngcf_score_bwd_rows_f32 (scores, BCE, rows backward)

@@ -96,6 +96,8 @@ SIGNATURES = {
     "spex_expert_gate_rows_bwd_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i32, c_i64, c_i64, c_i64, c_i32,
                                                      c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "spex_sample_negatives": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, ctypes.c_uint64, c_vp, c_vp]),
+    "spex_sample_bpr_triples": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i64, c_i32, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp,
+                                               c_vp, c_vp]),
     "spex_graph_set_values": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
     "spex_sddmm_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "spex_edge_softmax_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp]),
@@ -120,6 +122,12 @@ SIGNATURES = {
     "spex_lightgcn_step_bpr_adam_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "spex_lightgcn_epoch_bpr_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_f32, ctypes.c_uint32, c_vp, c_vp,
                                                    c_vp]),
+    "spex_lightgcn_epoch_bpr_sampled_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i64, c_i32, ctypes.c_uint64,
+                                                           ctypes.c_uint32, c_i32, c_i64, c_f32, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                           c_vp]),
+    "spex_lightgcn_train_bpr_sampled_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i64, c_i32, ctypes.c_uint64,
+                                                           ctypes.c_uint32, c_i32, c_i32, c_i64, c_f32, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp,
+                                                           c_vp]),
     "spex_ngcf_step_bce_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "spex_ngcf_epoch_bce_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "spex_dual_task_step_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),

@@ -80,7 +80,135 @@ __global__ __launch_bounds__(256) void sample_negatives_kernel(const int32_t *__
     }
 }
 
+// ---- BPR triples (include/spex_hip.h: spex_sample_bpr_triples states the stream word by word; tests restate it from there)
+struct Philox4 {
+    uint32_t w[4];
+};
+
+// Standard Philox4x32-10: counter (c0, c1, c2, c3), key (k0, k1); all four output words.
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+
+// A uniform word onto [0, m), m >= 1, by multiply-high.
+__device__ __forceinline__ int to_range(uint32_t w, int m)
+{
+    return (int)(((uint64_t)w * (uint64_t)(uint32_t)m) >> 32);
+}
+
+// j is among the ascending items[beg, end)
+__device__ __forceinline__ bool row_has(const int32_t *__restrict__ items, int beg, int end, int j)
+{
+    int lo = beg, hi = end;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (items[mid] < j) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < end && items[lo] == j;
+}
+
+__global__ __launch_bounds__(256) void sample_bpr_triples_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ items,
+                                                                 int n_user_rows, const int32_t *__restrict__ active, int n_active,
+                                                                 int num_item, int64_t n, int mode, uint32_t seed_lo, uint32_t seed_hi,
+                                                                 uint32_t epoch, int64_t *__restrict__ users, int64_t *__restrict__ pos,
+                                                                 int64_t *__restrict__ neg)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int nnz = rowptr[n_user_rows];
+    for (int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; slot < n; slot += stride) {
+        const uint32_t s_lo = (uint32_t)slot, s_hi = (uint32_t)(slot >> 32);
+        const Philox4 r0 = philox4x32_10(s_lo, s_hi, epoch, 0u, seed_lo, seed_hi);
+        int u = 0, beg = 0, end = 0, p = 0;
+        if (mode == 0) {
+            u = active[to_range(r0.w[0], n_active)];
+            if (u >= 0 && u < n_user_rows) {
+                beg = rowptr[u];
+                end = rowptr[u + 1];
+            }
+            if (end > beg) p = items[beg + to_range(r0.w[1], end - beg)];
+        } else if (nnz > 0 && n_user_rows > 0) {
+            const int e = to_range(r0.w[0], nnz);
+            int lo = 0, hi = n_user_rows;          // first row index with rowptr[.] > e, over rowptr[1 .. n_user_rows]: the row that holds e
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (rowptr[mid + 1] > e) hi = mid;
+                else lo = mid + 1;
+            }
+            u = lo;
+            beg = rowptr[u];
+            end = rowptr[u + 1];
+            p = items[e];
+        }
+        // the negative: bounded rejection (candidates 0 .. 5), then the direct draw of the k-th admissible item — the same uniform
+        // law, and it terminates for a user who holds most of the catalogue
+        int j = to_range(r0.w[2], num_item);
+        bool done = !row_has(items, beg, end, j);
+        if (!done) {
+            j = to_range(r0.w[3], num_item);
+            done = !row_has(items, beg, end, j);
+        }
+        if (!done) {
+            const Philox4 r1 = philox4x32_10(s_lo, s_hi, epoch, 1u, seed_lo, seed_hi);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                if (!done) {
+                    j = to_range(r1.w[a], num_item);
+                    done = !row_has(items, beg, end, j);
+                }
+            }
+        }
+        if (!done) {
+            const int deg = end - beg, admissible = num_item - deg;
+            if (admissible > 0) {
+                const Philox4 r2 = philox4x32_10(s_lo, s_hi, epoch, 2u, seed_lo, seed_hi);
+                const int k = to_range(r2.w[0], admissible);
+                int lo = 0, hi = deg;  // first position m with items[beg+m] - m > k  (admissible items below it)
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (items[beg + mid] - mid > k) hi = mid;
+                    else lo = mid + 1;
+                }
+                j = k + lo;
+            } else {
+                j = 0;  // the user has every item: no valid negative exists
+            }
+        }
+        users[slot] = u;
+        pos[slot] = p;
+        neg[slot] = j;
+    }
+}
+
 }  // namespace
+
+extern "C" int spex_sample_bpr_triples(const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows, const int32_t *d_active,
+                                       int32_t n_active, int32_t num_item, int64_t n, int32_t mode, uint64_t seed, uint32_t epoch,
+                                       int64_t *d_users, int64_t *d_pos, int64_t *d_neg, void *stream)
+{
+    SPEX_CHECK_ARG(d_rowptr && d_items && d_active && d_users && d_pos && d_neg, "spex_sample_bpr_triples: NULL pointer");
+    SPEX_CHECK_ARG(n >= 0 && n_user_rows >= 0 && num_item >= 1, "spex_sample_bpr_triples: n=%lld n_user_rows=%d num_item=%d (needs n >= 0, num_item >= 1)",
+                   (long long)n, n_user_rows, num_item);
+    SPEX_CHECK_ARG(n == 0 || n_active >= 1, "spex_sample_bpr_triples: n_active=%d: no user has a positive to draw", n_active);
+    SPEX_CHECK_ARG(mode == 0 || mode == 1, "spex_sample_bpr_triples: mode %d (0: by user, 1: by interaction)", mode);
+    if (n == 0) return SPEX_OK;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(sample_bpr_triples_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_rowptr, d_items, n_user_rows,
+                       d_active, n_active, num_item, n, mode, (uint32_t)seed, (uint32_t)(seed >> 32), epoch, d_users, d_pos, d_neg);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
 
 extern "C" int spex_sample_negatives(const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows,
                                      const int64_t *d_pos_user, int64_t n_pos, int32_t num_ng, int32_t num_item,

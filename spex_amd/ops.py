@@ -616,6 +616,34 @@ def sample_negatives(rowptr, items, pos_user, num_ng, num_item, seed):
     return out
 
 
+BPR_SAMPLER_MODES = {"user": 0, "interaction": 1}      # spex_sample_bpr_triples' `mode`
+
+
+def sample_bpr_triples(rowptr, items, active, num_item, n, seed, epoch, by="user", out=None):
+    """n BPR triples drawn on the GPU (spex_sample_bpr_triples; the stream is written down in include/spex_hip.h).  rowptr / items:
+    device int32 CSR of R, rows ascending without duplicates; active: device int32 list of the users with a positive.  by "user": user
+    uniform over `active`, positive uniform over the user's items; by "interaction": a stored entry uniform over all of them.  The
+    negative is uniform over the items the user does not hold.  out: three int64 device tensors of at least n elements to draw into
+    (their first n are returned); default: fresh ones.  Returns (users, pos, neg), int64 [n]."""
+    for t, name in ((rowptr, "rowptr"), (items, "items"), (active, "active")):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise ValueError(f"{name}: need a contiguous torch.int32 CUDA tensor")
+    if by not in BPR_SAMPLER_MODES:
+        raise ValueError(f"sample_bpr_triples: by must be 'user' or 'interaction' (got {by!r})")
+    n = int(n)
+    if out is None:
+        out = tuple(torch.empty(n, dtype=torch.int64, device=rowptr.device) for _ in range(3))
+    for t in out:
+        if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() >= n):
+            raise ValueError("sample_bpr_triples: out needs three contiguous int64 CUDA tensors of at least n elements")
+    if n == 0:                       # (an empty device tensor has no storage to point at)
+        return tuple(t[:0] for t in out)
+    _launch(rowptr.device, "spex_sample_bpr_triples", _ptr(rowptr), _ptr(items), rowptr.numel() - 1, _ptr(active), active.numel(), int(num_item),
+            n, BPR_SAMPLER_MODES[by], int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, *(ctypes.c_void_p(t.data_ptr()) for t in out))
+    _bump(*out)
+    return tuple(t[:n] for t in out)
+
+
 # ------------------------------------------------------------------------------------------------ autograd glue
 def _flat_tables(user_w, item_w, strict=False):
     """The two embedding tables as one [N, d] buffer.  The drop-in model allocates them back-to-back so this is a

@@ -328,6 +328,53 @@ class LightGCNStepper:
         self.t = d.t
         _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged)
 
+    # -- sampled epochs: the triples drawn on the device by the same native call that trains on them
+    def _one_call_bpr_shape_ok(self):
+        """_one_call_bpr_ok without a batch: what the stepper itself must be for the one-call exact BPR step."""
+        masked = getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
+        return self.L >= 1 and self.E0.shape[1] == 64 and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
+
+    def _sampled_args(self, sampler, batch_size, max_steps, keep_prob, who):
+        if sampler.rowptr.device != self.E0.device:
+            raise ValueError(f"LightGCNStepper.{who}: the sampler's tables live on {sampler.rowptr.device}, the stepper on {self.E0.device}")
+        if not self._one_call_bpr_shape_ok() or sampler.n < 1 or int(batch_size) < 1:
+            raise ValueError(f"LightGCNStepper.{who}: needs an embedding width of 64, a sampler with n >= 1 and batch_size >= 1")
+        if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
+            raise ValueError(f"LightGCNStepper.{who}: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
+        d = self._prepare_desc(min(int(batch_size), sampler.n), 3)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        tables = (vp(sampler.rowptr), vp(sampler.items), sampler.rowptr.numel() - 1, vp(sampler.active), sampler.active.numel(), sampler.n_items,
+                  sampler.n, ops.BPR_SAMPLER_MODES[sampler.by], sampler.seed & 0xFFFFFFFFFFFFFFFF)
+        loop = (int(batch_size), -1 if max_steps is None else int(max_steps), float(keep_prob))
+        return d, tables, loop, tuple(vp(t) for t in sampler.epoch_buffers())
+
+    def epoch_bpr_sampled(self, sampler, epoch, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
+        """Epoch number `epoch` of a BprDeviceSampler drawn and trained as ONE native call (spex_lightgcn_epoch_bpr_sampled_f32): one
+        sampler launch into the sampler's index buffers, then epoch_bpr's loop over them — the state after it is that of
+        epoch_bpr(*sampler.draw(epoch), ...).  loss_full / loss_ragged, max_steps, keep_prob, drop_seed as in epoch_bpr."""
+        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, "epoch_bpr_sampled")
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        _launch(self.E0.device, "spex_lightgcn_epoch_bpr_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
+                int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
+        self.t = d.t
+        _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged, *sampler.epoch_buffers())
+
+    def train_bpr_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
+        """n_epochs sampled epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
+        (spex_lightgcn_train_bpr_sampled_f32): no host thread, no synchronisation.  loss_epochs: a contiguous fp32 device tensor of
+        2 n_epochs elements, zeroed by the caller — epoch e's loss sums of the full batches / of the ragged last one accumulate into
+        elements 2 e and 2 e + 1.  Under edge dropout epoch number E runs with the mask seed bpr_epoch_drop_seed(drop_seed, E)."""
+        if not (loss_epochs.is_cuda and loss_epochs.dtype == torch.float32 and loss_epochs.is_contiguous()
+                and loss_epochs.numel() >= 2 * int(n_epochs) and int(n_epochs) >= 0):
+            raise ValueError("LightGCNStepper.train_bpr_sampled: loss_epochs needs to be a contiguous fp32 device tensor of 2 n_epochs elements")
+        if int(n_epochs) == 0:
+            return
+        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, "train_bpr_sampled")
+        _launch(self.E0.device, "spex_lightgcn_train_bpr_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
+                *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
+        self.t = d.t
+        _bump(self.E0, self.m, self.v, self.grad_E0, loss_epochs, *sampler.epoch_buffers())
+
 
 def dataloader_epoch_order(n):
     """The index order `DataLoader(dataset, shuffle=True)` walks in one epoch, drawn from the GLOBAL torch RNG exactly as
@@ -555,18 +602,96 @@ def _is_positive(keys, users, items, n_items):
     return (at < len(keys)) & (keys[np.minimum(at, len(keys) - 1)] == q)
 
 
-def train_epoch_bpr(stepper, triples_or_sampler, batch_size=2048, pause_gc=True, edge_dropout=None, max_steps=None, step_losses=None):
+def bpr_sampler_tables(train_pairs, n_users, n_items):
+    """The tables the device sampler draws from (spex_sample_bpr_triples), from the key set bpr_epoch_triples builds: the CSR of R with
+    every row ascending and duplicates removed — rowptr int32 [n_users + 1], items int32 — and `active`, the int32 list of the users
+    that hold at least one item.  Raises like bpr_epoch_triples when a pair is out of range or a user holds every item."""
+    pairs = np.asarray(train_pairs, dtype=np.int64).reshape(-1, 2)
+    if len(pairs) and (pairs[:, 0].min() < 0 or pairs[:, 0].max() >= n_users or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= n_items):
+        raise ValueError("bpr_sampler_tables: a training pair is out of range")
+    keys = np.unique(pairs[:, 0] * np.int64(n_items) + pairs[:, 1])        # sorted (user, item) keys, duplicates removed
+    if len(keys) >= 2 ** 31:
+        raise ValueError("bpr_sampler_tables: 2^31 or more stored pairs: the tables are int32")
+    count = np.bincount(keys // n_items, minlength=n_users)
+    if len(keys) and count.max() >= n_items:
+        raise ValueError("bpr_sampler_tables: a user has every item as a positive: no negative to draw")
+    rowptr = np.zeros(n_users + 1, np.int32)
+    np.cumsum(count, out=rowptr[1:])
+    return rowptr, (keys % n_items).astype(np.int32), np.flatnonzero(count).astype(np.int32)
+
+
+def bpr_epoch_drop_seed(drop_seed, epoch):
+    """The edge-dropout mask seed of epoch number `epoch` in a multi-epoch sampled run (spex_lightgcn_train_bpr_sampled_f32):
+    drop_seed + 0x9E3779B9 * epoch modulo 2^32 — epoch 0 keeps drop_seed.  Step k of that epoch (from 0) wears the mask
+    edge_dropout_mask(graph, keep_prob, "philox", bpr_epoch_drop_seed(drop_seed, epoch), k + 1)."""
+    return (int(drop_seed) + 0x9E3779B9 * (int(epoch) & 0xFFFFFFFF)) & 0xFFFFFFFF
+
+
+class BprDeviceSampler:
+    """BPR triples drawn on the device (ops.sample_bpr_triples): the tables of bpr_sampler_tables held in HBM, the seed, the law
+    (by="user": bpr_epoch_triples' and upstream's; by="interaction": a stored pair uniform over all of them, users weighted by their
+    degree) and n, the draws per epoch (default: the number of training pairs, as bpr_epoch_triples draws).  draw(epoch) returns that
+    epoch's (users, pos, neg) device tensors — a function of (seed, epoch) alone, and a shorter draw is a prefix of a longer one.
+    Pass the sampler itself to train_epoch_bpr / train_epochs_bpr / LightGCNStepper.epoch_bpr_sampled and the epoch samples and
+    trains in one native call.  Not callable on purpose: a callable is a HOST sampler to those functions."""
+
+    def __init__(self, train_pairs, n_users, n_items, device, seed=0, by="user", n=None):
+        if by not in ops.BPR_SAMPLER_MODES:
+            raise ValueError(f"BprDeviceSampler: by must be 'user' or 'interaction' (got {by!r})")
+        rowptr, items, active = bpr_sampler_tables(train_pairs, n_users, n_items)
+        self.device = torch.device(device)
+        self.rowptr, self.items, self.active = (torch.from_numpy(a).to(self.device) for a in (rowptr, items, active))
+        self.n_items, self.seed, self.by = int(n_items), int(seed), by
+        self.n = len(np.asarray(train_pairs).reshape(-1, 2)) if n is None else int(n)
+        if self.n < 0 or (self.n > 0 and len(active) == 0):
+            raise ValueError("BprDeviceSampler: n < 0, or draws wanted from an empty training set")
+        self._buffers = None          # the index buffers of the native epoch calls (epoch_buffers)
+
+    def draw(self, epoch, n=None):
+        """Epoch `epoch`'s triples as three fresh int64 device tensors of n (default: self.n) elements."""
+        return ops.sample_bpr_triples(self.rowptr, self.items, self.active, self.n_items, self.n if n is None else n, self.seed, epoch,
+                                      by=self.by)
+
+    def epoch_buffers(self):
+        """Three int64 [n] device buffers, allocated once: what the native sampled epochs draw into (stream order keeps one epoch's
+        reads ahead of the next epoch's draw)."""
+        if self._buffers is None:
+            self._buffers = tuple(torch.empty(self.n, dtype=torch.int64, device=self.device) for _ in range(3))
+        return self._buffers
+
+
+def _is_device_triples(x):
+    return isinstance(x, (tuple, list)) and len(x) == 3 and all(torch.is_tensor(t) for t in x)
+
+
+def train_epoch_bpr(stepper, triples_or_sampler, batch_size=2048, pause_gc=True, edge_dropout=None, max_steps=None, step_losses=None,
+                    epoch=0):
     """One epoch of exact BPR training (upstream LightGCN: BPR through the propagation, L2 on the batch's E0 rows, Adam) over pre-drawn
     triples: (users, pos, neg) host arrays, or a callable returning them (e.g. lambda: bpr_epoch_triples(train, n_users, n_items, rng)).
     The epoch is moved to the device once and runs as ONE native call (LightGCNStepper.epoch_bpr) where nothing has to happen on the
     host between two steps; otherwise (step_losses wanted, a host-drawn "reference" mask, a width other than 64) step by step through
-    step_bpr_exact.  edge_dropout, max_steps, step_losses as in train_epoch.  Returns the epoch's sum of per-batch mean losses."""
+    step_bpr_exact.  edge_dropout, max_steps, step_losses as in train_epoch.  Returns the epoch's sum of per-batch mean losses.
+    Also: a tuple of three device tensors (used where they are), or a BprDeviceSampler — epoch number `epoch` is then drawn AND trained
+    in one native call (LightGCNStepper.epoch_bpr_sampled), or drawn by sampler.draw(epoch) for the step-by-step loop."""
+    sampler = triples_or_sampler if isinstance(triples_or_sampler, BprDeviceSampler) else None
     arrays = triples_or_sampler() if callable(triples_or_sampler) else triples_or_sampler
     keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
     if stream is not None and stepper.graph_t is stepper.graph:
         raise ValueError("train_epoch_bpr(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation")
     dev = stepper.E0.device
-    users, pos, neg = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev) for a in arrays)
+    native_ok = (step_losses is None and stream in (None, "philox") and stepper._one_call_bpr_shape_ok()
+                 and (stream is None or stepper.L >= 2))
+    if sampler is not None and sampler.n > 0 and native_ok:
+        acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
+        with _gc_paused(pause_gc):
+            stepper.epoch_bpr_sampled(sampler, epoch, batch_size, acc[0], acc[1], max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed)
+        return _sum_of_batch_means(acc, min(sampler.n, len(_batch_starts(sampler.n, batch_size, max_steps)) * batch_size), batch_size)
+    if sampler is not None:
+        users, pos, neg = sampler.draw(epoch)
+    elif _is_device_triples(arrays):
+        users, pos, neg = (t.to(device=dev, dtype=torch.int64).contiguous() for t in arrays)
+    else:
+        users, pos, neg = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev) for a in arrays)
     n = users.numel()
     starts = _batch_starts(n, batch_size, max_steps)
     acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
@@ -593,15 +718,45 @@ def train_epoch_bpr(stepper, triples_or_sampler, batch_size=2048, pause_gc=True,
     return _sum_of_batch_means(acc, min(n, len(starts) * batch_size), batch_size)
 
 
-def train_epochs_bpr(stepper, sampler, n_epochs, batch_size=2048, edge_dropout=None, after_epoch=None):
+def train_epochs_bpr(stepper, sampler, n_epochs, batch_size=2048, edge_dropout=None, after_epoch=None, max_steps=None, first_epoch=0):
     """n_epochs x train_epoch_bpr, the NEXT epoch's triples drawn by `sampler()` on a second host thread while the current epoch runs
     as one native call (_run_epochs).  The sampler must use only its own generator (bpr_epoch_triples over a numpy.random.Generator
     does): the hazard of train_epochs — the global torch generator drawn by both threads — does not arise then, and the draws come in
     the order of a sequential loop.  Not under the "reference" edge-dropout stream, whose masks the training thread draws from torch's
-    global generator per step: that loop runs sequentially.  Returns the per-epoch loss sums."""
+    global generator per step: that loop runs sequentially.  Returns the per-epoch loss sums.  max_steps: at most that many batches
+    per epoch.
+    sampler a BprDeviceSampler: no second thread — epochs first_epoch .. first_epoch + n_epochs - 1 are drawn on the device.  Without
+    after_epoch the whole run is ONE native call (LightGCNStepper.train_bpr_sampled) and one synchronisation at its end; with it, one
+    native call per epoch.  Under edge dropout epoch e runs with the mask seed bpr_epoch_drop_seed(seed, e) either way."""
+    if isinstance(sampler, BprDeviceSampler):
+        return _train_epochs_bpr_sampled(stepper, sampler, n_epochs, batch_size, edge_dropout, after_epoch, max_steps, int(first_epoch))
     totals = _run_epochs(n_epochs, sampler,
-                         lambda arrays: train_epoch_bpr(stepper, arrays, batch_size=batch_size, edge_dropout=edge_dropout),
+                         lambda arrays: train_epoch_bpr(stepper, arrays, batch_size=batch_size, edge_dropout=edge_dropout, max_steps=max_steps),
                          after_epoch, overlap=_edge_dropout_args(edge_dropout)[1] != "reference")
+    return [float(t) for t in totals]
+
+
+def _train_epochs_bpr_sampled(stepper, sampler, n_epochs, batch_size, edge_dropout, after_epoch, max_steps, first_epoch):
+    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
+    if stream is not None and stepper.graph_t is stepper.graph:
+        raise ValueError("train_epochs_bpr(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation")
+    one_call = (after_epoch is None and n_epochs > 0 and sampler.n > 0 and stream in (None, "philox") and stepper._one_call_bpr_shape_ok()
+                and (stream is None or stepper.L >= 2))
+    if one_call:
+        acc = torch.zeros(n_epochs, 2, 1, dtype=torch.float32, device=stepper.E0.device)
+        with _gc_paused():
+            stepper.train_bpr_sampled(sampler, n_epochs, batch_size, acc, max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed,
+                                      first_epoch=first_epoch)
+        n_done = min(sampler.n, len(_batch_starts(sampler.n, batch_size, max_steps)) * batch_size)
+        host = acc.cpu()                                  # the run's one synchronisation
+        return [float(_sum_of_batch_means(host[e], n_done, batch_size)) for e in range(n_epochs)]
+    totals = []
+    for e in range(first_epoch, first_epoch + n_epochs):
+        drop = None if stream is None else (keep_prob, stream, bpr_epoch_drop_seed(seed, e) if stream == "philox" else seed)
+        total = train_epoch_bpr(stepper, sampler, batch_size=batch_size, edge_dropout=drop, max_steps=max_steps, epoch=e)
+        totals.append(total)
+        if after_epoch is not None:
+            after_epoch(e - first_epoch, total)
     return [float(t) for t in totals]
 
 
