@@ -577,6 +577,45 @@ int spex_sample_bpr_triples(const int32_t *d_rowptr, const int32_t *d_items, int
                             int32_t n_active, int32_t num_item, int64_t n, int32_t mode, uint64_t seed, uint32_t epoch,
                             int64_t *d_users, int64_t *d_pos, int64_t *d_neg, void *stream);
 
+/* ------------------------------------------------------------------------------------------------ BCE epoch sampler
+ * One BCE epoch drawn on the device, already shuffled: what LightTrainData.ng_sample() followed by the DataLoader's shuffle prepare
+ * on the host (law, not stream — neither NumPy's nor torch's: for the same seed the individual samples differ from the reference's).
+ * d_rowptr int32[n_user_rows + 1] / d_items int32: CSR of R on the device, every row ascending without duplicates
+ * (trainer.bpr_sampler_tables); d_pos_user / d_pos_item int32[n_pos]: the positives in the caller's order, duplicates kept (each
+ * occurrence is a sample); num_ng >= 1 negatives per positive; num_item: catalogue size.  With P = n_pos and n = P (1 + num_ng):
+ * d_users int64[n], d_items_out int64[n], d_labels float[n] (the types spex_lightgcn_epoch_bce_f32 reads).
+ * The UNSHUFFLED epoch has n source samples: source j < P is positive j (user d_pos_user[j], item d_pos_item[j], label 1); source
+ * P + k, k in [0, P num_ng), is a negative of positive k / num_ng (all negatives of positive 0 first, ng_sample's order): user
+ * d_pos_user[k / num_ng], label 0, item uniform over the items that are not in that user's row.  One thread per OUTPUT slot i in
+ * [0, n): slot i holds source perm(i), perm a keyed bijection of [0, n) — the epoch is written in shuffled order by one launch.
+ * Randomness: standard Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85, ten rounds).
+ *   key     = (seed & 0xFFFFFFFF, seed >> 32)
+ *   a word w maps to [0, m) as floor(w * m / 2^32) (multiply-high)
+ *   negative k:  counter = (k & 0xFFFFFFFF, k >> 32 (= 0: n < 2^31), epoch, stage) -> output words w0 w1 w2 w3
+ *     stage 0:  w0 .. w3 -> candidates 0 .. 3 (m = num_item)
+ *     stage 1:  w0 .. w3 -> candidates 4 .. 7; computed only when candidates 0 .. 3 were all stored items of the user
+ *     stage 2:  computed only when all eight candidates were: w0 -> t (m = num_item - the row's length), the negative is the t-th
+ *               item in ascending order that is not in the row (w1 .. w3 unused)
+ *     The negative is the first candidate, in the order 0 .. 7, that is not in the user's row.  The draw is keyed by k, not by the
+ *     slot: where the shuffle puts a sample does not change it.
+ *   perm:  a balanced Feistel network with cycle walking.
+ *     bits = the bit length of n - 1 (0 for n = 1), h = max(1, ceil(bits / 2)), mask = 2^h - 1
+ *     round keys K[0 .. 3] = w0 .. w3 of counter (0, 0, epoch, 3); K[4], K[5] = w0, w1 of counter (1, 0, epoch, 3)   (stage 3: no
+ *       negative's counter)
+ *     fmix32(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16   (MurmurHash3's finaliser, mod 2^32)
+ *     x = i;  repeat { L = x >> h, R = x & mask;  for r = 0 .. 5: (L, R) <- (R, L ^ (fmix32(R ^ K[r]) & mask));  x = (L << h) | R }
+ *     while x >= n;  perm(i) = x.
+ *     Six Feistel rounds are a permutation of [0, 2^(2 h)), and n <= 2^(2 h) < 4 n (n >= 2): the walk from a point inside [0, n)
+ *     follows that permutation's cycle, which returns to [0, n) (at the latest at the starting point) — it terminates without a cap,
+ *     and the first return is a bijection of [0, n).
+ * A slot of (seed, epoch) is a function of i, n, seed, epoch, the positives and the tables alone — not of the launch's shape.  A
+ * user index outside [0, n_user_rows) reads as an empty row; a user whose row holds every item has no negative: 0 is written.
+ * Returns SPEX_ERR_INVALID before any launch for a NULL pointer, n_pos < 0, num_ng < 1, num_item < 1, n_user_rows < 0 or
+ * n_pos (1 + num_ng) >= 2^31; n_pos == 0 launches nothing. */
+int spex_sample_bce_epoch(const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows, const int32_t *d_pos_user,
+                          const int32_t *d_pos_item, int64_t n_pos, int32_t num_ng, int32_t num_item, uint64_t seed, uint32_t epoch,
+                          int64_t *d_users, int64_t *d_items_out, float *d_labels, void *stream);
+
 /* ------------------------------------------------------------------------------------------------ learned edge values
  * the Diffnet++ social / interest diffusion — the same SpMM on user x user, user x item and item x user
  * graphs whose stored values are LEARNED (a per-edge parameter pushed through a row softmax), so the values change
@@ -813,6 +852,27 @@ int spex_lightgcn_train_bpr_sampled_f32(spex_lightgcn_step_t *step, const int32_
                                         const int32_t *d_active, int32_t n_active, int32_t num_item, int64_t n, int32_t mode, uint64_t seed,
                                         uint32_t epoch0, int32_t n_epochs, int32_t T, int64_t max_steps, float keep_prob, uint32_t drop_seed,
                                         int64_t *users, int64_t *pos, int64_t *neg, float *loss_epochs, void *stream);
+
+/* A sampled BCE epoch with nothing crossing the host: ONE spex_sample_bce_epoch launch (tables, positives, num_ng, num_item, seed,
+ * epoch as there) into the caller-owned buffers users / items (device int64[n] each) and labels (device float[n]),
+ * n = n_pos (1 + num_ng), then exactly the loop of spex_lightgcn_epoch_bce_f32 over them (B, max_steps, keep_prob, drop_seed,
+ * loss_full, loss_ragged as there; drop_seed is used as given).  The arguments of both are checked before anything is launched (the
+ * descriptor's fields are the step's to check: a descriptor it rejects ends the call after the draw, with no step run); n_pos == 0
+ * launches nothing. */
+int spex_lightgcn_epoch_bce_sampled_f32(spex_lightgcn_step_t *step, const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows,
+                                        const int32_t *d_pos_user, const int32_t *d_pos_item, int64_t n_pos, int32_t num_ng, int32_t num_item,
+                                        uint64_t seed, uint32_t epoch, int32_t B, int64_t max_steps, float keep_prob, uint32_t drop_seed,
+                                        int64_t *users, int64_t *items, float *labels, float *loss_full, float *loss_ragged, void *stream);
+/* n_epochs sampled BCE epochs (epoch numbers epoch0 .. epoch0 + n_epochs - 1, modulo 2^32) back to back on one stream, no host
+ * thread and no synchronisation between them: epoch e's loss sums accumulate into loss_epochs[2 e] (full batches) and
+ * loss_epochs[2 e + 1] (the ragged last batch); loss_epochs: device float[2 n_epochs].  One set of buffers serves every epoch: stream
+ * order puts the sampler of epoch e + 1 behind the last step of epoch e.  Under edge dropout (keep_prob < 1) epoch number E runs with
+ * the mask seed  drop_seed + 0x9E3779B9 * E  (modulo 2^32)  in place of drop_seed — spex_lightgcn_train_bpr_sampled_f32's rule — so
+ * that no two epochs replay one mask sequence; step k of that epoch is keyed (that seed << 32) | (k + 1). */
+int spex_lightgcn_train_bce_sampled_f32(spex_lightgcn_step_t *step, const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows,
+                                        const int32_t *d_pos_user, const int32_t *d_pos_item, int64_t n_pos, int32_t num_ng, int32_t num_item,
+                                        uint64_t seed, uint32_t epoch0, int32_t n_epochs, int32_t B, int64_t max_steps, float keep_prob,
+                                        uint32_t drop_seed, int64_t *users, int64_t *items, float *labels, float *loss_epochs, void *stream);
 
 /* The single-layer NGCF training step (NGCF_SPEX/code/main_rec.py:122-128 with the default --layer_size [64]) as one call:
  *   spex_spmm_f32 (side = A ego) -> spex_ngcf_layer_fwd_f32 -> spex_ngcf_score_bwd_rows_f32 (scores, BCE, rows backward)

@@ -98,6 +98,8 @@ SIGNATURES = {
     "spex_sample_negatives": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, ctypes.c_uint64, c_vp, c_vp]),
     "spex_sample_bpr_triples": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i64, c_i32, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp,
                                                c_vp, c_vp]),
+    "spex_sample_bce_epoch": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp,
+                                             c_vp]),
     "spex_graph_set_values": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
     "spex_sddmm_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "spex_edge_softmax_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp]),
@@ -126,6 +128,12 @@ SIGNATURES = {
                                                            ctypes.c_uint32, c_i32, c_i64, c_f32, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                            c_vp]),
     "spex_lightgcn_train_bpr_sampled_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i64, c_i32, ctypes.c_uint64,
+                                                           ctypes.c_uint32, c_i32, c_i32, c_i64, c_f32, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp,
+                                                           c_vp]),
+    "spex_lightgcn_epoch_bce_sampled_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.c_uint64,
+                                                           ctypes.c_uint32, c_i32, c_i64, c_f32, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                           c_vp]),
+    "spex_lightgcn_train_bce_sampled_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.c_uint64,
                                                            ctypes.c_uint32, c_i32, c_i32, c_i64, c_f32, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp,
                                                            c_vp]),
     "spex_ngcf_step_bce_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),

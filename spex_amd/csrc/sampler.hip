@@ -190,7 +190,138 @@ __global__ __launch_bounds__(256) void sample_bpr_triples_kernel(const int32_t *
     }
 }
 
+// ---- BCE epochs (include/spex_hip.h: spex_sample_bce_epoch states the stream word by word; tests restate it from there)
+// MurmurHash3's 32-bit finaliser
+__device__ __forceinline__ uint32_t fmix32(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x85EBCA6Bu;
+    x ^= x >> 13;
+    x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+
+// The shuffle's six round keys: uniform per launch, drawn once on the host by the entry point (kernel arguments: no registers).
+struct BceRoundKeys {
+    uint32_t k[6];
+};
+
+// One thread per OUTPUT slot: the keyed bijection perm (a balanced Feistel network on 2 h bits, cycle-walked back into [0, n)) names
+// the source sample the slot holds, so the epoch is written already shuffled — no sort, no second pass.  Sources [0, P) are the
+// positives in the caller's order, source P + k is negative k % num_ng of positive k / num_ng (ng_sample's order), its draw keyed by k.
+__global__ __launch_bounds__(256) void sample_bce_epoch_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ items,
+                                                               int n_user_rows, const int32_t *__restrict__ pos_user,
+                                                               const int32_t *__restrict__ pos_item, uint32_t n_pos, uint32_t num_ng,
+                                                               int num_item, uint32_t n, uint32_t h, BceRoundKeys keys, uint32_t seed_lo,
+                                                               uint32_t seed_hi, uint32_t epoch, int64_t *__restrict__ users,
+                                                               int64_t *__restrict__ items_out, float *__restrict__ labels)
+{
+    const uint32_t stride = gridDim.x * blockDim.x, mask = (1u << h) - 1u;      // (h <= 16; n < 2^31: slot + stride cannot wrap)
+    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < n; slot += stride) {
+        uint32_t x = slot;
+        do {                       // a permutation of [0, 2^(2 h)) walked from inside [0, n) comes back inside: no cap needed
+            uint32_t l = x >> h, r = x & mask;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const uint32_t f = l ^ (fmix32(r ^ keys.k[q]) & mask);
+                l = r;
+                r = f;
+            }
+            x = (l << h) | r;
+        } while (x >= n);
+        if (x < n_pos) {
+            users[slot] = pos_user[x];
+            items_out[slot] = pos_item[x];
+            labels[slot] = 1.0f;
+            continue;
+        }
+        const uint32_t k = x - n_pos;
+        const int u = pos_user[k / num_ng];
+        int beg = 0, end = 0;
+        if (u >= 0 && u < n_user_rows) {
+            beg = rowptr[u];
+            end = rowptr[u + 1];
+        }
+        // bounded rejection (candidates 0 .. 7), then the direct draw of the k-th admissible item — the same uniform law, and it
+        // terminates for a user who holds most of the catalogue
+        int j = 0;
+        bool done = false;
+        for (uint32_t stage = 0; stage < 2u && !done; ++stage) {
+            const Philox4 c = philox4x32_10(k, 0u, epoch, stage, seed_lo, seed_hi);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                if (!done) {
+                    j = to_range(c.w[a], num_item);
+                    done = !row_has(items, beg, end, j);
+                }
+            }
+        }
+        if (!done) {
+            const int deg = end - beg, admissible = num_item - deg;
+            if (admissible > 0) {
+                const Philox4 r2 = philox4x32_10(k, 0u, epoch, 2u, seed_lo, seed_hi);
+                const int kth = to_range(r2.w[0], admissible);
+                int lo = 0, hi = deg;  // first position m with items[beg+m] - m > kth  (admissible items below it)
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (items[beg + mid] - mid > kth) hi = mid;
+                    else lo = mid + 1;
+                }
+                j = kth + lo;
+            } else {
+                j = 0;  // the user has every item: no valid negative exists
+            }
+        }
+        users[slot] = u;
+        items_out[slot] = j;
+        labels[slot] = 0.0f;
+    }
+}
+
 }  // namespace
+
+// Standard Philox4x32-10 on the host: the entry point draws the shuffle's round keys with it.
+static void philox4x32_10_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
+{
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+extern "C" int spex_sample_bce_epoch(const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows, const int32_t *d_pos_user,
+                                     const int32_t *d_pos_item, int64_t n_pos, int32_t num_ng, int32_t num_item, uint64_t seed, uint32_t epoch,
+                                     int64_t *d_users, int64_t *d_items_out, float *d_labels, void *stream)
+{
+    SPEX_CHECK_ARG(d_rowptr && d_items && d_pos_user && d_pos_item && d_users && d_items_out && d_labels, "spex_sample_bce_epoch: NULL pointer");
+    SPEX_CHECK_ARG(n_pos >= 0 && num_ng >= 1 && num_item >= 1 && n_user_rows >= 0,
+                   "spex_sample_bce_epoch: n_pos=%lld num_ng=%d num_item=%d n_user_rows=%d (needs n_pos >= 0, num_ng >= 1, num_item >= 1)",
+                   (long long)n_pos, num_ng, num_item, n_user_rows);
+    SPEX_CHECK_ARG(n_pos < ((int64_t)1 << 31) && n_pos * ((int64_t)num_ng + 1) < ((int64_t)1 << 31),
+                   "spex_sample_bce_epoch: n_pos=%lld x (1 + num_ng=%d) samples: the shuffle needs fewer than 2^31", (long long)n_pos, num_ng);
+    if (n_pos == 0) return SPEX_OK;
+    const uint32_t n = (uint32_t)(n_pos * ((int64_t)num_ng + 1));
+    uint32_t bits = 0;                                   // bit length of n - 1
+    while (bits < 32 && ((n - 1) >> bits) != 0) ++bits;
+    const uint32_t h = bits <= 2 ? 1u : (bits + 1) / 2;   // max(1, ceil(bits / 2)): the Feistel halves
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    uint32_t a[4], b[4];
+    philox4x32_10_host(0u, 0u, epoch, 3u, k0, k1, a);
+    philox4x32_10_host(1u, 0u, epoch, 3u, k0, k1, b);
+    const BceRoundKeys keys{{a[0], a[1], a[2], a[3], b[0], b[1]}};
+    int64_t blocks = ((int64_t)n + 255) / 256;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(sample_bce_epoch_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_rowptr, d_items, n_user_rows,
+                       d_pos_user, d_pos_item, (uint32_t)n_pos, (uint32_t)num_ng, num_item, n, h, keys, k0, k1, epoch, d_users, d_items_out,
+                       d_labels);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
 
 extern "C" int spex_sample_bpr_triples(const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows, const int32_t *d_active,
                                        int32_t n_active, int32_t num_item, int64_t n, int32_t mode, uint64_t seed, uint32_t epoch,

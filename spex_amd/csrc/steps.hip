@@ -323,6 +323,45 @@ extern "C" int spex_lightgcn_train_bpr_sampled_f32(spex_lightgcn_step_t *s, cons
     return SPEX_OK;
 }
 
+// A sampled BCE epoch: negatives, labels and the shuffle drawn on the device (sampler.hip: one launch into the caller's buffers) and
+// consumed by spex_lightgcn_epoch_bce_f32 — nothing crosses the host.  Every argument check of both calls comes before the sampler's
+// launch.
+extern "C" int spex_lightgcn_epoch_bce_sampled_f32(spex_lightgcn_step_t *s, const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows,
+                                                   const int32_t *d_pos_user, const int32_t *d_pos_item, int64_t n_pos, int32_t num_ng,
+                                                   int32_t num_item, uint64_t seed, uint32_t epoch, int32_t B, int64_t max_steps,
+                                                   float keep_prob, uint32_t drop_seed, int64_t *users, int64_t *items, float *labels,
+                                                   float *loss_full, float *loss_ragged, void *stream)
+{
+    const char *who = "spex_lightgcn_epoch_bce_sampled_f32";
+    SPEX_CHECK_ARG(s && s->graph && s->graph_t, "%s: NULL step descriptor or graph", who);
+    SPEX_CHECK_ARG(users && items && labels && loss_full && loss_ragged && B >= 1, "%s: NULL pointer or B < 1", who);
+    SPEX_CHECK_ARG(keep_prob > 0.0f && keep_prob <= 1.0f, "%s: keep_prob %g", who, keep_prob);
+    SPEX_TRY(spex_sample_bce_epoch(d_rowptr, d_items, n_user_rows, d_pos_user, d_pos_item, n_pos, num_ng, num_item, seed, epoch, users, items,
+                                   labels, stream));
+    return spex_lightgcn_epoch_bce_f32(s, users, items, labels, n_pos * ((int64_t)num_ng + 1), B, max_steps, keep_prob, drop_seed, loss_full,
+                                       loss_ragged, stream);
+}
+
+// Epochs epoch0 .. epoch0 + n_epochs - 1 of the call above, back to back on one stream: the host queues epoch after epoch and never
+// waits.  One set of buffers: epoch e + 1's sampler launch is ordered behind epoch e's last step.  Edge dropout: epoch number E runs
+// with the mask seed drop_seed + 0x9E3779B9 E (mod 2^32), the BPR call's rule — the per-epoch call keys its masks by the step WITHIN
+// the epoch, so one drop_seed for every epoch would replay one mask sequence.
+extern "C" int spex_lightgcn_train_bce_sampled_f32(spex_lightgcn_step_t *s, const int32_t *d_rowptr, const int32_t *d_items, int32_t n_user_rows,
+                                                   const int32_t *d_pos_user, const int32_t *d_pos_item, int64_t n_pos, int32_t num_ng,
+                                                   int32_t num_item, uint64_t seed, uint32_t epoch0, int32_t n_epochs, int32_t B,
+                                                   int64_t max_steps, float keep_prob, uint32_t drop_seed, int64_t *users, int64_t *items,
+                                                   float *labels, float *loss_epochs, void *stream)
+{
+    SPEX_CHECK_ARG(n_epochs >= 0 && loss_epochs, "spex_lightgcn_train_bce_sampled_f32: n_epochs < 0 or NULL loss_epochs");
+    for (int32_t e = 0; e < n_epochs; ++e) {
+        const uint32_t epoch = epoch0 + (uint32_t)e;
+        SPEX_TRY(spex_lightgcn_epoch_bce_sampled_f32(s, d_rowptr, d_items, n_user_rows, d_pos_user, d_pos_item, n_pos, num_ng, num_item, seed,
+                                                     epoch, B, max_steps, keep_prob, drop_seed + 0x9E3779B9u * epoch, users, items, labels,
+                                                     loss_epochs + 2 * (size_t)e, loss_epochs + 2 * (size_t)e + 1, stream));
+    }
+    return SPEX_OK;
+}
+
 // train() of NGCF_SPEX/code/main_rec.py:116-131 over a whole pre-shuffled, device-resident epoch as ONE call: batch k = samples
 // [k B, min((k+1) B, n)) through spex_ngcf_step_bce_f32 (the default one-layer model; the step advances its own Adam and dropout
 // counters) — the host issues the launches and nothing else.  Loss sums as in spex_lightgcn_epoch_bce_f32.

@@ -644,6 +644,34 @@ def sample_bpr_triples(rowptr, items, active, num_item, n, seed, epoch, by="user
     return tuple(t[:n] for t in out)
 
 
+def sample_bce_epoch(rowptr, items, pos_user, pos_item, num_ng, num_item, seed, epoch, out=None):
+    """One BCE epoch drawn on the GPU, already shuffled (spex_sample_bce_epoch; the stream is written down in include/spex_hip.h): every
+    positive (pos_user[j], pos_item[j]) with label 1 and num_ng negatives of its user with label 0, in the order of a keyed bijection of
+    (seed, epoch).  rowptr / items: device int32 CSR of R, rows ascending without duplicates; pos_user / pos_item: device int32 [P].  out:
+    (users int64, items int64, labels fp32) device tensors of at least n = P (1 + num_ng) elements to draw into (their first n are
+    returned); default: fresh ones.  Returns (users, items, labels) of n elements each."""
+    for t, name in ((rowptr, "rowptr"), (items, "items"), (pos_user, "pos_user"), (pos_item, "pos_item")):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise ValueError(f"{name}: need a contiguous torch.int32 CUDA tensor")
+    P, num_ng = pos_user.numel(), int(num_ng)
+    if pos_item.numel() != P or num_ng < 1:
+        raise ValueError("sample_bce_epoch: pos_user and pos_item need one length, and num_ng >= 1")
+    n = P * (1 + num_ng)
+    if n >= 2 ** 31:
+        raise ValueError(f"sample_bce_epoch: {n} samples: the shuffle needs fewer than 2^31")
+    if out is None:
+        out = tuple(torch.empty(n, dtype=dt, device=rowptr.device) for dt in (torch.int64, torch.int64, torch.float32))
+    for t, dt in zip(out, (torch.int64, torch.int64, torch.float32)):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= n):
+            raise ValueError("sample_bce_epoch: out needs contiguous (int64, int64, fp32) CUDA tensors of at least n elements")
+    if n == 0:                       # (an empty device tensor has no storage to point at)
+        return tuple(t[:0] for t in out)
+    _launch(rowptr.device, "spex_sample_bce_epoch", _ptr(rowptr), _ptr(items), rowptr.numel() - 1, _ptr(pos_user), _ptr(pos_item), P, num_ng,
+            int(num_item), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, *(ctypes.c_void_p(t.data_ptr()) for t in out))
+    _bump(*out)
+    return tuple(t[:n] for t in out)
+
+
 # ------------------------------------------------------------------------------------------------ autograd glue
 def _flat_tables(user_w, item_w, strict=False):
     """The two embedding tables as one [N, d] buffer.  The drop-in model allocates them back-to-back so this is a

@@ -375,6 +375,53 @@ class LightGCNStepper:
         self.t = d.t
         _bump(self.E0, self.m, self.v, self.grad_E0, loss_epochs, *sampler.epoch_buffers())
 
+    # -- sampled BCE epochs: negatives, labels and the shuffle drawn on the device by the same native call that trains on them
+    def _one_call_bce_shape_ok(self):
+        """_one_call_ok without a batch: what the stepper itself must be for the one-call BCE step."""
+        masked = getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
+        return self.L >= 1 and self._wide_ok and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
+
+    def _sampled_bce_args(self, sampler, batch_size, max_steps, keep_prob, who):
+        if sampler.rowptr.device != self.E0.device:
+            raise ValueError(f"LightGCNStepper.{who}: the sampler's tables live on {sampler.rowptr.device}, the stepper on {self.E0.device}")
+        if not self._one_call_bce_shape_ok() or sampler.n < 1 or int(batch_size) < 1:
+            raise ValueError(f"LightGCNStepper.{who}: needs an embedding width of 64, 128 or 256, a sampler with n >= 1 and batch_size >= 1")
+        if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
+            raise ValueError(f"LightGCNStepper.{who}: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
+        d = self._prepare_desc(min(int(batch_size), sampler.n))
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        tables = (vp(sampler.rowptr), vp(sampler.items), sampler.rowptr.numel() - 1, vp(sampler.pos_user), vp(sampler.pos_item), sampler.n_pos,
+                  sampler.num_ng, sampler.n_items, sampler.seed & 0xFFFFFFFFFFFFFFFF)
+        loop = (int(batch_size), -1 if max_steps is None else int(max_steps), float(keep_prob))
+        return d, tables, loop, tuple(vp(t) for t in sampler.epoch_buffers())
+
+    def epoch_bce_sampled(self, sampler, epoch, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
+        """Epoch number `epoch` of a BceDeviceSampler drawn and trained as ONE native call (spex_lightgcn_epoch_bce_sampled_f32): one
+        sampler launch into the sampler's epoch buffers, then epoch_bce's loop over them — the state after it is that of
+        epoch_bce(*sampler.draw(epoch), ...).  loss_full / loss_ragged, max_steps, keep_prob, drop_seed as in epoch_bce."""
+        d, tables, loop, bufs = self._sampled_bce_args(sampler, batch_size, max_steps, keep_prob, "epoch_bce_sampled")
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        _launch(self.E0.device, "spex_lightgcn_epoch_bce_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
+                int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
+        self.t = d.t
+        _bump(self.E0, self.m, self.v, loss_full, loss_ragged, *sampler.epoch_buffers())
+
+    def train_bce_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
+        """n_epochs sampled BCE epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
+        (spex_lightgcn_train_bce_sampled_f32): no host thread, no synchronisation.  loss_epochs: a contiguous fp32 device tensor of
+        2 n_epochs elements, zeroed by the caller — epoch e's loss sums of the full batches / of the ragged last one accumulate into
+        elements 2 e and 2 e + 1.  Under edge dropout epoch number E runs with the mask seed bpr_epoch_drop_seed(drop_seed, E)."""
+        if not (loss_epochs.is_cuda and loss_epochs.dtype == torch.float32 and loss_epochs.is_contiguous()
+                and loss_epochs.numel() >= 2 * int(n_epochs) and int(n_epochs) >= 0):
+            raise ValueError("LightGCNStepper.train_bce_sampled: loss_epochs needs to be a contiguous fp32 device tensor of 2 n_epochs elements")
+        if int(n_epochs) == 0:
+            return
+        d, tables, loop, bufs = self._sampled_bce_args(sampler, batch_size, max_steps, keep_prob, "train_bce_sampled")
+        _launch(self.E0.device, "spex_lightgcn_train_bce_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
+                *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
+        self.t = d.t
+        _bump(self.E0, self.m, self.v, loss_epochs, *sampler.epoch_buffers())
+
 
 def dataloader_epoch_order(n):
     """The index order `DataLoader(dataset, shuffle=True)` walks in one epoch, drawn from the GLOBAL torch RNG exactly as
@@ -506,21 +553,53 @@ def _run_epochs(n_epochs, prepare, train, after_epoch, overlap):
     return totals
 
 
-def train_epochs(stepper, train_data, n_epochs, batch_size=256, edge_dropout=None, after_epoch=None):
+def train_epochs(stepper, train_data, n_epochs, batch_size=256, edge_dropout=None, after_epoch=None, max_steps=None, first_epoch=0):
     """n_epochs x train_epoch with the NEXT epoch's negatives and shuffle prepared on a second host thread while the GPU trains the
     current one (an Epinion2 epoch: 0.14 s of sampling beside 0.38 s of steps; the NumPy / torch generators drawn in the order of a
     sequential `ng_sample(); train_epoch()` loop: same negatives, same shuffles, same run).  Not under the "reference" edge-dropout
     stream, whose per-step masks are drawn from torch's generator on the host: that loop runs sequentially.  after_epoch(epoch,
     loss_sum_tensor) runs between epochs (evaluation: the reference's Test() draws no random numbers — a callback that does would see
-    them drawn AFTER the next epoch's).  Returns the per-epoch loss sums (main_rec.py:36)."""
+    them drawn AFTER the next epoch's).  Returns the per-epoch loss sums (main_rec.py:36).  max_steps: at most that many batches per
+    epoch.
+    train_data a BceDeviceSampler: no second thread and no global generator — epochs first_epoch .. first_epoch + n_epochs - 1 are drawn
+    on the device.  Without after_epoch the whole run is ONE native call (LightGCNStepper.train_bce_sampled) and one synchronisation
+    at its end; with it, one native call per epoch.  Under edge dropout epoch e runs with the mask seed bpr_epoch_drop_seed(seed, e)
+    either way."""
+    if isinstance(train_data, BceDeviceSampler):
+        return _train_epochs_bce_sampled(stepper, train_data, n_epochs, batch_size, edge_dropout, after_epoch, max_steps, int(first_epoch))
     totals = _run_epochs(n_epochs, lambda: epoch_arrays(train_data),
-                         lambda arrays: train_epoch(stepper, train_data, batch_size=batch_size, edge_dropout=edge_dropout, arrays=arrays),
+                         lambda arrays: train_epoch(stepper, train_data, batch_size=batch_size, edge_dropout=edge_dropout, arrays=arrays,
+                                                    max_steps=max_steps),
                          after_epoch, overlap=_edge_dropout_args(edge_dropout)[1] != "reference")
     return [float(t) for t in totals]
 
 
+def _train_epochs_bce_sampled(stepper, sampler, n_epochs, batch_size, edge_dropout, after_epoch, max_steps, first_epoch):
+    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
+    if stream is not None and stepper.graph_t is stepper.graph:
+        raise ValueError("train_epochs(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation")
+    one_call = (after_epoch is None and n_epochs > 0 and sampler.n > 0 and stream in (None, "philox") and stepper._one_call_bce_shape_ok()
+                and (stream is None or stepper.L >= 2))
+    if one_call:
+        acc = torch.zeros(n_epochs, 2, 1, dtype=torch.float32, device=stepper.E0.device)
+        with _gc_paused():
+            stepper.train_bce_sampled(sampler, n_epochs, batch_size, acc, max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed,
+                                      first_epoch=first_epoch)
+        n_done = min(sampler.n, len(_batch_starts(sampler.n, batch_size, max_steps)) * batch_size)
+        host = acc.cpu()                                  # the run's one synchronisation
+        return [float(_sum_of_batch_means(host[e], n_done, batch_size)) for e in range(n_epochs)]
+    totals = []
+    for e in range(first_epoch, first_epoch + n_epochs):
+        drop = None if stream is None else (keep_prob, stream, bpr_epoch_drop_seed(seed, e) if stream == "philox" else seed)
+        total = train_epoch(stepper, sampler, batch_size=batch_size, edge_dropout=drop, max_steps=max_steps, epoch=e)
+        totals.append(total)
+        if after_epoch is not None:
+            after_epoch(e - first_epoch, total)
+    return [float(t) for t in totals]
+
+
 def train_epoch(stepper, train_data, batch_size=256, resample=True, pause_gc=True, edge_dropout=None, max_steps=None,
-                step_losses=None, arrays=None):
+                step_losses=None, arrays=None, epoch=0):
     """Train() of main_rec.py:25-38 without the per-step host work of its DataLoader loop: negatives are drawn like the
     reference's (`train_data.ng_sample()`, NumPy global RNG), the epoch's sample order is the DataLoader's own
     (dataloader_epoch_order), the whole shuffled epoch is moved to the device once, and every batch is one
@@ -530,14 +609,30 @@ def train_epoch(stepper, train_data, batch_size=256, resample=True, pause_gc=Tru
     step (edge_dropout_mask) on the stepper's graph and graph_t — which must then be the transposed handle carrying the edge-id
     permutation, since the masked operator is not symmetric.  max_steps: stop after that many batches; step_losses: a list that
     receives every step's mean loss (synchronises per step: a validation aid).  arrays: the epoch's (users, items, labels) host arrays
-    already sampled and shuffled (epoch_arrays) — train_epochs prepares the next epoch's while this one runs."""
-    arrays = arrays if arrays is not None else epoch_arrays(train_data, resample)
+    already sampled and shuffled (epoch_arrays) — train_epochs prepares the next epoch's while this one runs.
+    train_data a BceDeviceSampler: epoch number `epoch` is drawn on the device (its law is the reference's, its stream is not) — drawn
+    AND trained in one native call (LightGCNStepper.epoch_bce_sampled) where the native epoch applies, drawn by sampler.draw(epoch) for
+    the step-by-step loop otherwise; resample and arrays are not read."""
+    sampler = train_data if isinstance(train_data, BceDeviceSampler) else None
+    if sampler is None:
+        arrays = arrays if arrays is not None else epoch_arrays(train_data, resample)
     keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
     if stream is not None and stepper.graph_t is stepper.graph:
         raise ValueError("train_epoch(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id "
                          "permutation (LightGCN._transposed()): a masked adjacency is not symmetric")
     dev = stepper.E0.device
-    users, items, labels = _upload(dev, *arrays)
+    if sampler is not None:
+        if sampler.rowptr.device != dev:
+            raise ValueError(f"train_epoch: the sampler's tables live on {sampler.rowptr.device}, the stepper on {dev}")
+        if (step_losses is None and stream in (None, "philox") and sampler.n > 0 and stepper._one_call_bce_shape_ok()
+                and (stream is None or stepper.L >= 2)):
+            acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
+            with _gc_paused(pause_gc):
+                stepper.epoch_bce_sampled(sampler, epoch, batch_size, acc[0], acc[1], max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed)
+            return _sum_of_batch_means(acc, min(sampler.n, len(_batch_starts(sampler.n, batch_size, max_steps)) * batch_size), batch_size)
+        users, items, labels = sampler.draw(epoch)
+    else:
+        users, items, labels = _upload(dev, *arrays)
     n = users.numel()
     starts = _batch_starts(n, batch_size, max_steps)
     acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)     # loss sums of the full batches / of the ragged last one
@@ -657,6 +752,52 @@ class BprDeviceSampler:
         reads ahead of the next epoch's draw)."""
         if self._buffers is None:
             self._buffers = tuple(torch.empty(self.n, dtype=torch.int64, device=self.device) for _ in range(3))
+        return self._buffers
+
+
+class BceDeviceSampler:
+    """BCE epochs drawn on the device (ops.sample_bce_epoch): what LightTrainData.ng_sample() and the DataLoader's shuffle prepare on the
+    host — every positive with label 1, num_ng negatives of its user (uniform over the items the user does not hold) with label 0, the
+    whole epoch in a shuffled order — written by one launch.  The law is the reference's; the stream is neither NumPy's nor torch's, so
+    for the same seed the individual samples differ (the exact-replay path stays LightTrainData).  Holds the tables of
+    bpr_sampler_tables and the positives, in the order given and with their duplicates, in HBM.  draw(epoch) returns that epoch's
+    (users, items, labels) device tensors — a function of (seed, epoch) alone.  Pass the sampler itself to train_epoch / train_epochs /
+    LightGCNStepper.epoch_bce_sampled and the epoch samples and trains in one native call: no host thread, no global generator.
+    Not callable and without ng_sample on purpose: nothing can mistake it for host data."""
+
+    def __init__(self, train_pairs, n_users, n_items, num_ng=5, seed=0, device="cuda"):
+        pairs = np.asarray(train_pairs, dtype=np.int64).reshape(-1, 2)
+        rowptr, items, _ = bpr_sampler_tables(pairs, n_users, n_items)
+        self.n_pos, self.num_ng = len(pairs), int(num_ng)
+        if self.num_ng < 1:
+            raise ValueError(f"BceDeviceSampler: num_ng must be at least 1 (got {num_ng})")
+        self.n = self.n_pos * (1 + self.num_ng)
+        if self.n >= 2 ** 31:
+            raise ValueError(f"BceDeviceSampler: {self.n} samples per epoch: the device shuffle needs fewer than 2^31")
+        self.device = torch.device(device)
+        self.rowptr, self.items, self.pos_user, self.pos_item = (
+            torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device) for a in (rowptr, items, pairs[:, 0], pairs[:, 1]))
+        self.n_items, self.seed = int(n_items), int(seed)
+        self._buffers = None          # the buffers of the native epoch calls (epoch_buffers)
+
+    @classmethod
+    def from_train_data(cls, train_data, n_users=None, seed=0, device="cuda"):
+        """The sampler of a LightTrainData: its positives (`_ps`, in its order), `num_item` and `num_ng`.  n_users: the number of user
+        rows (default: the largest user index + 1)."""
+        pairs = np.asarray(train_data._ps, dtype=np.int64).reshape(-1, 2)
+        if n_users is None:
+            n_users = int(pairs[:, 0].max()) + 1 if len(pairs) else 0
+        return cls(pairs, n_users, train_data.num_item, num_ng=train_data.num_ng, seed=seed, device=device)
+
+    def draw(self, epoch):
+        """Epoch `epoch`'s samples as three fresh device tensors: users int64 [n], items int64 [n], labels fp32 [n]."""
+        return ops.sample_bce_epoch(self.rowptr, self.items, self.pos_user, self.pos_item, self.num_ng, self.n_items, self.seed, epoch)
+
+    def epoch_buffers(self):
+        """(users int64 [n], items int64 [n], labels fp32 [n]) device buffers, allocated once: what the native sampled epochs draw into
+        (stream order keeps one epoch's reads ahead of the next epoch's draw)."""
+        if self._buffers is None:
+            self._buffers = tuple(torch.empty(self.n, dtype=dt, device=self.device) for dt in (torch.int64, torch.int64, torch.float32))
         return self._buffers
 
 
