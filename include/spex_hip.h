@@ -393,7 +393,7 @@ int spex_lightgcn_batch_slots_f32(const spex_graph_t *g, const float *X, const f
                                   float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream);
 
 /* The batch-sized middle of the exact BPR step as ONE launch — the three-row sibling of spex_lightgcn_batch_f32, d == 64 ONLY
- * (d = 128 / 256 are rejected: they keep the launch-by-launch form).  Triple t has rows u = users[t], p = n_user_rows + pos[t],
+ * (d = 128 / 256 are rejected here: spex_lightgcn_bpr_batch_wide_f32 below takes them).  Triple t has rows u = users[t], p = n_user_rows + pos[t],
  * n = n_user_rows + neg[t]:
  *   light_r = (acc_in[r] + (A X)[r]) / acc_div for the three rows (bit-identical to spex_spmm_f32 / spex_spmm_rowlist_f32 for rows
  *             of <= 1 024 entries, also under an edge mask on the handle)
@@ -416,6 +416,20 @@ int spex_lightgcn_bpr_batch_slots_f32(const spex_graph_t *g, const float *X, con
                                       const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows, float grad_scale,
                                       float weight_decay, const float *E0, int32_t *row_counts, float *loss_sum, float *loss_per_sample,
                                       float *grad_slots, int32_t d, void *stream);
+/* The same two launches at d = 128 / 256 ONLY (any other d is rejected; d == 64 takes the two entry points above, which promised 64
+ * and keep rejecting everything else — a caller whose tables are 64 wide must not be able to ask for a wider gather by accident).
+ * Same arguments, same arithmetic per column; X, acc_in and E0 must be 16-byte aligned (rows move as dwordx2 / dwordx4 per lane).
+ * A row of <= 1 024 entries is bit-identical to spex_spmm_f32's row at this width, also under an edge mask; a dot product is a lane's
+ * d / 64 products (columns lane, lane + 64, ..) in ascending order and then a fixed tree; the push issues d / 64 row atomics of 256
+ * bytes per stored entry.  grad_slots: [3 T, d]. */
+int spex_lightgcn_bpr_batch_wide_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div, const int64_t *users,
+                                     const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows, float grad_scale,
+                                     float push_scale, float weight_decay, const float *E0, int32_t *row_counts, float *loss_sum,
+                                     float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream);
+int spex_lightgcn_bpr_batch_slots_wide_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div,
+                                           const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows,
+                                           float grad_scale, float weight_decay, const float *E0, int32_t *row_counts, float *loss_sum,
+                                           float *loss_per_sample, float *grad_slots, int32_t d, void *stream);
 
 /* Deterministic accumulation of a batch's per-slot rows into a dense [n_rows, d] table — replaces the float atomics of the row-
  * sparse backward where results must repeat bit for bit (and follows the order of the reference's CPU `index_put_(accumulate)` /
@@ -757,7 +771,11 @@ enum {
                                          * fork / join on the critical cycle; see spex_dual_task_step_t and spex_dual_task_step_join */
     SPEX_STEP_BPR_DENSE = 8,            /* exact BPR step only: force the dense form of the fast path (gradient rows into g_out, all-pull
                                          * backward) ... */
-    SPEX_STEP_BPR_PUSH = 16             /* ... or the push form, whatever T; neither flag: chosen by T (see spex_lightgcn_step_bpr_adam_f32) */
+    SPEX_STEP_BPR_PUSH = 16,            /* ... or the push form, whatever T; neither flag: chosen by T (see spex_lightgcn_step_bpr_adam_f32) */
+    SPEX_STEP_WIDE = 32                 /* exact BPR step only: this descriptor's tables and slots are d wide with d = 128 or 256.  The BCE step
+                                         * needs no such flag (it took the three widths from its first version); the BPR entry point promised
+                                         * d == 64 ONLY and rejects a descriptor whose d says otherwise — callers rely on that rejection for a
+                                         * 64-wide descriptor with a wrong d, which would gather out of bounds — so a wider d is an opt-in */
 };
 /* The north-star step — LightGCN L-layer propagation + the fused BPR gather + dot + sigmoid + SGD kernel over T triples — as one
  * call of at most L + 1 launches: EVERY whole-graph layer in the plain form (no epilogue operand, one output stream); the layer-1 launch also sets
@@ -790,7 +808,7 @@ typedef struct spex_lightgcn_step {
     int32_t slot_capacity, n_user_rows, L, d;
     float lr, beta1, beta2, eps;
     int32_t t;
-    int32_t flags;                           /* SPEX_STEP_DETERMINISTIC */
+    int32_t flags;                           /* SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE / _PUSH, SPEX_STEP_WIDE */
     /* appended for spex_lightgcn_step_bpr_adam_f32 / spex_lightgcn_epoch_bpr_f32 (the BCE entry points never read them): */
     float weight_decay;                      /* >= 0: upstream LightGCN's L2 term on the E0 rows of the batch */
     int32_t *row_counts;                     /* [2, N] int32, all-zero before the first call: per-row occurrence counts, by step parity */
@@ -809,12 +827,13 @@ int spex_lightgcn_epoch_bce_f32(spex_lightgcn_step_t *step, const int64_t *users
 
 /* The exact BPR training step — upstream LightGCN's training semantics: BPR differentiated through the propagation, an L2 term on
  * the E0 rows of the batch, Adam — as ONE call with the schedule of spex_lightgcn_step_bce_f32 and the triple-shaped batch kernel
- * (spex_lightgcn_bpr_batch_f32) in the middle.  d == 64 ONLY (any other width is rejected: d = 128 / 256 keep the launch-by-launch
- * form); the descriptor's buffers as for the BCE step, with slot_capacity >= 3 T and row_counts [2, N] int32 (all-zero before the
+ * (spex_lightgcn_bpr_batch_f32; at d = 128 / 256 spex_lightgcn_bpr_batch_wide_f32) in the middle.  d == 64 — any other width is
+ * rejected — unless flags carries SPEX_STEP_WIDE: then d = 128 or 256 (any other width is rejected) and every table and slot of the
+ * descriptor is d wide; the epoch and sampled-epoch calls below go through this step and take the same descriptors.  The descriptor's buffers as for the BCE step, with slot_capacity >= 3 T and row_counts [2, N] int32 (all-zero before the
  * first call; every call leaves the table of the next step's parity all-zero).
  *   loss = mean_t softplus(xn_t - xp_t) + weight_decay * 0.5 * sum_t (|E0[u_t]|^2 + |E0[p_t]|^2 + |E0[n_t]|^2) / T
  *   fast path: L-1 x spex_spmm_f32 (plain for L <= 3) -> spex_lightgcn_bpr_batch_f32 -> L-1 x spex_spmm_f32 on A^T (all plain at
- *   L == 3) -> Adam (sums the per-triple losses in order, adds the L2 gradient): 2 L launches.  From 768 triples up (measured on Epinion2;
+ *   L == 3) -> Adam (sums the per-triple losses in order, adds the L2 gradient): 2 L launches.  From 768 (d = 64), 1 024 (d = 128) or 512 (d = 256) triples up (measured on Epinion2;
  *   SPEX_STEP_BPR_DENSE / SPEX_STEP_BPR_PUSH force either form) the same batch launch skips the push — its gradient rows go to the
  *   dense g_out with atomics — and spex_propagate_bwd_f32 runs the whole backward in pull form.
  *   SPEX_STEP_DETERMINISTIC: spex_lightgcn_bpr_batch_slots_f32 -> spex_reduce_slots_f32 (users; then pos and neg) ->

@@ -79,6 +79,10 @@ SIGNATURES = {
                                                    c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "spex_lightgcn_bpr_batch_slots_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp,
                                                          c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "spex_lightgcn_bpr_batch_wide_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp,
+                                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "spex_lightgcn_bpr_batch_slots_wide_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp,
+                                                              c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "spex_reduce_slots_f32": (ctypes.c_int, [c_vp, c_i32, c_i64, c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_f32, c_vp, c_i32, c_i32, c_vp]),
     "spex_expert_gate_rows_bwd_parts": (c_i32, [c_i32]),
     "spex_expert_gate_rows_bwd_det_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i32, c_i64, c_i64, c_i64, c_i32,
@@ -174,6 +178,7 @@ STEP_FIXED_TASK_WEIGHTS = 2     # spex_hip.h: SPEX_STEP_FIXED_TASK_WEIGHTS
 STEP_PIPELINED = 4              # spex_hip.h: SPEX_STEP_PIPELINED
 STEP_BPR_DENSE = 8              # spex_hip.h: SPEX_STEP_BPR_DENSE
 STEP_BPR_PUSH = 16              # spex_hip.h: SPEX_STEP_BPR_PUSH
+STEP_WIDE = 32                  # spex_hip.h: SPEX_STEP_WIDE (exact BPR step at d = 128 / 256)
 
 
 class NGCFStepDesc(ctypes.Structure):

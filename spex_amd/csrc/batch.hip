@@ -285,8 +285,8 @@ __global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_batch_kernel(
 }
 
 // The batch-sized middle of the exact BPR step (BPR differentiated through the propagation, Adam: upstream LightGCN's training
-// semantics) as one launch: lightgcn_batch_kernel with THREE rows per workgroup.  d == 64 only (d = 128 / 256 keep the
-// launch-by-launch form).  Workgroup (triple t, part p), rows ru = u[t], rp = n_user_rows + pos[t], rn = n_user_rows + neg[t]:
+// semantics) as one launch: lightgcn_batch_kernel with THREE rows per workgroup.  d == 64 (d = 128 / 256:
+// lightgcn_bpr_batch_wide_kernel below).  Workgroup (triple t, part p), rows ru = u[t], rp = n_user_rows + pos[t], rn = n_user_rows + neg[t]:
 //   1. last layer at the three rows: each row's 64-entry segments go to its virtual waves v = segment mod 16, the three rows' virtual
 //      waves numbered jointly and dealt to the 16 waves, segment sums added in segment order through LDS — a row of <= 1 024 entries is
 //      the spex_spmm_f32 / spex_spmm_rowlist_f32 row bit for bit, also under an edge mask;
@@ -642,6 +642,204 @@ __global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_batch_wide_kernel(
     }
 }
 
+
+// lightgcn_bpr_batch_kernel for wider embeddings, d = 64 V (V = 2, 4): the cross product of the two kernels above — three rows per
+// workgroup as in lightgcn_bpr_batch_kernel (rows selected by wave-uniform sel3 selects on scalars, never an indexed array: no
+// scratch), V consecutive columns per lane in the forward and columns lane, lane + 64, .. behind the layer mean as in
+// lightgcn_batch_wide_kernel.  Same workgroup shape, same dealing of segments to virtual waves and of push runs to (part, wave),
+// same kBprBatchParts / kBprBatchRunsPerPart.
+//   1. forward through segment_sum_wide<V, MASKED> (64 result registers at every width), every column's chain in entry order, segment
+//      sums added in segment order through LDS: a row of <= 1 024 entries is the spex_spmm_f32 row at this width bit for bit, masked
+//      or not;
+//   2. xp, xn: a lane's V products in ascending column order (one fmaf chain each), then the fixed DPP tree; z, loss, dg and the three
+//      gradient rows as in the V = 1 kernel; |E0[r]|^2: a lane's V consecutive columns in ascending order (one chain from the first
+//      square), then the same tree;
+//   3. PUSH: V 256-byte atomics per row and per stored entry; !PUSH: the slots as V plain 256-byte stores per row.
+// LDS: segment partials [3][16][64 V] + the three light rows + three norms: 12.75 V KB (25.5 KB at V = 2, 51 KB at V = 4).
+template <bool PUSH, int V>
+__global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_bpr_batch_wide_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, int n_rows, int n_user_rows,
+    const float *__restrict__ X, const float *__restrict__ acc_in, float acc_div, const int64_t *__restrict__ users,
+    const int64_t *__restrict__ pos, const int64_t *__restrict__ neg, int parts, float grad_scale, float push_scale, float *loss_sum,
+    float *__restrict__ loss_rows, float *g_out, float *G, int runs_per_part, float *__restrict__ grad_slots, int T,
+    const float *__restrict__ acc2, const float *__restrict__ acc3, float weight_decay, const float *__restrict__ E0,
+    int32_t *row_counts, const spex::EdgeDrop drop)
+{
+    typedef typename spex::WideVec<V>::T vec;
+    constexpr int kRow = kWave * V;
+    constexpr int KPRE = kPre;                    // push runs a wave loads ahead
+    __shared__ float s_part[3][kWgWaves][kRow];   // [row: user, positive, negative][virtual wave][column block j][lane]
+    __shared__ float s_light[3][kRow];            // the three light rows, by column
+    __shared__ float s_norm[3];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int t = blockIdx.x / parts, part = blockIdx.x % parts;
+    const int64_t u64 = users[t], p64 = pos[t], n64 = neg[t];
+    const int64_t n_items = (int64_t)n_rows - n_user_rows;
+    if (u64 < 0 || u64 >= n_user_rows || p64 < 0 || p64 >= n_items || n64 < 0 || n64 >= n_items) {   // workgroup-uniform
+        if (loss_rows && part == 0 && threadIdx.x == 0) loss_rows[t] = 0.0f;
+        if (!PUSH && wave < 3) {
+#pragma unroll
+            for (int c = 0; c < V; ++c) grad_slots[((size_t)wave * T + t) * kRow + c * kWave + lane] = 0.0f;
+        }
+        return;
+    }
+    const int r0 = (int)u64, r1 = (int)p64 + n_user_rows, r2 = (int)n64 + n_user_rows;
+    const int beg0 = rowptr[r0], beg1 = rowptr[r1], beg2 = rowptr[r2];
+    const int deg0 = rowptr[r0 + 1] - beg0, deg1 = rowptr[r1 + 1] - beg1, deg2 = rowptr[r2 + 1] - beg2;
+    const int my_row = sel3(wave, r0, r1, r2);             // (waves 0 .. 2 own a row each behind the forward)
+    // the running layer sum at the three rows, ((E^0 + E^1) + E^2) + y, and the E^0 rows of the L2 term
+    vec run = (vec)(0.0f), e0v = (vec)(0.0f);
+    if (wave < 3) {
+        const size_t o = (size_t)my_row * kRow + lane * V;
+        run = *reinterpret_cast<const vec *>(acc_in + o);
+        vec q2 = (vec)(0.0f), q3 = (vec)(0.0f);
+        if (acc2) q2 = *reinterpret_cast<const vec *>(acc2 + o);
+        if (acc3) q3 = *reinterpret_cast<const vec *>(acc3 + o);
+        if (weight_decay > 0.0f) e0v = *reinterpret_cast<const vec *>(E0 + o);
+        if (acc2) run = run + q2;
+        if (acc3) run = run + q3;
+    }
+    // the push's runs of 16 entries, the three rows' runs numbered jointly and dealt over (part, wave)
+    const int n_run0 = (deg0 + 15) >> 4, n_run1 = (deg1 + 15) >> 4, n_run2 = (deg2 + 15) >> 4, n_runs = n_run0 + n_run1 + n_run2;
+    const bool push = PUSH && G != nullptr;                 // (G == NULL: the dense form — gradient rows into g_out only, no push)
+    const int want = (n_runs + runs_per_part - 1) / runs_per_part;
+    const int act = !push ? 1 : (want < parts ? (want < 1 ? 1 : want) : parts);
+    if (part >= act) return;
+    const int q_step = act * kWgWaves;
+    int q = part * kWgWaves + wave;
+    int p_col[KPRE], p_cnt[KPRE], p_side[KPRE];
+    float p_val[KPRE];
+    auto load_runs = [&](int q0) {
+#pragma unroll
+        for (int p = 0; p < KPRE; ++p) {
+            const int qq = q0 + p * q_step;
+            p_col[p] = 0;
+            p_val[p] = 0.0f;
+            p_cnt[p] = 0;
+            p_side[p] = 0;
+            if (qq < n_runs) {
+                const int side = (qq >= n_run0) + (qq >= n_run0 + n_run1), rr = qq - sel3(side, 0, n_run0, n_run0 + n_run1);
+                const int base = sel3(side, beg0, beg1, beg2) + rr * 16, left = sel3(side, deg0, deg1, deg2) - rr * 16;
+                p_side[p] = side;
+                p_cnt[p] = left < 16 ? left : 16;
+                if (lane < p_cnt[p]) {
+                    p_col[p] = col[base + lane];
+                    p_val[p] = val[base + lane];
+                    if (drop.mode != 0) p_val[p] = spex::edge_kept(drop, base + lane) ? p_val[p] / drop.keep_prob : 0.0f;   // the forward's mask
+                }
+            }
+        }
+    };
+    if (push) load_runs(q);
+    // ---- 1. last layer at the three rows: segments to virtual waves v = segment mod 16, the three rows' virtual waves dealt to the 16 waves
+    const int nseg0 = (deg0 + kTaskEntries - 1) / kTaskEntries, nseg1 = (deg1 + kTaskEntries - 1) / kTaskEntries,
+              nseg2 = (deg2 + kTaskEntries - 1) / kTaskEntries;
+    const int nv0 = nseg0 < kWgWaves ? nseg0 : kWgWaves, nv1 = nseg1 < kWgWaves ? nseg1 : kWgWaves, nv2 = nseg2 < kWgWaves ? nseg2 : kWgWaves;
+    const int nv = nv0 + nv1 + nv2;
+    const float *__restrict__ Xl = X + lane * V;
+    for (int j = wave; j < nv; j += kWgWaves) {
+        const int side = (j >= nv0) + (j >= nv0 + nv1), v = j - sel3(side, 0, nv0, nv0 + nv1);
+        const int s_beg = sel3(side, beg0, beg1, beg2), s_deg = sel3(side, deg0, deg1, deg2), s_nseg = sel3(side, nseg0, nseg1, nseg2);
+        vec acc = (vec)(0.0f);
+        for (int sgi = v; sgi < s_nseg; sgi += kWgWaves) {
+            const int left = s_deg - sgi * kTaskEntries;
+            const int cnt = left < kTaskEntries ? left : kTaskEntries;
+            if (drop.mode != 0) acc = spex::segment_sum_wide<V, true>(col, val, Xl, s_beg + sgi * kTaskEntries, cnt, lane, acc, drop);
+            else acc = spex::segment_sum_wide<V, false>(col, val, Xl, s_beg + sgi * kTaskEntries, cnt, lane, acc, drop);
+        }
+#pragma unroll
+        for (int c = 0; c < V; ++c) s_part[side][v][c * kWave + lane] = acc[c];
+    }
+    __syncthreads();
+    // ---- 2. layer mean at the three rows (waves 0 .. 2), the two scores, the three gradient rows
+    if (wave < 3) {
+        const int lim = sel3(wave, nv0, nv1, nv2);
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+            float y = lim > 0 ? s_part[wave][0][c * kWave + lane] : 0.0f;
+            for (int w = 1; w < lim; ++w) y = y + s_part[wave][w][c * kWave + lane];   // segment order
+            float s = run[c] + y;
+            if (acc_div != 1.0f) s = s / acc_div;
+            s_light[wave][lane * V + c] = s;                                  // by column: what follows owns columns lane + 64 c
+        }
+        if (weight_decay > 0.0f) {
+            float sq = e0v[0] * e0v[0];
+#pragma unroll
+            for (int c = 1; c < V; ++c) sq = fmaf(e0v[c], e0v[c], sq);        // the lane's columns in ascending order, then the fixed tree
+            const float nrm = wave_sum_f32(sq);
+            if (lane == 0) s_norm[wave] = nrm;
+        }
+    }
+    __syncthreads();
+    // (from here on a lane owns columns lane, lane + 64, ...: every store and every atomic below covers 256 contiguous bytes)
+    vec lu, lp, ln;
+    float dp = 0.0f, dn = 0.0f;
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+        lu[c] = s_light[0][c * kWave + lane];
+        lp[c] = s_light[1][c * kWave + lane];
+        ln[c] = s_light[2][c * kWave + lane];
+        dp = fmaf(lu[c], lp[c], dp);
+        dn = fmaf(lu[c], ln[c], dn);
+    }
+    const float xp = wave_sum_f32(dp), xn = wave_sum_f32(dn);
+    const float z = xn - xp;
+    const float dg = sigmoid_f(z) * grad_scale;
+    const vec gn = dg * lu, gu = dg * (ln - lp), gp = -gn;   // d loss / d light at the negative, the user, the positive row
+    if (part == 0 && wave < 3) {
+        if (wave == 0 && lane == 0) {
+            float loss = fmaxf(z, 0.0f) + log1pf(expf(-fabsf(z)));
+            if (weight_decay > 0.0f) loss = loss + 0.5f * weight_decay * ((s_norm[0] + s_norm[1]) + s_norm[2]);
+            if (loss_rows) loss_rows[t] = loss;
+            else atomicAdd(loss_sum, loss);
+        }
+        if (row_counts && lane == 0) atomicAdd(row_counts + my_row, 1);       // occurrences of the row in the batch: the L2 gradient's weight
+        const vec gw = wave == 0 ? gu : (wave == 1 ? gp : gn);
+        if (!PUSH) {
+#pragma unroll
+            for (int c = 0; c < V; ++c) grad_slots[((size_t)wave * T + t) * kRow + c * kWave + lane] = gw[c];
+        } else {
+            const size_t o = (size_t)my_row * kRow + lane;
+#pragma unroll
+            for (int c = 0; c < V; ++c) {
+                if (g_out) atomicAdd(g_out + o + c * kWave, gw[c]);
+                if (push) atomicAdd(G + o + c * kWave, push_scale * gw[c]);   // the `g` of (g + A^T g) / (L + 1)
+            }
+        }
+    }
+    if (!push) return;
+    // ---- 3. push over the three rows' entries (lightgcn_batch_kernel's loop: lane 0 of every loaded run is read before the first atomic)
+    float *out_l = G + lane;
+    const vec gsu = push_scale * gu, gsp = push_scale * gp, gsn = push_scale * gn;
+    for (;;) {
+        int c0[KPRE];
+        float v0[KPRE];
+#pragma unroll
+        for (int p = 0; p < KPRE; ++p) {
+            c0[p] = __builtin_amdgcn_readlane(p_col[p], 0);
+            v0[p] = lane_bcast(p_val[p], 0);
+        }
+#pragma unroll
+        for (int p = 0; p < KPRE; ++p) {
+            const vec gs = p_side[p] == 0 ? gsu : (p_side[p] == 1 ? gsp : gsn);
+            if (p_cnt[p] > 0) {
+#pragma unroll
+                for (int c = 0; c < V; ++c) atomicAdd(out_l + (size_t)c0[p] * kRow + c * kWave, v0[p] * gs[c]);
+            }
+#pragma unroll 1
+            for (int j = 1; j < p_cnt[p]; ++j) {
+                const int cc = __builtin_amdgcn_readlane(p_col[p], j);
+                const float v = lane_bcast(p_val[p], j);
+#pragma unroll
+                for (int c = 0; c < V; ++c) atomicAdd(out_l + (size_t)cc * kRow + c * kWave, v * gs[c]);
+            }
+        }
+        q += KPRE * q_step;
+        if (q >= n_runs) break;
+        load_runs(q);
+    }
+}
 
 // The dual-task model's rec branch has the expert gate between the layer mean and the score (utility1/model_expert_s.py:154-168),
 // so its batch-sized middle cannot include the push (the gate's backward comes first).  Its FORWARD half is one launch of the
@@ -1283,20 +1481,80 @@ int spex::lightgcn_batch_layers(const spex_graph_t *g, const float *X, const flo
     return SPEX_OK;
 }
 
-// ---- the BPR triple form (d == 64 only)
+// ---- the BPR triple form.  The narrow exports promised d == 64 only (their callers' tables are 64 wide: a larger d would gather out
+//      of bounds), so the wide kernel has exports of its own; the internal *_layers forms dispatch on d (what the step calls).
+enum BprWidths { kBprNarrow, kBprWide, kBprAny };
 static int bpr_batch_check(const char *who, const spex_graph_t *g, const float *X, const float *acc_in, const int64_t *users,
                            const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows, float weight_decay, const float *E0,
-                           int32_t d)
+                           int32_t d, BprWidths widths = kBprAny)
 {
     SPEX_CHECK_ARG(g && X && acc_in && T >= 0 && (T == 0 || (users && pos && neg)), "%s: NULL argument or T < 0", who);
     SPEX_CHECK_ARG(n_user_rows >= 0 && n_user_rows <= g->n_rows && g->n_rows == g->n_cols, "%s: n_user_rows=%d on a %d x %d graph", who,
                    n_user_rows, g->n_rows, g->n_cols);
     SPEX_CHECK_ARG(weight_decay >= 0.0f && (weight_decay == 0.0f || E0), "%s: weight_decay %g needs E0 (and must not be negative)", who,
                    (double)weight_decay);
-    if (d != kWave) {
-        spex::set_error("%s: d == 64 only (got %d); d = 128 / 256 take the launch-by-launch form", who, d);
+    if (widths == kBprNarrow && d != kWave) {
+        spex::set_error("%s: d == 64 only (got %d); d = 128 / 256 take the _wide entry point", who, d);
         return SPEX_ERR_UNSUPPORTED;
     }
+    if (widths == kBprWide && d != 2 * kWave && d != 4 * kWave) {
+        spex::set_error("%s: d = 128 or 256 only (got %d); d == 64 takes the narrow entry point (the name without _wide)", who, d);
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    if (d != kWave && d != 2 * kWave && d != 4 * kWave) {
+        spex::set_error("%s: d = 64, 128 or 256 only (got %d)", who, d);
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    return SPEX_OK;
+}
+
+static int bpr_batch_slots_go(const char *who, BprWidths widths, const spex_graph_t *g, const float *X, const float *acc_in,
+                              const float *acc2, const float *acc3, float acc_div, const int64_t *users, const int64_t *pos,
+                              const int64_t *neg, int32_t T, int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0,
+                              int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream)
+{
+    int rc = bpr_batch_check(who, g, X, acc_in, users, pos, neg, T, n_user_rows, weight_decay, E0, d, widths);
+    if (rc != SPEX_OK) return rc;
+    SPEX_CHECK_ARG((loss_sum || loss_per_sample) && grad_slots && acc_div != 0.0f && (!acc3 || acc2),
+                   "%s: needs loss_sum or loss_per_sample, grad_slots, acc_div != 0 (and acc2 with acc3)", who);
+    SPEX_CHECK_ARG(d == kWave || (wide_aligned(X, acc_in, acc2, acc3) && wide_aligned(E0, nullptr, nullptr, nullptr)),
+                   "%s: X / acc_in / E0 must be 16-byte aligned at d > 64", who);
+    if (T == 0 || g->n_rows == 0) return SPEX_OK;
+#define SPEX_GO(KERNEL)                                                                                                                    \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)T), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val, g->n_rows,   \
+                       n_user_rows, X, acc_in, acc_div, users, pos, neg, 1, grad_scale, 0.0f, loss_sum, loss_per_sample, nullptr, nullptr, \
+                       1, grad_slots, T, acc2, acc3, weight_decay, E0, row_counts, edge_drop_of(g))
+    if (d == kWave) SPEX_GO(lightgcn_bpr_batch_kernel<false>);
+    else if (d == 2 * kWave) SPEX_GO((lightgcn_bpr_batch_wide_kernel<false, 2>));
+    else SPEX_GO((lightgcn_bpr_batch_wide_kernel<false, 4>));
+#undef SPEX_GO
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
+
+static int bpr_batch_go(const char *who, BprWidths widths, const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2,
+                        const float *acc3, float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
+                        int32_t n_user_rows, float grad_scale, float push_scale, float weight_decay, const float *E0, int32_t *row_counts,
+                        float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream)
+{
+    int rc = bpr_batch_check(who, g, X, acc_in, users, pos, neg, T, n_user_rows, weight_decay, E0, d, widths);
+    if (rc != SPEX_OK) return rc;
+    SPEX_CHECK_ARG((loss_sum || loss_per_sample) && (G || g_out) && G != g_out && acc_div != 0.0f && (!acc3 || acc2),
+                   "%s: needs loss_sum or loss_per_sample, G and / or g_out (two tables), acc_div != 0 (and acc2 with acc3)", who);
+    SPEX_CHECK_ARG(d == kWave || (wide_aligned(X, acc_in, acc2, acc3) && wide_aligned(E0, nullptr, nullptr, nullptr)),
+                   "%s: X / acc_in / E0 must be 16-byte aligned at d > 64", who);
+    if (T == 0 || g->n_rows == 0) return SPEX_OK;
+    const int parts = G ? kBprBatchParts : 1, runs_per_part = kBprBatchRunsPerPart;     // (no push: one workgroup per triple)
+    SPEX_CHECK_ARG((int64_t)T * parts < (int64_t)1 << 31, "%s: T=%d is too many triples for one launch", who, T);
+#define SPEX_GO(KERNEL)                                                                                                                    \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)T * parts), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val,      \
+                       g->n_rows, n_user_rows, X, acc_in, acc_div, users, pos, neg, parts, grad_scale, push_scale, loss_sum,               \
+                       loss_per_sample, g_out, G, runs_per_part, nullptr, T, acc2, acc3, weight_decay, E0, row_counts, edge_drop_of(g))
+    if (d == kWave) SPEX_GO(lightgcn_bpr_batch_kernel<true>);
+    else if (d == 2 * kWave) SPEX_GO((lightgcn_bpr_batch_wide_kernel<true, 2>));
+    else SPEX_GO((lightgcn_bpr_batch_wide_kernel<true, 4>));
+#undef SPEX_GO
+    SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }
 
@@ -1306,8 +1564,18 @@ extern "C" int spex_lightgcn_bpr_batch_slots_f32(const spex_graph_t *g, const fl
                                                  int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *grad_slots,
                                                  int32_t d, void *stream)
 {
-    return spex::lightgcn_bpr_batch_slots_layers(g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg, T, n_user_rows, grad_scale,
-                                                 weight_decay, E0, row_counts, loss_sum, loss_per_sample, grad_slots, d, stream);
+    return bpr_batch_slots_go("spex_lightgcn_bpr_batch_slots_f32", kBprNarrow, g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg, T,
+                              n_user_rows, grad_scale, weight_decay, E0, row_counts, loss_sum, loss_per_sample, grad_slots, d, stream);
+}
+
+extern "C" int spex_lightgcn_bpr_batch_slots_wide_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div,
+                                                      const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
+                                                      int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0,
+                                                      int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *grad_slots,
+                                                      int32_t d, void *stream)
+{
+    return bpr_batch_slots_go("spex_lightgcn_bpr_batch_slots_wide_f32", kBprWide, g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg,
+                              T, n_user_rows, grad_scale, weight_decay, E0, row_counts, loss_sum, loss_per_sample, grad_slots, d, stream);
 }
 
 int spex::lightgcn_bpr_batch_slots_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
@@ -1315,17 +1583,9 @@ int spex::lightgcn_bpr_batch_slots_layers(const spex_graph_t *g, const float *X,
                                           int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0, int32_t *row_counts,
                                           float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream)
 {
-    const char *who = "spex_lightgcn_bpr_batch_slots_f32";
-    int rc = bpr_batch_check(who, g, X, acc_in, users, pos, neg, T, n_user_rows, weight_decay, E0, d);
-    if (rc != SPEX_OK) return rc;
-    SPEX_CHECK_ARG((loss_sum || loss_per_sample) && grad_slots && acc_div != 0.0f && (!acc3 || acc2),
-                   "%s: needs loss_sum or loss_per_sample, grad_slots, acc_div != 0 (and acc2 with acc3)", who);
-    if (T == 0 || g->n_rows == 0) return SPEX_OK;
-    hipLaunchKernelGGL(lightgcn_bpr_batch_kernel<false>, dim3((unsigned)T), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col,
-                       g->val, g->n_rows, n_user_rows, X, acc_in, acc_div, users, pos, neg, 1, grad_scale, 0.0f, loss_sum, loss_per_sample,
-                       nullptr, nullptr, 1, grad_slots, T, acc2, acc3, weight_decay, E0, row_counts, edge_drop_of(g));
-    SPEX_HIP(hipGetLastError());
-    return SPEX_OK;
+    return bpr_batch_slots_go(d == kWave ? "spex_lightgcn_bpr_batch_slots_f32" : "spex_lightgcn_bpr_batch_slots_wide_f32", kBprAny, g, X,
+                              acc_in, acc2, acc3, acc_div, users, pos, neg, T, n_user_rows, grad_scale, weight_decay, E0, row_counts,
+                              loss_sum, loss_per_sample, grad_slots, d, stream);
 }
 
 extern "C" int spex_lightgcn_bpr_batch_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div, const int64_t *users,
@@ -1333,8 +1593,18 @@ extern "C" int spex_lightgcn_bpr_batch_f32(const spex_graph_t *g, const float *X
                                            float push_scale, float weight_decay, const float *E0, int32_t *row_counts, float *loss_sum,
                                            float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream)
 {
-    return spex::lightgcn_bpr_batch_layers(g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg, T, n_user_rows, grad_scale, push_scale,
-                                           weight_decay, E0, row_counts, loss_sum, loss_per_sample, g_out, G, d, stream);
+    return bpr_batch_go("spex_lightgcn_bpr_batch_f32", kBprNarrow, g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg, T, n_user_rows,
+                        grad_scale, push_scale, weight_decay, E0, row_counts, loss_sum, loss_per_sample, g_out, G, d, stream);
+}
+
+extern "C" int spex_lightgcn_bpr_batch_wide_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div,
+                                                const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
+                                                int32_t n_user_rows, float grad_scale, float push_scale, float weight_decay, const float *E0,
+                                                int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *g_out, float *G,
+                                                int32_t d, void *stream)
+{
+    return bpr_batch_go("spex_lightgcn_bpr_batch_wide_f32", kBprWide, g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg, T,
+                        n_user_rows, grad_scale, push_scale, weight_decay, E0, row_counts, loss_sum, loss_per_sample, g_out, G, d, stream);
 }
 
 int spex::lightgcn_bpr_batch_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
@@ -1343,19 +1613,9 @@ int spex::lightgcn_bpr_batch_layers(const spex_graph_t *g, const float *X, const
                                     int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d,
                                     void *stream)
 {
-    const char *who = "spex_lightgcn_bpr_batch_f32";
-    int rc = bpr_batch_check(who, g, X, acc_in, users, pos, neg, T, n_user_rows, weight_decay, E0, d);
-    if (rc != SPEX_OK) return rc;
-    SPEX_CHECK_ARG((loss_sum || loss_per_sample) && (G || g_out) && G != g_out && acc_div != 0.0f && (!acc3 || acc2),
-                   "%s: needs loss_sum or loss_per_sample, G and / or g_out (two tables), acc_div != 0 (and acc2 with acc3)", who);
-    if (T == 0 || g->n_rows == 0) return SPEX_OK;
-    const int parts = G ? kBprBatchParts : 1, runs_per_part = kBprBatchRunsPerPart;     // (no push: one workgroup per triple)
-    SPEX_CHECK_ARG((int64_t)T * parts < (int64_t)1 << 31, "%s: T=%d is too many triples for one launch", who, T);
-    hipLaunchKernelGGL(lightgcn_bpr_batch_kernel<true>, dim3((unsigned)T * parts), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr,
-                       g->col, g->val, g->n_rows, n_user_rows, X, acc_in, acc_div, users, pos, neg, parts, grad_scale, push_scale, loss_sum,
-                       loss_per_sample, g_out, G, runs_per_part, nullptr, T, acc2, acc3, weight_decay, E0, row_counts, edge_drop_of(g));
-    SPEX_HIP(hipGetLastError());
-    return SPEX_OK;
+    return bpr_batch_go(d == kWave ? "spex_lightgcn_bpr_batch_f32" : "spex_lightgcn_bpr_batch_wide_f32", kBprAny, g, X, acc_in, acc2, acc3,
+                        acc_div, users, pos, neg, T, n_user_rows, grad_scale, push_scale, weight_decay, E0, row_counts, loss_sum,
+                        loss_per_sample, g_out, G, d, stream);
 }
 
 int spex::rows_train_push(const spex_graph_t *push, const float *rows_raw, const float *rows_prop, const float *att_u, const float *att_i,

@@ -24,8 +24,9 @@ __device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, flo
 
 // (g and zero_buf carry no __restrict__: the caller may pass the gradient buffer itself to be cleared — every element is
 // read before the same thread clears it)
-// L2: the exact BPR step's pass — gradient += l2.scale * l2.count[row] * p[row] (rows of 64 parameters: 16 float4 steps), the other
-// parity's count table cleared by the thread that holds a row's first columns, and the whole gradient stored to l2.g_store.
+// L2: the exact BPR step's pass — gradient += l2.scale * l2.count[row] * p[row] (rows of 64 / 128 / 256 parameters: 1 << l2.shift
+// float4 steps, shift = 4 / 5 / 6), the other parity's count table cleared by the thread that holds a row's first columns, and the
+// whole gradient stored to l2.g_store.
 template <bool L2>
 __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *g,
                                                    float *__restrict__ m, float *__restrict__ v, int64_t n4,
@@ -76,12 +77,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
             G.x = G.x + A.x / add_div; G.y = G.y + A.y / add_div; G.z = G.z + A.z / add_div; G.w = G.w + A.w / add_div;
         }
         if constexpr (L2) {
-            const int64_t row = i >> 4;
+            const int64_t row = i >> l2.shift;
             if (l2.count) {
                 const float c = l2.scale * (float)l2.count[row];
                 G.x = G.x + c * P.x; G.y = G.y + c * P.y; G.z = G.z + c * P.z; G.w = G.w + c * P.w;
             }
-            if (l2.clear && (i & 15) == 0) l2.clear[row] = 0;
+            if (l2.clear && (i & (((int64_t)1 << l2.shift) - 1)) == 0) l2.clear[row] = 0;
             if (l2.g_store) reinterpret_cast<float4 *>(l2.g_store)[i] = G;
         }
         float4 M = reinterpret_cast<float4 *>(m)[i];
@@ -115,8 +116,9 @@ int spex::adam_step_z2(float *p, const float *g, float *m, float *v, int64_t n, 
 {
     spex::L2Rows l2{};
     if (l2_in) l2 = *l2_in;
-    SPEX_CHECK_ARG(!l2_in || (n % 64 == 0 && (((uintptr_t)l2.g_store) & 15) == 0 && l2.g_store != p && l2.g_store != m && l2.g_store != v),
-                   "spex_adam_step_f32: the L2 form takes whole rows of 64 and a 16-byte aligned gradient store");
+    SPEX_CHECK_ARG(!l2_in || (l2.shift >= 4 && l2.shift <= 6 && n % ((int64_t)4 << l2.shift) == 0 && (((uintptr_t)l2.g_store) & 15) == 0
+                              && l2.g_store != p && l2.g_store != m && l2.g_store != v),
+                   "spex_adam_step_f32: the L2 form takes whole rows of 64, 128 or 256 and a 16-byte aligned gradient store");
     SPEX_CHECK_ARG(!add_g || ((((uintptr_t)add_g) & 15) == 0 && add_div != 0.0f), "spex_adam_step_f32: add_g unaligned or add_div == 0");
     spex::SmallAdam small{};
     if (small_in) small = *small_in;

@@ -18,11 +18,12 @@ struct SmallAdam {          // a second, small parameter block updated by the sa
     int64_t stride = 0;
     int32_t n = 0;
 };
-struct L2Rows {             // the exact BPR step's L2 term, applied by its Adam launch: gradient += scale * count[row] * p[row], rows of 64
+struct L2Rows {             // the exact BPR step's L2 term, applied by its Adam launch: gradient += scale * count[row] * p[row]
     const int32_t *count = nullptr;   // occurrences of every table row in this step's batch (written by the batch kernel)
     int32_t *clear = nullptr;         // the OTHER step parity's count table, cleared here (no thread clears a cell another still reads)
     float scale = 0.0f;               // weight_decay / T
     float *g_store = nullptr;         // receives the step's whole gradient (product + add_g share + L2 term); may be g itself
+    int32_t shift = 4;                // log2 of a row's float4 count: 4 / 5 / 6 for rows of 64 / 128 / 256
 };
 int adam_step_z2(float *p, const float *g, float *m, float *v, int64_t n, int32_t t, float lr, float beta1, float beta2, float eps,
                  float *zero_buf, float *zero_buf2, void *stream, const float *loss_rows = nullptr, int32_t n_loss = 0,
@@ -53,7 +54,7 @@ int lightgcn_batch_slots_layers(const spex_graph_t *g, const float *X, const flo
                                 float acc_div, const int64_t *users, const int64_t *items, const float *labels, int32_t B,
                                 int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d,
                                 void *stream);
-// (the exact BPR step's batch-sized middle, three rows per triple, d == 64: batch.hip)
+// (the exact BPR step's batch-sized middle, three rows per triple; d = 64, or 128 / 256 through the wide kernel: batch.hip)
 int lightgcn_bpr_batch_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
                               float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows,
                               float grad_scale, float push_scale, float weight_decay, const float *E0, int32_t *row_counts,

@@ -145,7 +145,8 @@ extern "C" int spex_lightgcn_epoch_bce_f32(spex_lightgcn_step_t *s, const int64_
 
 // The exact BPR training step — BPR differentiated through the propagation, an L2 term on the E0 rows of the batch, Adam: upstream
 // LightGCN's training semantics — as ONE call.  The schedule is spex_lightgcn_step_bce_f32's with the triple-shaped batch kernel
-// (batch.hip: lightgcn_bpr_batch_kernel, three rows per workgroup) in the middle; d == 64 only.
+// (batch.hip: lightgcn_bpr_batch_kernel, three rows per workgroup; lightgcn_bpr_batch_wide_kernel at d = 128 / 256) in the middle.
+// d == 64, or — for a descriptor that carries SPEX_STEP_WIDE: its tables and slots are d wide — d = 128 / 256.
 //   fast path:      L - 1 whole-graph launches (plain for L <= 3) -> spex_lightgcn_bpr_batch_f32 (last layer at the 3 T rows, scores,
 //                   loss, gradient rows, (g + A^T g) / (L + 1) in push form) -> L - 1 pull products on A^T (all plain at L == 3:
 //                   A^T (A^T P) + P) -> Adam, which sums the per-triple losses in order and adds the L2 gradient: 2 L launches
@@ -161,7 +162,10 @@ extern "C" int spex_lightgcn_epoch_bce_f32(spex_lightgcn_step_t *s, const int64_
 // entries, a third pull product's does not.  Measured on Epinion2, L = 3, us per step push / dense, both forced, alternating
 // (tools/bpr_exact_step_time.py --sweep, profiles/bpr_exact/form_sweep.jsonl): T = 256: 71.8 / 80.2, 512: 84.1 / 86.9,
 // 768: 95.2 / 92.5, 1 024: 105.9 / 98.8, 1 536: 127.3 / 108.8, 2 048: 150.3 / 120.3, 4 096: 241.0 / 167.6.
-constexpr int32_t kBprStepDenseMinTriples = 768;
+// d = 128 / 256, the same sweep (--recdim; profiles/bpr_exact_wide/form_sweep_d128.jsonl, _d256.jsonl; two rounds), the
+// smallest swept T from which the dense form wins by more than the windows' spread in both rounds: d = 128: 768: 158.5 / 158.2 and
+// 159.1 / 159.8 (no), 1 024: 176.5 / 165.3; d = 256: 256: 214.9 / 224.6 (no), 512: 247.1 / 234.6 and 246.0 / 232.6.
+constexpr int32_t kBprStepDenseMinTriples = 768, kBprStepDenseMinTriples128 = 1024, kBprStepDenseMinTriples256 = 512;
 
 extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const int64_t *users, const int64_t *pos, const int64_t *neg,
                                                int32_t T, float *loss_sum, void *stream)
@@ -174,7 +178,12 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     const spex_graph *g = s->graph, *gt = s->graph_t;
     const int32_t L = s->L, d = s->d, n_u = s->n_user_rows;
     SPEX_CHECK_ARG(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_rows, "%s: square graphs of one size", who);
-    if (d != 64) {
+    if ((s->flags & SPEX_STEP_WIDE) != 0) {
+        if (d != 128 && d != 256) {
+            spex::set_error("%s: SPEX_STEP_WIDE takes d = 128 or 256 (got %d); d == 64 runs without the flag — the widths are 64, 128 and 256", who, d);
+            return SPEX_ERR_UNSUPPORTED;
+        }
+    } else if (d != 64) {
         spex::set_error("%s: d == 64 only (got %d); d = 128 / 256 take the launch-by-launch form", who, d);
         return SPEX_ERR_UNSUPPORTED;
     }
@@ -196,6 +205,7 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     l2.clear = cnt_other;
     l2.scale = wd / (float)T;
     l2.g_store = s->grad_E0;
+    l2.shift = d == 64 ? 4 : (d == 128 ? 5 : 6);
     // ---- forward: layers 0 .. L-2 over the whole graph (plain for L <= 3), the last layer at the batch's rows only
     const bool plain = L >= 2 && L <= 3;
     const float *cur = s->E0;
@@ -220,7 +230,8 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
         s->t = t_next;
         return SPEX_OK;
     }
-    const bool dense = (s->flags & SPEX_STEP_BPR_DENSE) != 0 || ((s->flags & SPEX_STEP_BPR_PUSH) == 0 && T >= kBprStepDenseMinTriples);
+    const int32_t dense_min = d == 64 ? kBprStepDenseMinTriples : (d == 128 ? kBprStepDenseMinTriples128 : kBprStepDenseMinTriples256);
+    const bool dense = (s->flags & SPEX_STEP_BPR_DENSE) != 0 || ((s->flags & SPEX_STEP_BPR_PUSH) == 0 && T >= dense_min);
     if (dense) {
         // ---- large batches: the same launch with the push skipped — the gradient rows go to the dense g_out with atomics — and the
         //      whole backward in pull form (L products: their cost does not grow with T, the push's does)

@@ -481,14 +481,18 @@ def lightgcn_batch(graph, X, acc_in, acc_div, users, items, labels, n_user_rows,
     return loss_sum if loss_per_sample is None else loss_per_sample
 
 
-def _bpr_batch_args(name, graph, X, acc_in, users, pos, neg, weight_decay, E0, row_counts):
-    """Argument checks shared by lightgcn_bpr_batch / lightgcn_bpr_batch_slots (d == 64 only); returns T."""
+def _bpr_batch_args(name, graph, X, acc_in, users, pos, neg, weight_decay, E0, row_counts, wide=False):
+    """Argument checks shared by lightgcn_bpr_batch / lightgcn_bpr_batch_slots (d == 64 only) and their _wide forms (d = 128 / 256
+    only); returns (T, d)."""
     n = graph.n_rows
-    if X.dim() != 2 or X.shape[1] != 64:
-        raise ValueError(f"{name}: d == 64 only (got shape {tuple(X.shape)}); d = 128 / 256 take the launch-by-launch form")
+    if not wide and (X.dim() != 2 or X.shape[1] != 64):
+        raise ValueError(f"{name}: d == 64 only (got shape {tuple(X.shape)}); d = 128 / 256 take {name}_wide")
+    if wide and (X.dim() != 2 or X.shape[1] not in (128, 256)):
+        raise ValueError(f"{name}: d = 128 or 256 only (got shape {tuple(X.shape)}); d == 64 takes {name[:-5]}")
+    d = X.shape[1]
     for t, nm in ((X, "X"), (acc_in, "acc_in"), (E0, "E0")):
-        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (n, 64)):
-            raise ValueError(f"{name}: {nm} must be a contiguous fp32 [{n}, 64] device tensor")
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (n, d)):
+            raise ValueError(f"{name}: {nm} must be a contiguous fp32 [{n}, {d}] device tensor")
     T = users.numel()
     for t, nm in ((users, "users"), (pos, "pos"), (neg, "neg")):
         if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == T):
@@ -498,26 +502,60 @@ def _bpr_batch_args(name, graph, X, acc_in, users, pos, neg, weight_decay, E0, r
     if row_counts is not None and not (row_counts.is_cuda and row_counts.dtype == torch.int32 and row_counts.is_contiguous()
                                        and row_counts.numel() >= n):
         raise ValueError(f"{name}: row_counts must be a contiguous int32 device tensor of >= {n} elements")
-    return T
+    return T, d
+
+
+def _bpr_batch_slots(name, entry, wide, graph, X, acc_in, acc_div, users, pos, neg, n_user_rows, grad_scale, grad_slots, loss_sum,
+                     loss_per_sample, weight_decay, E0, row_counts):
+    T, d = _bpr_batch_args(name, graph, X, acc_in, users, pos, neg, weight_decay, E0, row_counts, wide)
+    if not (grad_slots.is_cuda and grad_slots.dtype == torch.float32 and grad_slots.is_contiguous() and grad_slots.dim() == 2
+            and grad_slots.shape[0] >= 3 * T and grad_slots.shape[1] == d):
+        raise ValueError(f"{name}: grad_slots must be a contiguous fp32 [>= 3T, {d}] device tensor")
+    if loss_sum is None and loss_per_sample is None:
+        raise ValueError(f"{name}: needs loss_sum or loss_per_sample")
+    if loss_per_sample is not None and not (loss_per_sample.is_cuda and loss_per_sample.dtype == torch.float32
+                                            and loss_per_sample.is_contiguous() and loss_per_sample.numel() >= T):
+        raise ValueError(f"{name}: loss_per_sample must be a contiguous fp32 device tensor of >= T elements")
+    _launch(X.device, entry, graph._h, _ptr(X), _ptr(acc_in), float(acc_div), _ptr(users), _ptr(pos),
+            _ptr(neg), T, int(n_user_rows), float(grad_scale), float(weight_decay), _ptr(E0), _ptr(row_counts), _ptr(loss_sum),
+            _ptr(loss_per_sample), _ptr(grad_slots), d)
+    _bump(loss_sum, loss_per_sample, grad_slots, row_counts)
+
+
+def _bpr_batch(name, entry, wide, graph, X, acc_in, acc_div, users, pos, neg, n_user_rows, grad_scale, push_scale, loss_sum, g_out, G,
+               loss_per_sample, weight_decay, E0, row_counts):
+    T, d = _bpr_batch_args(name, graph, X, acc_in, users, pos, neg, weight_decay, E0, row_counts, wide)
+    n = graph.n_rows
+    for t, nm in ((g_out, "g_out"), (G, "G")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (n, d)):
+            raise ValueError(f"{name}: {nm} must be a contiguous fp32 [{n}, {d}] device tensor")
+    if G is None and g_out is None:
+        raise ValueError(f"{name}: needs the push target G and / or the dense g_out")
+    for t, k, nm in ((loss_sum, 1, "loss_sum"), (loss_per_sample, T, "loss_per_sample")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= k):
+            raise ValueError(f"{name}: {nm} must be a contiguous fp32 device tensor of >= {k} elements")
+    if loss_sum is None and loss_per_sample is None:
+        raise ValueError(f"{name}: needs loss_sum or loss_per_sample")
+    _launch(X.device, entry, graph._h, _ptr(X), _ptr(acc_in), float(acc_div), _ptr(users), _ptr(pos), _ptr(neg),
+            T, int(n_user_rows), float(grad_scale), float(push_scale), float(weight_decay), _ptr(E0), _ptr(row_counts), _ptr(loss_sum),
+            _ptr(loss_per_sample), _ptr(g_out), _ptr(G), d)
+    _bump(loss_sum, loss_per_sample, g_out, G, row_counts)
+    return loss_sum if loss_per_sample is None else loss_per_sample
 
 
 def lightgcn_bpr_batch_slots(graph, X, acc_in, acc_div, users, pos, neg, n_user_rows, grad_scale, grad_slots, loss_sum=None,
                              loss_per_sample=None, weight_decay=0.0, E0=None, row_counts=None):
     """spex_lightgcn_bpr_batch_slots_f32 (d == 64): the exact BPR step's batch kernel without push and without float atomics — the
     three gradient rows of triple t stored as grad_slots[t] (user), [T + t] (positive), [2 T + t] (negative)."""
-    T = _bpr_batch_args("lightgcn_bpr_batch_slots", graph, X, acc_in, users, pos, neg, weight_decay, E0, row_counts)
-    if not (grad_slots.is_cuda and grad_slots.dtype == torch.float32 and grad_slots.is_contiguous() and grad_slots.shape[0] >= 3 * T
-            and grad_slots.shape[1] == 64):
-        raise ValueError("lightgcn_bpr_batch_slots: grad_slots must be a contiguous fp32 [>= 3T, 64] device tensor")
-    if loss_sum is None and loss_per_sample is None:
-        raise ValueError("lightgcn_bpr_batch_slots: needs loss_sum or loss_per_sample")
-    if loss_per_sample is not None and not (loss_per_sample.is_cuda and loss_per_sample.dtype == torch.float32
-                                            and loss_per_sample.is_contiguous() and loss_per_sample.numel() >= T):
-        raise ValueError("lightgcn_bpr_batch_slots: loss_per_sample must be a contiguous fp32 device tensor of >= T elements")
-    _launch(X.device, "spex_lightgcn_bpr_batch_slots_f32", graph._h, _ptr(X), _ptr(acc_in), float(acc_div), _ptr(users), _ptr(pos),
-            _ptr(neg), T, int(n_user_rows), float(grad_scale), float(weight_decay), _ptr(E0), _ptr(row_counts), _ptr(loss_sum),
-            _ptr(loss_per_sample), _ptr(grad_slots), 64)
-    _bump(loss_sum, loss_per_sample, grad_slots, row_counts)
+    _bpr_batch_slots("lightgcn_bpr_batch_slots", "spex_lightgcn_bpr_batch_slots_f32", False, graph, X, acc_in, acc_div, users, pos, neg,
+                     n_user_rows, grad_scale, grad_slots, loss_sum, loss_per_sample, weight_decay, E0, row_counts)
+
+
+def lightgcn_bpr_batch_slots_wide(graph, X, acc_in, acc_div, users, pos, neg, n_user_rows, grad_scale, grad_slots, loss_sum=None,
+                                  loss_per_sample=None, weight_decay=0.0, E0=None, row_counts=None):
+    """spex_lightgcn_bpr_batch_slots_wide_f32: lightgcn_bpr_batch_slots at d = 128 / 256 (grad_slots: [>= 3T, d])."""
+    _bpr_batch_slots("lightgcn_bpr_batch_slots_wide", "spex_lightgcn_bpr_batch_slots_wide_f32", True, graph, X, acc_in, acc_div, users,
+                     pos, neg, n_user_rows, grad_scale, grad_slots, loss_sum, loss_per_sample, weight_decay, E0, row_counts)
 
 
 def lightgcn_bpr_batch(graph, X, acc_in, acc_div, users, pos, neg, n_user_rows, grad_scale, push_scale, loss_sum, g_out, G,
@@ -525,23 +563,15 @@ def lightgcn_bpr_batch(graph, X, acc_in, acc_div, users, pos, neg, n_user_rows, 
     """The batch-sized middle of the exact BPR step as one launch (spex_lightgcn_bpr_batch_f32, d == 64): last layer + layer mean at
     the triples' three rows, both scores, softplus(xn - xp) [+ the L2 share], the three gradient rows added into g_out (None: not
     formed) and G += push_scale * (g + A^T g) in push form (None: no push).  g_out, G: fp32 [N, 64], accumulated into (zero them first)."""
-    T = _bpr_batch_args("lightgcn_bpr_batch", graph, X, acc_in, users, pos, neg, weight_decay, E0, row_counts)
-    n = graph.n_rows
-    for t, nm in ((g_out, "g_out"), (G, "G")):
-        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (n, 64)):
-            raise ValueError(f"lightgcn_bpr_batch: {nm} must be a contiguous fp32 [{n}, 64] device tensor")
-    if G is None and g_out is None:
-        raise ValueError("lightgcn_bpr_batch: needs the push target G and / or the dense g_out")
-    for t, k, nm in ((loss_sum, 1, "loss_sum"), (loss_per_sample, T, "loss_per_sample")):
-        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= k):
-            raise ValueError(f"lightgcn_bpr_batch: {nm} must be a contiguous fp32 device tensor of >= {k} elements")
-    if loss_sum is None and loss_per_sample is None:
-        raise ValueError("lightgcn_bpr_batch: needs loss_sum or loss_per_sample")
-    _launch(X.device, "spex_lightgcn_bpr_batch_f32", graph._h, _ptr(X), _ptr(acc_in), float(acc_div), _ptr(users), _ptr(pos), _ptr(neg),
-            T, int(n_user_rows), float(grad_scale), float(push_scale), float(weight_decay), _ptr(E0), _ptr(row_counts), _ptr(loss_sum),
-            _ptr(loss_per_sample), _ptr(g_out), _ptr(G), 64)
-    _bump(loss_sum, loss_per_sample, g_out, G, row_counts)
-    return loss_sum if loss_per_sample is None else loss_per_sample
+    return _bpr_batch("lightgcn_bpr_batch", "spex_lightgcn_bpr_batch_f32", False, graph, X, acc_in, acc_div, users, pos, neg, n_user_rows,
+                      grad_scale, push_scale, loss_sum, g_out, G, loss_per_sample, weight_decay, E0, row_counts)
+
+
+def lightgcn_bpr_batch_wide(graph, X, acc_in, acc_div, users, pos, neg, n_user_rows, grad_scale, push_scale, loss_sum, g_out, G,
+                            loss_per_sample=None, weight_decay=0.0, E0=None, row_counts=None):
+    """spex_lightgcn_bpr_batch_wide_f32: lightgcn_bpr_batch at d = 128 / 256 (g_out, G: fp32 [N, d])."""
+    return _bpr_batch("lightgcn_bpr_batch_wide", "spex_lightgcn_bpr_batch_wide_f32", True, graph, X, acc_in, acc_div, users, pos, neg,
+                      n_user_rows, grad_scale, push_scale, loss_sum, g_out, G, loss_per_sample, weight_decay, E0, row_counts)
 
 
 def gated_batch_fwd(graph, X, acc_in, acc_div, raw, att_u, att_i, users, items, labels, n_user_rows, grad_scale, loss_sum, lo_batch,

@@ -189,6 +189,8 @@ class LightGCNStepper:
         d.t, d.lr = self.t, self.lr
         d.flags = _lib.STEP_DETERMINISTIC if self.deterministic else 0
         d.flags |= {None: 0, "push": _lib.STEP_BPR_PUSH, "dense": _lib.STEP_BPR_DENSE}[self.bpr_backward]     # (the BCE step ignores them)
+        if self.E0.shape[1] in (128, 256):
+            d.flags |= _lib.STEP_WIDE       # the exact BPR step's opt-in: every table and slot of this descriptor is d wide
         d.weight_decay = self.weight_decay
         d.row_counts = None if self.row_counts is None else self.row_counts.data_ptr()
         return d
@@ -271,10 +273,19 @@ class LightGCNStepper:
         propagated) are added with plain torch ops on the device.
         With `loss_acc` (a 1-element device buffer) and batch_rows_only=True the step is ONE library call
         (spex_lightgcn_step_bpr_adam_f32: last layer at the triples' rows, the batch-sized middle in one launch, 2 L launches) where
-        that applies — width 64, contiguous int64 device indices, the mask rules of the BCE step; the batch's loss SUM is accumulated
-        into loss_acc and None is returned.  Otherwise loss_acc, if given, still receives the loss sum."""
+        that applies — width 64, 128 or 256, contiguous int64 device indices, the mask rules of the BCE step; the batch's loss SUM is
+        accumulated into loss_acc and None is returned.  Otherwise loss_acc, if given, still receives the loss sum.
+        deterministic=True: only the one-call form takes its sums in a fixed order; the launch-by-launch form scores through
+        ops.bpr_loss_grad, which uses float atomics.  At width 128 / 256 a deterministic stepper therefore refuses the
+        launch-by-launch form (ValueError) instead of handing out atomics silently.  At width 64 it is left as it was — the
+        launch-by-launch step is what the one-call step is checked against there, in deterministic mode too
+        (tests/test_gpu_bpr_exact_step.py) — so at that width pass loss_acc and batch_rows_only=True for a reproducible step."""
         if batch_rows_only and loss_acc is not None and self._one_call_bpr_ok(users, pos, neg):
             return self._step_bpr_one_call(users, pos, neg, loss_acc)
+        if self.deterministic and self.E0.shape[1] != 64:
+            raise ValueError("LightGCNStepper(deterministic=True).step_bpr_exact: at width 128 / 256 only the one-call form is fixed-order — "
+                             "pass loss_acc and batch_rows_only=True with contiguous int64 device indices (the launch-by-launch form "
+                             "uses float atomics)")
         self.propagate()
         T = users.numel()
         lo = self.light_out
@@ -301,7 +312,7 @@ class LightGCNStepper:
     # -- the exact BPR step as one library call (spex_lightgcn_step_bpr_adam_f32) and the native epoch over it
     def _one_call_bpr_ok(self, users, pos, neg):
         masked = getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
-        return (self.L >= 1 and self.E0.shape[1] == 64 and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
+        return (self.L >= 1 and self._wide_ok and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
                 and all(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() for t in (users, pos, neg))
                 and users.numel() == pos.numel() == neg.numel() >= 1)
 
@@ -318,7 +329,7 @@ class LightGCNStepper:
         """A whole epoch of pre-drawn, device-resident triples as ONE native call (spex_lightgcn_epoch_bpr_f32): batch k = triples
         [k T, (k+1) T) through the one-call exact BPR step.  loss_full / loss_ragged, keep_prob and drop_seed as in epoch_bce."""
         if not self._one_call_bpr_ok(users[:1], pos[:1], neg[:1]):
-            raise ValueError("LightGCNStepper.epoch_bpr: needs an embedding width of 64 and contiguous int64 device tensors")
+            raise ValueError("LightGCNStepper.epoch_bpr: needs an embedding width of 64, 128 or 256 and contiguous int64 device tensors")
         if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
             raise ValueError("LightGCNStepper.epoch_bpr: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
         d = self._prepare_desc(min(int(batch_size), users.numel()), 3)
@@ -332,13 +343,13 @@ class LightGCNStepper:
     def _one_call_bpr_shape_ok(self):
         """_one_call_bpr_ok without a batch: what the stepper itself must be for the one-call exact BPR step."""
         masked = getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
-        return self.L >= 1 and self.E0.shape[1] == 64 and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
+        return self.L >= 1 and self._wide_ok and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
 
     def _sampled_args(self, sampler, batch_size, max_steps, keep_prob, who):
         if sampler.rowptr.device != self.E0.device:
             raise ValueError(f"LightGCNStepper.{who}: the sampler's tables live on {sampler.rowptr.device}, the stepper on {self.E0.device}")
         if not self._one_call_bpr_shape_ok() or sampler.n < 1 or int(batch_size) < 1:
-            raise ValueError(f"LightGCNStepper.{who}: needs an embedding width of 64, a sampler with n >= 1 and batch_size >= 1")
+            raise ValueError(f"LightGCNStepper.{who}: needs an embedding width of 64, 128 or 256, a sampler with n >= 1 and batch_size >= 1")
         if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
             raise ValueError(f"LightGCNStepper.{who}: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
         d = self._prepare_desc(min(int(batch_size), sampler.n), 3)
@@ -810,7 +821,7 @@ def train_epoch_bpr(stepper, triples_or_sampler, batch_size=2048, pause_gc=True,
     """One epoch of exact BPR training (upstream LightGCN: BPR through the propagation, L2 on the batch's E0 rows, Adam) over pre-drawn
     triples: (users, pos, neg) host arrays, or a callable returning them (e.g. lambda: bpr_epoch_triples(train, n_users, n_items, rng)).
     The epoch is moved to the device once and runs as ONE native call (LightGCNStepper.epoch_bpr) where nothing has to happen on the
-    host between two steps; otherwise (step_losses wanted, a host-drawn "reference" mask, a width other than 64) step by step through
+    host between two steps; otherwise (step_losses wanted, a host-drawn "reference" mask, a width other than 64 / 128 / 256) step by step through
     step_bpr_exact.  edge_dropout, max_steps, step_losses as in train_epoch.  Returns the epoch's sum of per-batch mean losses.
     Also: a tuple of three device tensors (used where they are), or a BprDeviceSampler — epoch number `epoch` is then drawn AND trained
     in one native call (LightGCNStepper.epoch_bpr_sampled), or drawn by sampler.draw(epoch) for the step-by-step loop."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Step times of the exact BPR step (BPR through the propagation, L2, Adam) on Epinion2 (tests/golden/epinion2_dataset.npz), d = 64,
-L = 3, weight_decay 1e-4, at T = 256 and T = 2 048: us per step of
+"""Step times of the exact BPR step (BPR through the propagation, L2, Adam) on Epinion2 (tests/golden/epinion2_dataset.npz), d = 64
+(--recdim 128 / 256: the wide kernels), L = 3, weight_decay 1e-4, at T = 256 and T = 2 048: us per step of
   * the one-call step (LightGCNStepper.step_bpr_exact(.., loss_acc=.., batch_rows_only=True)), fast and deterministic,
   * the launch-by-launch step_bpr_exact (whole-graph propagation, dense scoring gradient, all-pull backward),
   * the native epoch (LightGCNStepper.epoch_bpr: one library call for the window), per step.
@@ -8,7 +8,7 @@ The forms ALTERNATE in one process: every repeat times one window of --steps ste
 window's elapsed time on the GPU, host-bound gaps included), after a warm-up of each.  Three repeats by default; per form the
 per-repeat figures, their median and their spread (max - min) are printed.  Triples: one bpr_epoch_triples draw from a fixed seed.
 
-usage: python tools/bpr_exact_step_time.py [--out FILE] [--T 256,2048] [--steps 2000] [--repeats 3]
+usage: python tools/bpr_exact_step_time.py [--out FILE] [--T 256,2048] [--steps 2000] [--repeats 3] [--recdim 64|128|256]
        python tools/bpr_exact_step_time.py --profile 256      (300 one-call steps and nothing else: for rocprofv3 --kernel-trace --stats)
        python tools/bpr_exact_step_time.py --sweep 256,512,1024,2048 [--out FILE]   (the fast path's push and dense forms, forced)
 Every T runs in a child process of its own under a time limit; the first failure ends the run.  One JSON line per T on stdout."""
@@ -20,6 +20,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 L, N_U, N_I, WD = 3, 3186, 12407, 1e-4
+D = 64            # --recdim
 
 
 def setup(T):
@@ -34,7 +35,7 @@ def setup(T):
     dev = torch.device("cuda:0")
     train = load_epinion2()["train"]
     csr = lightgcn_norm_adj(train[:, 0], train[:, 1], N_U - 1, N_I)
-    E0 = np.concatenate(epinion2_tables(N_U, N_I, dim=64))
+    E0 = np.concatenate(epinion2_tables(N_U, N_I, dim=D))
     arrays = bpr_epoch_triples(train[:, :2], N_U, N_I, np.random.default_rng(7))
     dev_arrays = tuple(torch.from_numpy(a).to(dev) for a in arrays)
     graph = SpexGraph(*csr)
@@ -79,7 +80,7 @@ def measure(T, steps, repeats):
             e1.record()
             e1.synchronize()
             out[name].append(e0.elapsed_time(e1) * 1e3 / steps)
-    res = {"T": T, "L": L, "d": 64, "weight_decay": WD, "steps_per_window": steps, "repeats": repeats}
+    res = {"T": T, "L": L, "d": D, "weight_decay": WD, "steps_per_window": steps, "repeats": repeats}
     for name, xs in out.items():
         res[name] = [round(x, 2) for x in xs]
         res[name.replace("_us", "_median_us")] = round(sorted(xs)[len(xs) // 2], 2)
@@ -115,7 +116,10 @@ def sweep(T, steps, repeats):
             e1.record()
             e1.synchronize()
             out[form].append(round(e0.elapsed_time(e1) * 1e3 / steps, 2))
-    print(json.dumps({"T": T, "L": L, "steps_per_window": steps, "push_step_us": out["push"], "dense_step_us": out["dense"]}), flush=True)
+    res = {"T": T, "L": L, "steps_per_window": steps, "push_step_us": out["push"], "dense_step_us": out["dense"]}
+    if D != 64:
+        res["d"] = D
+    print(json.dumps(res), flush=True)
 
 
 def profile(T):
@@ -139,7 +143,10 @@ def main():
     ap.add_argument("--sweep", help="comma-separated T: the push and the dense form of the fast path, forced, alternating")
     ap.add_argument("--one-sweep", type=int, help="(internal) sweep this T in this process")
     ap.add_argument("--limit", type=int, default=240, help="seconds per T")
+    ap.add_argument("--recdim", type=int, default=64, choices=(64, 128, 256), help="embedding width")
     a = ap.parse_args()
+    global D
+    D = a.recdim
     if a.profile is not None:
         return profile(a.profile)
     if a.one is not None:
@@ -149,7 +156,7 @@ def main():
     child = "--one-sweep" if a.sweep else "--one"
     for T in (int(w) for w in (a.sweep or a.T).split(",")):
         r = subprocess.run(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), child, str(T), "--steps", str(a.steps),
-                            "--repeats", str(a.repeats)], capture_output=True, text=True)
+                            "--repeats", str(a.repeats), "--recdim", str(D)], capture_output=True, text=True)
         sys.stderr.write(r.stderr[-2000:])
         if r.returncode != 0:
             raise SystemExit(f"bpr_exact_step_time: T = {T} ended with status {r.returncode}; nothing more is started")
