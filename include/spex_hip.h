@@ -630,6 +630,43 @@ int spex_sample_bce_epoch(const int32_t *d_rowptr, const int32_t *d_items, int32
                           const int32_t *d_pos_item, int64_t n_pos, int32_t num_ng, int32_t num_item, uint64_t seed, uint32_t epoch,
                           int64_t *d_users, int64_t *d_items_out, float *d_labels, void *stream);
 
+/* ------------------------------------------------------------------------------------------------ dual-task trust-path sampler
+ * The per-batch trust-path selection of LightGCN_SPEX/code/main_auto_expert_s.py:64-71 for a whole shuffled epoch, on the device: what
+ * trainer.dual_task_epoch_paths chooses on the host with random.sample (law, not stream).  One workgroup of 256 threads per batch,
+ * one launch.  d_users int64[n]: the shuffled epoch (spex_sample_bce_epoch's d_users); batch k holds the samples j in [0, nb),
+ * nb = min(B, n - k B), at d_users[k B + j]; max_steps < 0: all ceil(n / B) batches, else the first min(max_steps, ceil(n / B)).
+ * d_path_rowptr int32[n_user_rows + 1] / d_path_idx int32[n_paths]: the path ids grouped by the path's first node, ascending within a
+ * user (the reference's user_path_indx as a CSR; trainer.dual_sampler_tables); d_paths int64[n_paths, path_len]: the padded paths
+ * (Data.inputs); d_path_l int64[n_paths]: their lengths (the row sums of Data.mask); d_path_tgt int64[n_paths]: their targets.
+ * d_seq int64[n_batches cap, path_len], d_seq_l / d_targets int64[n_batches cap], d_count int32[n_batches].
+ * The law, for batch k:
+ *   first(j):  no j' < j holds the same user (d_users[k B + j'] == d_users[k B + j])
+ *   c_j     =  d_path_rowptr[u + 1] - d_path_rowptr[u] for u = d_users[k B + j], if first(j) and 0 <= u < n_user_rows; else 0
+ *   off_j   =  the exclusive prefix sum of c in order of j;  total = the sum of all c_j
+ *   candidate q in [0, total) belongs to the j with off_j <= q < off_j + c_j and is path d_path_idx[d_path_rowptr[u_j] + q - off_j]
+ *   d_count[k] = T_k = min(total, cap)
+ *   slot t in [0, T_k) holds candidate q = t when total <= cap, otherwise q = perm_k(t)
+ *   perm_k:  spex_sample_bce_epoch's balanced Feistel network with cycle walking, on the domain [0, total):
+ *     bits = the bit length of total - 1, h = max(1, ceil(bits / 2)), mask = 2^h - 1
+ *     key     = (seed & 0xFFFFFFFF, seed >> 32)   (standard Philox4x32-10, as there)
+ *     round keys K[0 .. 3] = w0 .. w3 of counter (k, 0, epoch, 4); K[4], K[5] = w0, w1 of counter (k, 1, epoch, 4)   (stage 4: no counter
+ *       of spex_sample_bce_epoch, whose stages are 0 .. 3 — one seed may serve both samplers)
+ *     x = t;  repeat { L = x >> h, R = x & mask;  for r = 0 .. 5: (L, R) <- (R, L ^ (fmix32(R ^ K[r]) & mask));  x = (L << h) | R }
+ *     while x >= total;  perm_k(t) = x.
+ *     The first cap images of a keyed bijection of [0, total) are a sample without replacement in random order: random.sample's
+ *     law, not its stream.
+ *   slot t of batch k is written at row k cap + t: the path's row of d_paths, its d_path_l, its d_path_tgt.  Slots t >= T_k are not
+ *   written.  (An entry of d_path_idx outside [0, n_paths) — no table of trainer.dual_sampler_tables holds one — writes nothing.)
+ * A batch's output is a function of (its users, the tables, cap, seed, epoch, k) alone — not of n beyond the batch, nor of the order
+ * in which the workgroup's threads arrive: a draw bounded by max_steps = m is the first m batches of the full draw.
+ * Returns SPEX_ERR_INVALID before any launch for a NULL pointer, B outside [1, 4096] (a batch's users are held in LDS as int32), n < 0,
+ * cap < 0, path_len < 1, n_user_rows < 0, n_paths < 0 or 2^31 batches and more; n == 0 launches nothing, cap == 0 writes only the
+ * counts (zeros). */
+int spex_sample_dual_task_paths(const int64_t *d_users, int64_t n, int32_t B, int64_t max_steps, const int32_t *d_path_rowptr,
+                                int32_t n_user_rows, const int32_t *d_path_idx, int32_t n_paths, const int64_t *d_paths, int32_t path_len,
+                                const int64_t *d_path_l, const int64_t *d_path_tgt, int32_t cap, uint64_t seed, uint32_t epoch,
+                                int64_t *d_seq, int64_t *d_seq_l, int64_t *d_targets, int32_t *d_count, void *stream);
+
 /* ------------------------------------------------------------------------------------------------ learned edge values
  * the Diffnet++ social / interest diffusion — the same SpMM on user x user, user x item and item x user
  * graphs whose stored values are LEARNED (a per-edge parameter pushed through a row softmax), so the values change
@@ -1038,6 +1075,14 @@ int spex_dual_task_step_f32(spex_dual_task_step_t *step, const int64_t *users, c
 int spex_dual_task_epoch_f32(spex_dual_task_step_t *step, const int64_t *users, const int64_t *items, const float *labels, int64_t n,
                              int32_t B, int64_t max_steps, const int64_t *seq, const int64_t *seq_l, const int64_t *targets,
                              const int64_t *path_off, float keep_prob, uint32_t drop_seed, void *stream);
+/* spex_dual_task_epoch_f32 over paths staged with a fixed stride — the layout spex_sample_dual_task_paths writes (path_stride = its
+ * cap): batch k's paths are the first h_count[k] rows from row k path_stride of seq / seq_l / targets.  h_count: a HOST int32 array of
+ * one count per batch run (the step needs T on the host: the trust launch's grid and the T task_weights[1] term of the loss).
+ * Returns SPEX_ERR_INVALID before any launch for a count < 0, > path_stride or > the descriptor's path_capacity.  Edge-dropout keys,
+ * loss_acc and max_steps as in spex_dual_task_epoch_f32. */
+int spex_dual_task_epoch_strided_f32(spex_dual_task_step_t *step, const int64_t *users, const int64_t *items, const float *labels, int64_t n,
+                                     int32_t B, int64_t max_steps, const int64_t *seq, const int64_t *seq_l, const int64_t *targets,
+                                     int64_t path_stride, const int32_t *h_count, float keep_prob, uint32_t drop_seed, void *stream);
 /* Orders everything a pipelined step left on side_stream in front of whatever is queued on `stream` next (a no-op otherwise). */
 int spex_dual_task_step_join(spex_dual_task_step_t *step, void *stream);
 

@@ -104,6 +104,8 @@ SIGNATURES = {
                                                c_vp, c_vp]),
     "spex_sample_bce_epoch": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp,
                                              c_vp]),
+    "spex_sample_dual_task_paths": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, ctypes.c_uint64,
+                                                   ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "spex_graph_set_values": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
     "spex_sddmm_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "spex_edge_softmax_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp]),
@@ -145,6 +147,8 @@ SIGNATURES = {
     "spex_dual_task_step_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "spex_dual_task_epoch_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32,
                                                 ctypes.c_uint32, c_vp]),
+    "spex_dual_task_epoch_strided_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_f32,
+                                                        ctypes.c_uint32, c_vp]),
     "spex_dual_task_step_join": (ctypes.c_int, [ctypes.c_void_p, c_vp]),
     "spex_comm_unique_id": (ctypes.c_int, [c_vp]),
     "spex_comm_create": (ctypes.c_int, [c_i32, c_i32, c_vp, ctypes.POINTER(c_vp)]),

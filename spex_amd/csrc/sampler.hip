@@ -279,6 +279,163 @@ __global__ __launch_bounds__(256) void sample_bce_epoch_kernel(const int32_t *__
     }
 }
 
+// ---- dual-task trust paths (include/spex_hip.h: spex_sample_dual_task_paths states the law word by word; tests restate it from there)
+// One 256-thread workgroup per batch.  LDS at capacity CAP (the largest batch the instance serves): the batch's users as int32
+// (-1: outside the tables), an open-addressing table of 2 CAP sample positions, the per-sample candidate counts (then their
+// exclusive prefix sums), 256 cells for the block scan (then the chosen paths of 256 slots) and the total.
+template <int CAP>
+struct DualPathsLds {
+    int32_t user[CAP];
+    int32_t table[2 * CAP];
+    uint32_t off[CAP];
+    uint32_t part[256];
+    uint32_t total;
+};
+
+// first(j) by an open-addressing table keyed by the user of the position a cell holds: a cell, once taken, only ever holds positions
+// of ONE user (atomicMin among them), so the minimum position per user — all the law reads — does not depend on arrival order.
+// Only users with at least one path are entered; 2 CAP cells for at most CAP keys: a probe always meets the key or an empty cell.
+template <int CAP>
+__global__ __launch_bounds__(256) void sample_dual_paths_kernel(const int64_t *__restrict__ users, int64_t n, int B,
+                                                                const int32_t *__restrict__ path_rowptr, int n_user_rows,
+                                                                const int32_t *__restrict__ path_idx, int n_paths,
+                                                                const int64_t *__restrict__ paths, int path_len,
+                                                                const int64_t *__restrict__ path_l, const int64_t *__restrict__ path_tgt,
+                                                                int cap, uint32_t seed_lo, uint32_t seed_hi, uint32_t epoch,
+                                                                int64_t *__restrict__ seq, int64_t *__restrict__ seq_l,
+                                                                int64_t *__restrict__ targets, int32_t *__restrict__ count)
+{
+    __shared__ DualPathsLds<CAP> s;
+    constexpr uint32_t kCells = 2u * CAP;
+    const int tid = threadIdx.x;
+    const uint32_t k = blockIdx.x;
+    const int64_t b0 = (int64_t)k * B;
+    if (cap == 0) {                                       // (uniform) nothing to choose: the count alone
+        if (tid == 0) count[k] = 0;
+        return;
+    }
+    const int nb = (int)(n - b0 < (int64_t)B ? n - b0 : (int64_t)B);          // 1 <= nb <= B <= CAP
+    for (uint32_t c = tid; c < kCells; c += 256) s.table[c] = -1;
+    for (int j = tid; j < nb; j += 256) {
+        const int64_t u = users[b0 + j];
+        int cnt = 0;
+        if (u >= 0 && u < n_user_rows) {
+            cnt = path_rowptr[u + 1] - path_rowptr[u];
+            if (cnt < 0) cnt = 0;
+        }
+        s.user[j] = cnt > 0 ? (int)u : -1;                 // a user without paths takes no part
+        s.off[j] = (uint32_t)cnt;
+    }
+    __syncthreads();
+    for (int j = tid; j < nb; j += 256) {
+        const int u = s.user[j];
+        if (u < 0) continue;
+        uint32_t c = fmix32((uint32_t)u) & (kCells - 1u);
+        for (;;) {
+            const int prev = atomicCAS(&s.table[c], -1, j);
+            if (prev == -1) break;                         // the cell is this user's now
+            if (s.user[prev] == u) {
+                atomicMin(&s.table[c], j);
+                break;
+            }
+            c = (c + 1u) & (kCells - 1u);
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < nb; j += 256) {
+        const int u = s.user[j];
+        if (u < 0) continue;
+        uint32_t c = fmix32((uint32_t)u) & (kCells - 1u);
+        int at = s.table[c];
+        while (at != -1 && s.user[at] != u) {
+            c = (c + 1u) & (kCells - 1u);
+            at = s.table[c];
+        }
+        if (at != j) s.off[j] = 0u;                        // an earlier sample holds the same user
+    }
+    __syncthreads();
+    // exclusive prefix sums of the counts in order of j: a thread's run of `per` consecutive entries, the 256 run sums scanned in LDS
+    const int per = (nb + 255) >> 8;
+    const int j0 = tid * per, j1 = j0 + per < nb ? j0 + per : nb;
+    uint32_t run = 0u;
+    for (int j = j0; j < j1; ++j) run += s.off[j];
+    s.part[tid] = run;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const uint32_t add = tid >= d ? s.part[tid - d] : 0u;
+        __syncthreads();
+        s.part[tid] += add;
+        __syncthreads();
+    }
+    uint32_t before = s.part[tid] - run;
+    if (tid == 255) s.total = s.part[255];
+    for (int j = j0; j < j1; ++j) {
+        const uint32_t c = s.off[j];
+        s.off[j] = before;
+        before += c;
+    }
+    __syncthreads();
+    const uint32_t total = s.total;
+    const uint32_t T = total < (uint32_t)cap ? total : (uint32_t)cap;
+    if (tid == 0) count[k] = (int32_t)T;
+    if (T == 0u) return;
+    // total > cap: slot t holds candidate perm_k(t) — the BCE sampler's Feistel network on [0, total), keyed by the batch
+    const bool cut = total > (uint32_t)cap;
+    uint32_t h = 1u, key[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    if (cut) {
+        const uint32_t bits = 32u - (uint32_t)__clz((int)(total - 1u));        // (total >= 2 here)
+        h = bits <= 2u ? 1u : (bits + 1u) / 2u;
+        const Philox4 a = philox4x32_10(k, 0u, epoch, 4u, seed_lo, seed_hi), b = philox4x32_10(k, 1u, epoch, 4u, seed_lo, seed_hi);
+        key[0] = a.w[0]; key[1] = a.w[1]; key[2] = a.w[2]; key[3] = a.w[3]; key[4] = b.w[0]; key[5] = b.w[1];
+    }
+    const uint32_t mask = (1u << h) - 1u;
+    const int64_t row0 = (int64_t)k * cap;
+    for (uint32_t base = 0u; base < T; base += 256u) {         // (uniform bounds: the barriers inside are met by every thread)
+        const uint32_t t = base + (uint32_t)tid;
+        int p = -1;
+        if (t < T) {
+            uint32_t q = t;
+            if (cut) {
+                do {
+                    uint32_t l = q >> h, r = q & mask;
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) {
+                        const uint32_t f = l ^ (fmix32(r ^ key[i]) & mask);
+                        l = r;
+                        r = f;
+                    }
+                    q = (l << h) | r;
+                } while (q >= total);
+            }
+            int lo = 0, hi = nb;                             // the last j with off[j] <= q: first j with off[j] > q, minus one
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s.off[mid] <= q) lo = mid + 1;
+                else hi = mid;
+            }
+            const int j = lo - 1;                            // off[0] = 0 <= q: j >= 0, and its count is positive
+            const int64_t at = (int64_t)path_rowptr[s.user[j]] + (int64_t)(q - s.off[j]);
+            if (at >= 0 && at < n_paths) {
+                p = path_idx[at];
+                if (p < 0 || p >= n_paths) p = -1;
+            }
+            if (p >= 0) {
+                seq_l[row0 + t] = path_l[p];
+                targets[row0 + t] = path_tgt[p];
+            }
+        }
+        s.part[tid] = (uint32_t)p;
+        __syncthreads();
+        const uint32_t slots = T - base < 256u ? T - base : 256u;
+        for (uint32_t e = tid; e < slots * (uint32_t)path_len; e += 256u) {
+            const uint32_t slot = e / (uint32_t)path_len, col = e - slot * (uint32_t)path_len;
+            const int pp = (int)s.part[slot];
+            if (pp >= 0) seq[(row0 + base + slot) * path_len + col] = paths[(int64_t)pp * path_len + col];
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 // Standard Philox4x32-10 on the host: the entry point draws the shuffle's round keys with it.
@@ -319,6 +476,35 @@ extern "C" int spex_sample_bce_epoch(const int32_t *d_rowptr, const int32_t *d_i
     hipLaunchKernelGGL(sample_bce_epoch_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_rowptr, d_items, n_user_rows,
                        d_pos_user, d_pos_item, (uint32_t)n_pos, (uint32_t)num_ng, num_item, n, h, keys, k0, k1, epoch, d_users, d_items_out,
                        d_labels);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
+
+extern "C" int spex_sample_dual_task_paths(const int64_t *d_users, int64_t n, int32_t B, int64_t max_steps, const int32_t *d_path_rowptr,
+                                           int32_t n_user_rows, const int32_t *d_path_idx, int32_t n_paths, const int64_t *d_paths,
+                                           int32_t path_len, const int64_t *d_path_l, const int64_t *d_path_tgt, int32_t cap, uint64_t seed,
+                                           uint32_t epoch, int64_t *d_seq, int64_t *d_seq_l, int64_t *d_targets, int32_t *d_count, void *stream)
+{
+    SPEX_CHECK_ARG(d_users && d_path_rowptr && d_path_idx && d_paths && d_path_l && d_path_tgt && d_seq && d_seq_l && d_targets && d_count,
+                   "spex_sample_dual_task_paths: NULL pointer");
+    SPEX_CHECK_ARG(B >= 1 && B <= 4096, "spex_sample_dual_task_paths: B=%d (needs 1 <= B <= 4096: a batch's users are held in LDS)", B);
+    SPEX_CHECK_ARG(n >= 0 && cap >= 0 && path_len >= 1 && n_user_rows >= 0 && n_paths >= 0,
+                   "spex_sample_dual_task_paths: n=%lld cap=%d path_len=%d n_user_rows=%d n_paths=%d (needs n >= 0, cap >= 0, path_len >= 1)",
+                   (long long)n, cap, path_len, n_user_rows, n_paths);
+    int64_t n_batches = (n + B - 1) / B;
+    if (max_steps >= 0 && max_steps < n_batches) n_batches = max_steps;
+    SPEX_CHECK_ARG(n_batches < ((int64_t)1 << 31), "spex_sample_dual_task_paths: %lld batches: the batch index keys a 32-bit counter word",
+                   (long long)n_batches);
+    if (n_batches == 0) return SPEX_OK;
+    const dim3 grid((unsigned)n_batches), block(256);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#define SPEX_DUAL_PATHS_LAUNCH(CAP)                                                                                                          \
+    hipLaunchKernelGGL(sample_dual_paths_kernel<CAP>, grid, block, 0, (hipStream_t)stream, d_users, n, B, d_path_rowptr, n_user_rows, d_path_idx, \
+                       n_paths, d_paths, path_len, d_path_l, d_path_tgt, cap, k0, k1, epoch, d_seq, d_seq_l, d_targets, d_count)
+    if (B <= 256) SPEX_DUAL_PATHS_LAUNCH(256);
+    else if (B <= 1024) SPEX_DUAL_PATHS_LAUNCH(1024);
+    else SPEX_DUAL_PATHS_LAUNCH(4096);
+#undef SPEX_DUAL_PATHS_LAUNCH
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

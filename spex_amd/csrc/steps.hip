@@ -854,3 +854,45 @@ extern "C" int spex_dual_task_epoch_f32(spex_dual_task_step_t *s, const int64_t 
     }
     return rc;
 }
+
+// spex_dual_task_epoch_f32 over paths staged with a fixed stride: batch k's paths are the first h_count[k] rows from row
+// k * path_stride of seq / seq_l / targets — the layout spex_sample_dual_task_paths writes (stride = its cap) — and h_count is a HOST
+// array (the step needs T there: the trust launch's grid and the T * task_weights[1] term).  Every count is checked before the first
+// launch.  Edge-dropout keys, loss_acc and max_steps as in spex_dual_task_epoch_f32.
+extern "C" int spex_dual_task_epoch_strided_f32(spex_dual_task_step_t *s, const int64_t *users, const int64_t *items, const float *labels,
+                                                int64_t n, int32_t B, int64_t max_steps, const int64_t *seq, const int64_t *seq_l,
+                                                const int64_t *targets, int64_t path_stride, const int32_t *h_count, float keep_prob,
+                                                uint32_t drop_seed, void *stream)
+{
+    SPEX_CHECK_ARG(s && s->graph && s->graph_t && users && items && labels && h_count && n >= 0 && B >= 1 && path_stride >= 0,
+                   "spex_dual_task_epoch_strided_f32: NULL pointer, n < 0, B < 1 or path_stride < 0");
+    SPEX_CHECK_ARG(keep_prob > 0.0f && keep_prob <= 1.0f, "spex_dual_task_epoch_strided_f32: keep_prob %g", keep_prob);
+    int64_t n_batches = (n + B - 1) / B;
+    if (max_steps >= 0 && max_steps < n_batches) n_batches = max_steps;
+    for (int64_t k = 0; k < n_batches; ++k) {
+        const int64_t T = h_count[k];
+        SPEX_CHECK_ARG(T >= 0 && T <= path_stride && T <= s->path_capacity && (T == 0 || (seq && seq_l && targets)),
+                       "spex_dual_task_epoch_strided_f32: batch %lld has %lld paths (stride %lld, capacity %d; path arrays must be given)",
+                       (long long)k, (long long)T, (long long)path_stride, s->path_capacity);
+    }
+    spex_graph *g = const_cast<spex_graph *>(s->graph), *gt = const_cast<spex_graph *>(s->graph_t);
+    const bool drop = keep_prob < 1.0f;
+    int rc = SPEX_OK;
+    for (int64_t k = 0; k < n_batches && rc == SPEX_OK; ++k) {
+        const int64_t b0 = k * B, p0 = k * path_stride;
+        const int32_t nb = (int32_t)(n - b0 < B ? n - b0 : B), T = h_count[k];
+        if (drop) {
+            const uint64_t seed = ((uint64_t)drop_seed << 32) | (uint64_t)(uint32_t)(k + 1);
+            rc = spex_graph_set_edge_mask(g, 2, nullptr, keep_prob, seed);
+            if (rc == SPEX_OK && gt != g) rc = spex_graph_set_edge_mask(gt, 2, nullptr, keep_prob, seed);
+            if (rc != SPEX_OK) break;
+        }
+        rc = spex_dual_task_step_f32(s, users + b0, items + b0, labels + b0, nb, T ? seq + p0 * s->path_len : nullptr, T ? seq_l + p0 : nullptr,
+                                     T ? targets + p0 : nullptr, T, stream);
+    }
+    if (drop) {
+        (void)spex_graph_set_edge_mask(g, 0, nullptr, 1.0f, 0);
+        if (gt != g) (void)spex_graph_set_edge_mask(gt, 0, nullptr, 1.0f, 0);
+    }
+    return rc;
+}

@@ -702,6 +702,52 @@ def sample_bce_epoch(rowptr, items, pos_user, pos_item, num_ng, num_item, seed, 
     return tuple(t[:n] for t in out)
 
 
+def sample_dual_task_paths(users, batch_size, path_rowptr, path_idx, paths, path_l, path_tgt, cap, seed, epoch, max_steps=None, out=None):
+    """Every batch's trust paths of a shuffled dual-task epoch, chosen on the GPU by one launch (spex_sample_dual_task_paths; the law is
+    written down in include/spex_hip.h): all paths that start at one of the batch's users, cut to `cap` by a keyed sample without
+    replacement.  users: device int64 [n] (the epoch, e.g. sample_bce_epoch's); path_rowptr / path_idx: device int32 CSR of the path ids
+    by first node (trainer.dual_sampler_tables); paths: device int64 [n_paths, path_len]; path_l, path_tgt: device int64 [n_paths].
+    out: (seq int64 [>= n_batches cap, path_len], seq_l, targets int64 [>= n_batches cap], count int32 [>= n_batches]) device tensors to
+    write into; default: fresh ones (rows past a batch's count are left as they were: uninitialised in fresh tensors).  Returns (seq,
+    seq_l, targets, count) cut to n_batches cap rows / n_batches counts; batch k's paths are rows [k cap, k cap + count[k])."""
+    for t, name in ((path_rowptr, "path_rowptr"), (path_idx, "path_idx")):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise ValueError(f"{name}: need a contiguous torch.int32 CUDA tensor")
+    for t, name in ((users, "users"), (paths, "paths"), (path_l, "path_l"), (path_tgt, "path_tgt")):
+        if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
+            raise ValueError(f"{name}: need a contiguous torch.int64 CUDA tensor")
+    B, cap, n = int(batch_size), int(cap), users.numel()
+    n_paths = path_idx.numel()
+    if paths.dim() != 2 or paths.shape[0] != n_paths or paths.shape[1] < 1 or path_l.numel() != n_paths or path_tgt.numel() != n_paths \
+            or path_rowptr.numel() < 1:
+        raise ValueError("sample_dual_task_paths: paths [n_paths, path_len], path_l, path_tgt and path_idx need one n_paths; path_rowptr one entry at least")
+    if not 1 <= B <= 4096 or cap < 0:
+        raise ValueError(f"sample_dual_task_paths: batch_size {B} (1 .. 4096) / cap {cap} (>= 0)")
+    n_batches = -(-n // B)
+    if max_steps is not None:
+        n_batches = min(n_batches, max(0, int(max_steps)))
+    path_len, dev = paths.shape[1], users.device
+    if out is None:
+        out = (torch.empty(n_batches * cap, path_len, dtype=torch.int64, device=dev), torch.empty(n_batches * cap, dtype=torch.int64, device=dev),
+               torch.empty(n_batches * cap, dtype=torch.int64, device=dev), torch.empty(n_batches, dtype=torch.int32, device=dev))
+    seq, seq_l, targets, count = out
+    for t, dt, rows in ((seq, torch.int64, n_batches * cap), (seq_l, torch.int64, n_batches * cap), (targets, torch.int64, n_batches * cap),
+                        (count, torch.int32, n_batches)):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.shape[0] >= rows):
+            raise ValueError("sample_dual_task_paths: out needs contiguous (int64 [n_batches cap, path_len], int64, int64, int32 [n_batches]) CUDA tensors")
+    if seq.dim() != 2 or seq.shape[1] != path_len:
+        raise ValueError(f"sample_dual_task_paths: out[0] must be [*, {path_len}]")
+    res = (seq[:n_batches * cap], seq_l[:n_batches * cap], targets[:n_batches * cap], count[:n_batches])
+    if n_batches == 0:               # (an empty device tensor has no storage to point at)
+        return res
+    p = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else count.data_ptr())      # (cap == 0 / no paths: never dereferenced)
+    _launch(dev, "spex_sample_dual_task_paths", p(users), n, B, n_batches, p(path_rowptr), path_rowptr.numel() - 1, p(path_idx), n_paths,
+            p(paths), path_len, p(path_l), p(path_tgt), cap, int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, p(seq), p(seq_l),
+            p(targets), p(count))
+    _bump(*out)
+    return res
+
+
 # ------------------------------------------------------------------------------------------------ autograd glue
 def _flat_tables(user_w, item_w, strict=False):
     """The two embedding tables as one [N, d] buffer.  The drop-in model allocates them back-to-back so this is a

@@ -1408,6 +1408,47 @@ class DualTaskStepper(_DualTaskArena):
         _bump(self.arena, self.m, self.v, self.loss_acc)
         self.model._cache = None
 
+    def epoch_strided(self, users, items, labels, batch_size, seq, seq_l, targets, path_stride, counts, max_steps=None, keep_prob=1.0,
+                      drop_seed=0):
+        """`epoch` over paths staged with a fixed stride (spex_dual_task_epoch_strided_f32) — what ops.sample_dual_task_paths writes:
+        batch k's paths are the first counts[k] rows from row k * path_stride of seq / seq_l / targets.  counts: a HOST int32 array (or
+        CPU tensor) of one count per batch run.  A count outside [0, min(path_stride, path_capacity)] is refused before any launch."""
+        if not _batch_ok(users, items, labels, min_len=0):
+            raise ValueError("DualTaskStepper.epoch_strided: users / items (int64) and labels (fp32) must be contiguous device tensors of one length")
+        counts = counts.numpy() if torch.is_tensor(counts) else np.asarray(counts)
+        if counts.dtype != np.int32 or not counts.flags.c_contiguous:
+            raise ValueError("DualTaskStepper.epoch_strided: counts must be a contiguous host int32 array")
+        n_batches = (users.numel() + int(batch_size) - 1) // int(batch_size)
+        if max_steps is not None:
+            n_batches = min(n_batches, max(0, int(max_steps)))
+        if len(counts) < n_batches:
+            raise ValueError("DualTaskStepper.epoch_strided: counts needs one entry per batch")
+        path_stride = int(path_stride)
+        any_paths = n_batches > 0 and bool(counts[:n_batches].any())
+        if any_paths:
+            for t in (seq, seq_l, targets):
+                if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
+                    raise ValueError("DualTaskStepper.epoch_strided: seq / seq_l / targets must be contiguous device int64 tensors")
+            rows = n_batches * path_stride
+            if seq.dim() != 2 or seq.shape[1] != self.path_len or seq.shape[0] < rows or seq_l.numel() < rows or targets.numel() < rows:
+                raise ValueError("DualTaskStepper.epoch_strided: the staged paths do not cover n_batches * path_stride rows of the stepper's width")
+        if keep_prob < 1.0 and (self._graph_t is self.model.Graph or self.L < 2):
+            raise ValueError("DualTaskStepper.epoch_strided: edge dropout needs the transposed handle (a model built with --dropout 1) and L >= 2")
+        dsc = self._prepare_desc(max(1, min(int(batch_size), users.numel())))
+        if any_paths and self._side is not None:
+            for t in (seq, seq_l, targets):
+                t.record_stream(self._side)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        try:
+            _launch(self.dev, "spex_dual_task_epoch_strided_f32", ctypes.byref(dsc), vp(users), vp(items), vp(labels), users.numel(),
+                    int(batch_size), n_batches, vp(seq) if any_paths else None, vp(seq_l) if any_paths else None,
+                    vp(targets) if any_paths else None, path_stride, counts.ctypes.data_as(ctypes.c_void_p), float(keep_prob),
+                    int(drop_seed) & 0xFFFFFFFF)
+        finally:
+            self.t = dsc.t
+        _bump(self.arena, self.m, self.v, self.loss_acc)
+        self.model._cache = None
+
     def set_edge_dropout(self, mask=None):
         """The next steps' edge-dropout mask on both handles (an edge_dropout_mask(...) tuple; None: off) — model_expert_s.py:104-109."""
         g, gt = self.model.Graph, self._graph_t
@@ -1457,11 +1498,245 @@ def epoch_arrays_dual(train_data, trust_data, by_user, cap, batch_size=256, resa
             np.asarray(targets).astype(np.int64), chosen)
 
 
-def train_epochs_dual(stepper, train_data, trust_data, by_user, cap, n_epochs, batch_size=256, edge_dropout=None, after_epoch=None):
+def dual_sampler_tables(paths, n_user_rows=None):
+    """The CSR the device path sampler reads (spex_sample_dual_task_paths): the ids of `paths` (a list of node lists, or a padded
+    [n_paths, len] array: the first column is read) grouped by the path's first node, ascending within a user — the reference's
+    user_path_indx, main_auto_expert_s.py:45-51.  n_user_rows: the number of rows (default: the largest first node + 1).  Returns
+    (rowptr int32 [n_user_rows + 1], idx int32 [n_paths])."""
+    if isinstance(paths, np.ndarray):
+        first = np.asarray(paths, dtype=np.int64).reshape(len(paths), -1)[:, 0] if len(paths) else np.zeros(0, np.int64)
+    else:
+        first = np.fromiter((p[0] for p in paths), dtype=np.int64, count=len(paths))
+    if len(first) >= 2 ** 31:
+        raise ValueError("dual_sampler_tables: 2^31 or more paths: the tables are int32")
+    if n_user_rows is None:
+        n_user_rows = int(first.max()) + 1 if len(first) else 0
+    if len(first) and (first.min() < 0 or first.max() >= n_user_rows):
+        raise ValueError("dual_sampler_tables: a path's first node is out of range")
+    rowptr = np.zeros(n_user_rows + 1, np.int32)
+    np.cumsum(np.bincount(first, minlength=n_user_rows), out=rowptr[1:])
+    return rowptr, np.argsort(first, kind="stable").astype(np.int32)
+
+
+class _DualEpochSet:
+    """One set of epoch buffers of a DualDeviceSampler: the epoch's samples, its staged paths, the counts on the device and in pinned
+    host memory, the event behind the draw and the event behind the epoch that read the set last."""
+
+    def __init__(self, n, n_batches, cap, path_len, device):
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+        self.users, self.items, self.labels = e(n, torch.int64), e(n, torch.int64), e(n, torch.float32)
+        self.seq, self.seq_l, self.targets = e((n_batches * cap, path_len), torch.int64), e(n_batches * cap, torch.int64), e(n_batches * cap, torch.int64)
+        self.count = e(n_batches, torch.int32)
+        self.count_host = torch.empty(n_batches, dtype=torch.int32, pin_memory=True)
+        self.drawn, self.read = torch.cuda.Event(), None
+        self.key = None                    # (epoch, batches drawn) the set holds
+
+    def tensors(self):
+        return self.users, self.items, self.labels, self.seq, self.seq_l, self.targets, self.count
+
+
+class DualDeviceSampler:
+    """Dual-task epochs (main_auto_expert_s.py:56-71) drawn on the device: a BceDeviceSampler (negatives, labels, shuffle: one launch)
+    and the per-batch trust-path selection on its output (ops.sample_dual_task_paths: one launch) — what epoch_arrays_dual prepares on
+    the host with three global generators.  The law is the reference's, the stream is not (the exact-replay path stays
+    epoch_arrays_dual).  Holds the BCE tables plus the path tables of dual_sampler_tables, trust_data's padded paths, their lengths and
+    targets in HBM.  trust_data: a utility2.utils.Data (inputs, mask, targets); cap: the most paths a step takes; batch_size: the
+    epoch's batch size (the selection is per batch; 1 .. 4 096).  draw(epoch) returns (users, items, labels, seq, seq_l, targets,
+    count): batch k's paths are rows [k cap, k cap + count[k]) — a function of (seed, epoch) alone.  Pass the sampler itself to
+    train_epoch_dual / train_epochs_dual: no host thread, no global generator.  The sampler owns one stream, two sets of epoch
+    buffers and a pinned host copy of the counts per set: it draws on its stream, copies the counts asynchronously and records an
+    event — all the host ever waits on — so the next epoch is drawn beside the current one's steps.
+    Not callable and without ng_sample on purpose: nothing can mistake it for host data."""
+
+    def __init__(self, train_pairs, n_users, n_items, trust_data, cap, batch_size, num_ng=5, seed=0, device="cuda"):
+        self.bce = BceDeviceSampler(train_pairs, n_users, n_items, num_ng=num_ng, seed=seed, device=device)
+        self.cap, self.batch_size = int(cap), int(batch_size)
+        if self.cap < 0 or not 1 <= self.batch_size <= 4096:
+            raise ValueError(f"DualDeviceSampler: cap {cap} must not be negative and batch_size {batch_size} must lie in 1 .. 4096")
+        inputs = np.ascontiguousarray(trust_data.inputs, dtype=np.int64)
+        if inputs.ndim != 2 or inputs.shape[1] < 1:
+            raise ValueError("DualDeviceSampler: trust_data.inputs must be a [n_paths, path_len] array")
+        rowptr, idx = dual_sampler_tables(inputs, n_users)
+        self.device, self.seed, self.n, self.n_paths, self.path_len = self.bce.device, int(seed), self.bce.n, len(inputs), inputs.shape[1]
+        self.n_batches = -(-self.n // self.batch_size)
+        if self.n_batches * max(self.cap, 1) >= 2 ** 31:
+            raise ValueError("DualDeviceSampler: n_batches x cap staged path rows: fewer than 2^31 are supported")
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
+        self.path_rowptr, self.path_idx = up(rowptr, np.int32), up(idx, np.int32)
+        self.paths, self.path_l = up(inputs, np.int64), up(np.asarray(trust_data.mask).reshape(inputs.shape).sum(1), np.int64)
+        self.path_tgt = up(np.asarray(trust_data.targets).reshape(-1), np.int64)
+        if self.path_tgt.numel() != self.n_paths:
+            raise ValueError("DualDeviceSampler: trust_data needs one target per path")
+        self.device = self.path_rowptr.device          # (with its index: "cuda" is the current device's)
+        self._stream, self._sets, self._turn = None, None, 0       # created with the first draw (a sampler on "cpu" holds its tables only)
+
+    @classmethod
+    def from_train_data(cls, train_data, trust_data, cap, batch_size, n_users=None, seed=0, device="cuda"):
+        """The sampler of a LightTrainData and a trust Data: the positives (`_ps`, in its order), `num_item`, `num_ng` and the paths.
+        n_users: the number of user rows (default: the largest user index or first node + 1)."""
+        pairs = np.asarray(train_data._ps, dtype=np.int64).reshape(-1, 2)
+        if n_users is None:
+            firsts = np.asarray(trust_data.inputs)[:, 0] if len(trust_data.inputs) else np.zeros(0, np.int64)
+            n_users = max(int(pairs[:, 0].max()) + 1 if len(pairs) else 0, int(firsts.max()) + 1 if len(firsts) else 0)
+        return cls(pairs, n_users, train_data.num_item, trust_data, cap, batch_size, num_ng=train_data.num_ng, seed=seed, device=device)
+
+    def _ensure_stream(self):
+        if self._stream is None:
+            if self.device.type != "cuda":
+                raise ValueError(f"DualDeviceSampler: draws run on the GPU only (the tables live on {self.device})")
+            with torch.cuda.device(self.device):
+                self._stream = torch.cuda.Stream(device=self.device)
+                self._stream.wait_stream(torch.cuda.current_stream(self.device))       # behind the tables' uploads
+        return self._stream
+
+    def _draw_into(self, out, epoch, n_batches):
+        """Both launches on the sampler's stream, into `out` = (users, items, labels, seq, seq_l, targets, count)."""
+        b = self.bce
+        with torch.cuda.stream(self._stream):
+            ops.sample_bce_epoch(b.rowptr, b.items, b.pos_user, b.pos_item, b.num_ng, b.n_items, self.seed, epoch, out=out[:3])
+            ops.sample_dual_task_paths(out[0][:self.n], self.batch_size, self.path_rowptr, self.path_idx, self.paths, self.path_l, self.path_tgt,
+                                       self.cap, self.seed, epoch, max_steps=n_batches, out=out[3:])
+
+    def _batches(self, max_steps):
+        return self.n_batches if max_steps is None else min(self.n_batches, max(0, int(max_steps)))
+
+    def draw(self, epoch, max_steps=None):
+        """Epoch `epoch` as fresh device tensors (users int64 [n], items int64 [n], labels fp32 [n], seq int64 [n_batches cap, path_len],
+        seq_l int64, targets int64 [n_batches cap], count int32 [n_batches]); max_steps: the paths of the first max_steps batches only
+        (a prefix of the full draw).  Drawn on the sampler's stream; the current stream is ordered behind the draw."""
+        stream, nb = self._ensure_stream(), self._batches(max_steps)
+        cur = torch.cuda.current_stream(self.device)
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        out = (e(self.n, torch.int64), e(self.n, torch.int64), e(self.n, torch.float32), e((nb * self.cap, self.path_len), torch.int64),
+               e(nb * self.cap, torch.int64), e(nb * self.cap, torch.int64), e(nb, torch.int32))
+        stream.wait_stream(cur)
+        self._draw_into(out, epoch, nb)
+        for t in out:
+            t.record_stream(stream)
+        cur.wait_stream(stream)
+        return out
+
+    def issue(self, epoch, max_steps=None):
+        """Queue epoch `epoch`'s draw on the sampler's stream into the buffer set whose turn it is — behind the event of the epoch that
+        read the set last —, then the counts' copy to pinned memory and the set's event.  Returns the set; an epoch already issued
+        with the same bound is not drawn again."""
+        stream, nb = self._ensure_stream(), self._batches(max_steps)
+        if self._sets is None:
+            with torch.cuda.device(self.device):
+                self._sets = [_DualEpochSet(self.n, self.n_batches, self.cap, self.path_len, self.device) for _ in range(2)]
+            stream.wait_stream(torch.cuda.current_stream(self.device))
+        key = (int(epoch) & 0xFFFFFFFF, nb)
+        for st in self._sets:
+            if st.key == key:
+                return st
+        st = self._sets[self._turn]
+        self._turn ^= 1
+        if st.read is not None:
+            stream.wait_event(st.read)
+        self._draw_into(st.tensors(), epoch, nb)
+        with torch.cuda.stream(stream):
+            st.count_host[:nb].copy_(st.count[:nb], non_blocking=True)
+            st.drawn.record(stream)
+        st.key = key
+        return st
+
+
+def _train_epoch_dual_sampled(stepper, sampler, epoch, batch_size, pause_gc, max_steps, cum_every, cum_out, n_paths_out, edge_dropout,
+                              prefetch=None):
+    """train_epoch_dual over a DualDeviceSampler (see there).  prefetch: the epoch to draw, on the sampler's stream into its other
+    buffer set, once this one is queued."""
+    dev = stepper.dev
+    if sampler.device != dev:
+        raise ValueError(f"train_epoch_dual: the sampler's tables live on {sampler.device}, the stepper on {dev}")
+    if batch_size is not None and int(batch_size) != sampler.batch_size:
+        raise ValueError(f"train_epoch_dual: batch_size {batch_size} is not the sampler's ({sampler.batch_size}: its paths are chosen per batch)")
+    if sampler.cap > stepper.path_capacity or sampler.path_len != stepper.path_len:
+        raise ValueError(f"train_epoch_dual: the sampler stages {sampler.cap} paths of width {sampler.path_len} per batch, the stepper takes "
+                         f"{stepper.path_capacity} of width {stepper.path_len}")
+    B, cap, n = sampler.batch_size, sampler.cap, sampler.n
+    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
+    st = sampler.issue(epoch, max_steps)
+    cur = torch.cuda.current_stream(dev)
+    cur.wait_event(st.drawn)                       # the training stream behind the draw ...
+    st.drawn.synchronize()                         # ... and the host behind the counts' copy: the one wait, never on the training stream
+    n_run = st.key[1]
+    counts = st.count_host.numpy()[:n_run].copy()      # (the set may be drawn into again before the caller reads them)
+    users, items, labels, seq, seq_l, tgt, _ = st.tensors()
+    starts = _batch_starts(n, B, max_steps)
+    pipelined_env = stepper._side is not None and os.environ.get("SPEX_DUAL_PIPELINED", "0") == "1"
+    stepper.join()
+    stepper.loss_acc.zero_()
+    native = not cum_every and stream in (None, "philox") and n > 0 and not pipelined_env and not stepper.pipelined
+    with _gc_paused(pause_gc):
+        if native:
+            try:
+                stepper.epoch_strided(users, items, labels, B, seq, seq_l, tgt, cap, counts, max_steps=max_steps, keep_prob=keep_prob,
+                                      drop_seed=seed)
+            finally:
+                stepper.join()
+        else:                                      # (the loop of train_epoch_dual, over slices at k * cap)
+            was_pipelined = stepper.pipelined
+            stepper.pipelined = was_pipelined or pipelined_env
+            try:
+                for k, s in enumerate(starts):
+                    e, p0, T = min(s + B, n), k * cap, int(counts[k])
+                    if stream is not None:
+                        stepper.set_edge_dropout(edge_dropout_mask(stepper.model.Graph, keep_prob, stream, seed, k + 1))
+                    stepper.step(users[s:e], items[s:e], labels[s:e], seq[p0:p0 + T] if T else None, seq_l[p0:p0 + T], tgt[p0:p0 + T])
+                    if cum_every and cum_out is not None and (k + 1) % cum_every == 0:
+                        stepper.join()
+                        cum_out.append(stepper.loss_acc.clone())
+            finally:
+                stepper.join()
+                if stream is not None:
+                    stepper.set_edge_dropout(None)
+                stepper.pipelined = was_pipelined
+    total = stepper.loss_acc.clone()
+    if st.read is None:
+        st.read = torch.cuda.Event()
+    st.read.record(cur)                            # the set may be drawn into again behind this epoch (both branches are joined)
+    if prefetch is not None:
+        sampler.issue(prefetch, max_steps)
+    if n_paths_out is not None:
+        n_paths_out.extend(int(c) for c in counts)
+    return total
+
+
+def _train_epochs_dual_sampled(stepper, sampler, n_epochs, batch_size, edge_dropout, after_epoch, first_epoch, max_steps):
+    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
+    totals = []
+    for e in range(first_epoch, first_epoch + n_epochs):
+        drop = None if stream is None else (keep_prob, stream, bpr_epoch_drop_seed(seed, e) if stream == "philox" else seed)
+        total = _train_epoch_dual_sampled(stepper, sampler, e, batch_size, True, max_steps, None, None, None, drop,
+                                          prefetch=e + 1 if e + 1 < first_epoch + n_epochs else None)
+        totals.append(total)
+        if after_epoch is not None:
+            after_epoch(e - first_epoch, total)
+    return [t.cpu().numpy() for t in totals]
+
+
+def train_epochs_dual(stepper, train_data, trust_data=None, by_user=None, cap=None, n_epochs=None, batch_size=None, edge_dropout=None,
+                      after_epoch=None, first_epoch=0, max_steps=None):
     """n_epochs x train_epoch_dual with the NEXT epoch's negatives, shuffle and path selection prepared on a second host thread while
     the current epoch runs as one native call (see train_epochs: the three generators are drawn by that thread alone meanwhile, in the
     order a sequential loop draws them — the same run).  Not under the "reference" edge-dropout stream, whose per-step masks are
-    drawn from torch's generator on the host: that loop runs sequentially.  Returns the per-epoch (loss1, loss2) sums."""
+    drawn from torch's generator on the host: that loop runs sequentially.  Returns the per-epoch (loss1, loss2) sums.
+    train_data a DualDeviceSampler — train_epochs_dual(stepper, sampler, n_epochs, ...): trust_data, by_user and cap are not given (the
+    sampler holds them), no second thread and no global generator.  Epochs first_epoch .. first_epoch + n_epochs - 1 are drawn on the
+    device, epoch e + 1 on the sampler's stream into its other buffer set as soon as epoch e is queued; one native call per epoch
+    (the counts of every batch's paths must reach the host once per epoch).  Under the "philox" edge dropout epoch e runs with the
+    mask seed bpr_epoch_drop_seed(seed, e).  max_steps: at most that many batches per epoch."""
+    if isinstance(train_data, DualDeviceSampler):
+        if n_epochs is None:                       # train_epochs_dual(stepper, sampler, n_epochs): the third positional argument
+            n_epochs, trust_data = trust_data, None
+        if trust_data is not None or by_user is not None or cap is not None or n_epochs is None:
+            raise ValueError("train_epochs_dual(stepper, sampler, n_epochs, ...): the sampler holds the trust data, the path index and cap")
+        return _train_epochs_dual_sampled(stepper, train_data, int(n_epochs), batch_size, edge_dropout, after_epoch, int(first_epoch), max_steps)
+    if trust_data is None or by_user is None or cap is None or n_epochs is None:
+        raise ValueError("train_epochs_dual: trust_data, by_user, cap and n_epochs are optional for a DualDeviceSampler only")
+    if first_epoch or max_steps is not None:
+        raise ValueError("train_epochs_dual: first_epoch and max_steps apply to a DualDeviceSampler only")
+    batch_size = 256 if batch_size is None else batch_size
     totals = _run_epochs(n_epochs, lambda: epoch_arrays_dual(train_data, trust_data, by_user, cap, batch_size),
                          lambda arrays: train_epoch_dual(stepper, train_data, trust_data, by_user, cap, batch_size=batch_size,
                                                          edge_dropout=edge_dropout, arrays=arrays),
@@ -1469,8 +1744,8 @@ def train_epochs_dual(stepper, train_data, trust_data, by_user, cap, n_epochs, b
     return [t.cpu().numpy() for t in totals]
 
 
-def train_epoch_dual(stepper, train_data, trust_data, by_user, cap, batch_size=256, resample=True, pause_gc=True, max_steps=None,
-                     cum_every=None, cum_out=None, n_paths_out=None, edge_dropout=None, arrays=None):
+def train_epoch_dual(stepper, train_data, trust_data=None, by_user=None, cap=None, batch_size=None, resample=True, pause_gc=True,
+                     max_steps=None, cum_every=None, cum_out=None, n_paths_out=None, edge_dropout=None, arrays=None, epoch=0):
     """Train() of main_auto_expert_s.py:53-91 on the device: negatives drawn like the reference's (`ng_sample`), the
     epoch's sample order is the shuffled DataLoader's own, the per-batch paths are chosen by the reference's rule
     (dual_task_epoch_paths), everything is moved to the device once and every batch is one DualTaskStepper.step.
@@ -1478,7 +1753,20 @@ def train_epoch_dual(stepper, train_data, trust_data, by_user, cap, batch_size=2
     copy of the running (loss1, loss2) sums is appended to the list cum_out (device tensors: no synchronisation); n_paths_out: a
     list that receives every step's path count.  edge_dropout: None, or (keep_prob, stream[, seed]) for `--dropout 1 --keepprob p`
     (README.md:119-123; stream "reference" replays the reference's per-step `torch.rand(nnz)`, "philox" draws in-kernel) — a fresh
-    mask on the rec branch's handles per step; the model must have been built with --dropout 1."""
+    mask on the rec branch's handles per step; the model must have been built with --dropout 1.  batch_size: default 256.
+    train_data a DualDeviceSampler — train_epoch_dual(stepper, sampler, epoch=e, ...): epoch number `epoch` is drawn on the device (the
+    reference's law, not its streams); trust_data, by_user and cap are not given, batch_size is the sampler's, resample and arrays are
+    not read.  The training stream waits on the draw's event, the host on that event alone (for the counts); the epoch then runs as
+    ONE native call over the sampler's buffers (DualTaskStepper.epoch_strided) where the native epoch applies, through the same loop
+    with slices at k * cap otherwise.  No thread, no global generator."""
+    if isinstance(train_data, DualDeviceSampler):
+        if trust_data is not None or by_user is not None or cap is not None:
+            raise ValueError("train_epoch_dual(stepper, sampler, ...): the sampler holds the trust data, the path index and cap")
+        return _train_epoch_dual_sampled(stepper, train_data, epoch, batch_size, pause_gc, max_steps, cum_every, cum_out, n_paths_out,
+                                         edge_dropout)
+    if trust_data is None or by_user is None or cap is None:
+        raise ValueError("train_epoch_dual: trust_data, by_user and cap are optional for a DualDeviceSampler only")
+    batch_size = 256 if batch_size is None else batch_size
     if arrays is None:
         arrays = epoch_arrays_dual(train_data, trust_data, by_user, cap, batch_size, resample, max_steps)
     users_h, items_h, labels_h, seq_h, seq_l_h, tgt_h, chosen = arrays
