@@ -848,8 +848,14 @@ typedef struct spex_lightgcn_step {
     int32_t flags;                           /* SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE / _PUSH, SPEX_STEP_WIDE */
     /* appended for spex_lightgcn_step_bpr_adam_f32 / spex_lightgcn_epoch_bpr_f32 (the BCE entry points never read them): */
     float weight_decay;                      /* >= 0: upstream LightGCN's L2 term on the E0 rows of the batch */
-    int32_t *row_counts;                     /* [2, N] int32, all-zero before the first call: per-row occurrence counts, by step parity */
+    int32_t *row_counts;                     /* [2, N] int32, all-zero before the first call: per-row occurrence counts, by step parity.
+                                              * Only spex_lightgcn_step_bpr_adam_f32 (and the epochs over it) keeps the tables: a caller
+                                              * that advances t by ANY other call must clear both before the next BPR step */
 } spex_lightgcn_step_t;
+/* (On a descriptor shared with the exact BPR step: this call advances t and leaves row_counts alone.  The BPR step counts into the
+ * table of its own t's parity and relies on the step before it to have cleared that table, so clear both tables — one memset of
+ * 8 N bytes — between a BPR step and the next one whenever a BCE step, or a BCE epoch, ran in between; an odd number of BCE steps
+ * otherwise leaves the next BPR step adding to the counts of the one before: a stale L2 gradient.) */
 int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *step, const int64_t *users, const int64_t *items, const float *labels,
                                int32_t B, float *loss_sum, void *stream);
 /* Train() of main_rec.py:30-37 over a whole pre-shuffled, device-resident epoch as ONE call: batch k = samples [k B, min((k+1) B, n))
@@ -867,7 +873,8 @@ int spex_lightgcn_epoch_bce_f32(spex_lightgcn_step_t *step, const int64_t *users
  * (spex_lightgcn_bpr_batch_f32; at d = 128 / 256 spex_lightgcn_bpr_batch_wide_f32) in the middle.  d == 64 — any other width is
  * rejected — unless flags carries SPEX_STEP_WIDE: then d = 128 or 256 (any other width is rejected) and every table and slot of the
  * descriptor is d wide; the epoch and sampled-epoch calls below go through this step and take the same descriptors.  The descriptor's buffers as for the BCE step, with slot_capacity >= 3 T and row_counts [2, N] int32 (all-zero before the
- * first call; every call leaves the table of the next step's parity all-zero).
+ * first call; every call leaves the table of the next step's parity all-zero — and expects the table of its OWN parity all-zero on
+ * entry: advance t by no other call without clearing both tables, see spex_lightgcn_step_t).
  *   loss = mean_t softplus(xn_t - xp_t) + weight_decay * 0.5 * sum_t (|E0[u_t]|^2 + |E0[p_t]|^2 + |E0[n_t]|^2) / T
  *   fast path: L-1 x spex_spmm_f32 (plain for L <= 3) -> spex_lightgcn_bpr_batch_f32 -> L-1 x spex_spmm_f32 on A^T (all plain at
  *   L == 3) -> Adam (sums the per-triple losses in order, adds the L2 gradient): 2 L launches.  From 768 (d = 64), 1 024 (d = 128) or 512 (d = 256) triples up (measured on Epinion2;

@@ -137,6 +137,7 @@ class LightGCNStepper:
             _, loss_sum = ops.score_bce(lo[:self.n_u], lo[self.n_u:], users, items, labels, self.g_out[:self.n_u],
                                         self.g_out[self.n_u:], 1.0 / B, loss_sum=loss_acc, want_gamma=False, grad_slots=self.grad_slots)
             self.backward_from_batch_rows(users, items)
+        self._clear_row_counts()
         self.t += 1
         ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps,
                       zero=self.g_out)
@@ -149,6 +150,14 @@ class LightGCNStepper:
             self.grad_slots = torch.zeros((rows_per_sample * B, self.E0.shape[1]), dtype=torch.float32, device=self.E0.device)
             self._desc = None
         return self.grad_slots
+
+    def _clear_row_counts(self):
+        """For every path that advances t by anything but the one-call exact BPR step.  That step counts the batch's rows into
+        row_counts[(t + 1) & 1] and clears the OTHER table, relying on the step before it to have cleared the one it counts into:
+        a step that advances t without the tables would leave the next BPR step of the same parity adding to stale counts (a stale
+        L2 gradient weight_decay / T * count[row] * E0[row]).  Nothing to do on a stepper that never ran a one-call BPR step."""
+        if self.row_counts is not None:
+            self.row_counts.zero_()
 
     def set_edge_dropout(self, mask=None):
         """The next steps' edge-dropout mask on graph and graph_t (an edge_dropout_mask(...) tuple; None: off) — model.py:46-55."""
@@ -198,6 +207,7 @@ class LightGCNStepper:
     def _step_bce_one_call(self, users, items, labels, loss_acc):
         B = users.numel()
         d = self._prepare_desc(B)
+        self._clear_row_counts()
         _launch(self.E0.device, "spex_lightgcn_step_bce_f32", ctypes.byref(d), ctypes.c_void_p(users.data_ptr()),
                 ctypes.c_void_p(items.data_ptr()), ctypes.c_void_p(labels.data_ptr()), B, ctypes.c_void_p(loss_acc.data_ptr()))
         self.t = d.t
@@ -215,6 +225,7 @@ class LightGCNStepper:
             raise ValueError("LightGCNStepper.epoch_bce: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
         d = self._prepare_desc(min(int(batch_size), users.numel()))
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._clear_row_counts()
         _launch(self.E0.device, "spex_lightgcn_epoch_bce_f32", ctypes.byref(d), vp(users), vp(items), vp(labels), users.numel(), int(batch_size),
                 -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
         self.t = d.t
@@ -292,8 +303,7 @@ class LightGCNStepper:
         loss_sum = ops.bpr_loss_grad(lo[:self.n_u], lo[self.n_u:], users, pos, neg, self.g_out[:self.n_u],
                                      self.g_out[self.n_u:], 1.0 / T)
         self._ws0_clean = False
-        if self.row_counts is not None:
-            self.row_counts.zero_()              # (the one-call step's count tables go by step parity: this step advances t without them)
+        self._clear_row_counts()                 # (the one-call step's count tables go by step parity: this step advances t without them)
         self.graph_t.propagate_bwd(self.g_out, self.L, grad_E0=self.grad_E0, ws=self.ws_bwd)
         if self.weight_decay > 0:
             dev = self.E0.device
@@ -412,6 +422,7 @@ class LightGCNStepper:
         epoch_bce(*sampler.draw(epoch), ...).  loss_full / loss_ragged, max_steps, keep_prob, drop_seed as in epoch_bce."""
         d, tables, loop, bufs = self._sampled_bce_args(sampler, batch_size, max_steps, keep_prob, "epoch_bce_sampled")
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._clear_row_counts()
         _launch(self.E0.device, "spex_lightgcn_epoch_bce_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
                 int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
         self.t = d.t
@@ -428,6 +439,7 @@ class LightGCNStepper:
         if int(n_epochs) == 0:
             return
         d, tables, loop, bufs = self._sampled_bce_args(sampler, batch_size, max_steps, keep_prob, "train_bce_sampled")
+        self._clear_row_counts()
         _launch(self.E0.device, "spex_lightgcn_train_bce_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
                 *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
         self.t = d.t
