@@ -667,6 +667,60 @@ int spex_sample_dual_task_paths(const int64_t *d_users, int64_t n, int32_t B, in
                                 const int64_t *d_path_l, const int64_t *d_path_tgt, int32_t cap, uint64_t seed, uint32_t epoch,
                                 int64_t *d_seq, int64_t *d_seq_l, int64_t *d_targets, int32_t *d_count, void *stream);
 
+/* ------------------------------------------------------------------------------------------------ NGCF epoch sampler
+ * One NGCF epoch drawn on the device, already shuffled: what load_train_data / train_sample of NGCF_SPEX/code/utility/load_data.py
+ * (per user 5 |positives| DISTINCT negatives, random.sample from the items seen in training minus the user's own, then the positives)
+ * followed by the DataLoader's shuffle prepare on the host (law, not stream: for the same seed the individual samples differ from the
+ * reference's).  NOT spex_sample_bce_epoch's law: a user's negatives are drawn WITHOUT replacement, from a population that is the
+ * set of items seen in training, not the whole catalogue.  Tables (device, trainer.ngcf_sampler_tables builds them):
+ *   d_pop      int32[n_pop]   the population: the distinct items seen in training, ascending (ids may have gaps)
+ *   d_user     int32[U]       U = n_users: the epoch's users in the reference's order (file order, whole blocks of 256 users: the
+ *                             caller's cut — the kernel takes the list as given)
+ *   d_pos_off  int32[U + 1]   d_pos_off[0] = 0, non-decreasing, d_pos_off[U] = n_pos;  c_q = d_pos_off[q + 1] - d_pos_off[q] >= 0
+ *   d_pos_item int32[n_pos]   user q's positives in file order at [d_pos_off[q], d_pos_off[q + 1]), duplicates kept (each occurrence
+ *                             is a sample)
+ *   d_row_off  int32[U + 1]   d_row_off[0] = 0, non-decreasing;  m_q = d_row_off[q + 1] - d_row_off[q]
+ *   d_row_rank int32[d_row_off[U]]   at [d_row_off[q], d_row_off[q + 1]): the ranks within d_pop (positions, from 0) of user q's
+ *                             DISTINCT positives, ascending
+ * With n = 6 n_pos: d_users int64[n], d_items_out int64[n], d_labels float[n] (the types spex_ngcf_epoch_bce_f32 reads).
+ * The UNSHUFFLED epoch has n source samples.  User q owns the sources [6 d_pos_off[q], 6 d_pos_off[q + 1]); inside that block, with
+ * i the index from its start and k_q = 5 c_q:
+ *   i <  k_q:  negative i of user q  — user d_user[q], label 0, the item below
+ *   i >= k_q:  positive i - k_q      — user d_user[q], label 1, item d_pos_item[d_pos_off[q] + i - k_q]
+ * (the negatives first, then the positives: the reference's order; a user with c_q = 0 owns nothing).
+ * One thread per OUTPUT slot s in [0, n): slot s holds source perm(s), perm a keyed bijection of [0, n) — the epoch is written in
+ * shuffled order by one launch.
+ * Randomness: standard Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85, ten rounds), key =
+ * (seed & 0xFFFFFFFF, seed >> 32), counter (c0, c1, c2, c3) -> output words w0 w1 w2 w3.
+ *   F(x; m, K):  spex_sample_bce_epoch's balanced six-round Feistel network with cycle walking on the domain [0, m), round keys K[0 .. 5]:
+ *     bits = the bit length of m - 1 (0 for m = 1), h = max(1, ceil(bits / 2)), mask = 2^h - 1
+ *     fmix32(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16   (MurmurHash3's finaliser, mod 2^32)
+ *     repeat { L = x >> h, R = x & mask;  for r = 0 .. 5: (L, R) <- (R, L ^ (fmix32(R ^ K[r]) & mask));  x = (L << h) | R }
+ *     while x >= m;  F = x.   (A bijection of [0, m) that terminates without a cap: see spex_sample_bce_epoch.)
+ *   negative i of user q:  n_q = n_pop - m_q  (the population minus the user's distinct positives)
+ *     K[0 .. 3] = w0 .. w3 of counter (q, 0, epoch, 5);  K[4], K[5] = w0, w1 of counter (q, 1, epoch, 5)
+ *     r = F(i; n_q, K);  the item is d_pop[r + #{ t in [0, m_q) : d_row_rank[d_row_off[q] + t] - t <= r }] — the r-th member of the
+ *     population, in ascending order, that is not one of the user's positives.
+ *     The draw is keyed by (q, i) — q the user's POSITION in d_user, not the user id — and not by the slot: where the shuffle puts a
+ *     sample does not change it.  The first k_q images of a keyed bijection of [0, n_q) are k_q distinct members in random order:
+ *     random.sample's law, not its stream.
+ *   perm(s) = F(s; n, K) with K[0 .. 3] = w0 .. w3 of counter (0, 0, epoch, 6);  K[4], K[5] = w0, w1 of counter (1, 0, epoch, 6).
+ *   Stages 5 and 6 (the counter's last word) are no counter of spex_sample_bce_epoch (stages 0 .. 3) nor of
+ *   spex_sample_dual_task_paths (stage 4): one seed may serve all of these samplers.
+ * What is exact and what is not: a user's negatives are pairwise distinct, never one of the user's positives and always members of
+ * d_pop, at EVERY size — F is a bijection whatever its keys.  That each member of the complement is equally likely is a statement about
+ * domains of realistic size: on a domain of a few elements (h = 1 or 2: m <= 16) the six keyed rounds reach only a part of the m!
+ * orderings, and the frequencies over many (seed, epoch) are only roughly even there.  The same holds for perm on a tiny n.
+ * Guards: the caller promises k_q <= n_q for every user (random.sample raises ValueError("Sample larger than population or is
+ * negative") otherwise; trainer.ngcf_sampler_tables raises the same).  A negative with n_q <= 0 or i >= n_q writes item 0 and reads
+ * no table beyond the offsets; a positive whose index falls outside [0, n_pos) (offsets that break the promises above) writes item 0.
+ * A slot of (seed, epoch) is a function of s, the tables, seed and epoch alone — not of the launch's shape.
+ * Returns SPEX_ERR_INVALID before any launch for a NULL pointer, n_pop < 1, U < 0, n_pos < 0, n_pos > 0 with U < 1, or
+ * 6 n_pos >= 2^31; n_pos == 0 launches nothing. */
+int spex_sample_ngcf_epoch(const int32_t *d_pop, int32_t n_pop, const int32_t *d_user, int32_t n_users, const int32_t *d_pos_off,
+                           const int32_t *d_pos_item, int64_t n_pos, const int32_t *d_row_off, const int32_t *d_row_rank, uint64_t seed,
+                           uint32_t epoch, int64_t *d_users, int64_t *d_items_out, float *d_labels, void *stream);
+
 /* ------------------------------------------------------------------------------------------------ learned edge values
  * the Diffnet++ social / interest diffusion — the same SpMM on user x user, user x item and item x user
  * graphs whose stored values are LEARNED (a per-edge parameter pushed through a row softmax), so the values change
@@ -976,6 +1030,25 @@ int spex_ngcf_step_bce_f32(spex_ngcf_step_t *step, const int64_t *users, const i
  * spex_lightgcn_epoch_bce_f32. */
 int spex_ngcf_epoch_bce_f32(spex_ngcf_step_t *step, const int64_t *users, const int64_t *items, const float *labels, int64_t n, int32_t B,
                             int64_t max_steps, float *loss_full, float *loss_ragged, void *stream);
+/* A sampled NGCF epoch with nothing crossing the host: ONE spex_sample_ngcf_epoch launch (tables, seed, epoch as there) into the
+ * caller-owned buffers users / items (device int64[n] each) and labels (device float[n]), n = 6 n_pos, then exactly the loop of
+ * spex_ngcf_epoch_bce_f32 over them (B, max_steps, loss_full, loss_ragged as there).  The arguments of both are checked before anything
+ * is launched (the descriptor's fields are the step's to check: a descriptor it rejects ends the call after the draw, with no step
+ * run); n_pos == 0 launches nothing.  Single-layer model only, like the native epoch. */
+int spex_ngcf_epoch_bce_sampled_f32(spex_ngcf_step_t *step, const int32_t *d_pop, int32_t n_pop, const int32_t *d_user, int32_t n_users,
+                                    const int32_t *d_pos_off, const int32_t *d_pos_item, int64_t n_pos, const int32_t *d_row_off,
+                                    const int32_t *d_row_rank, uint64_t seed, uint32_t epoch, int32_t B, int64_t max_steps, int64_t *users,
+                                    int64_t *items, float *labels, float *loss_full, float *loss_ragged, void *stream);
+/* n_epochs sampled NGCF epochs (epoch numbers epoch0 .. epoch0 + n_epochs - 1, modulo 2^32) back to back on one stream, no host thread
+ * and no synchronisation between them: epoch e's loss sums accumulate into loss_epochs[2 e] (full batches) and loss_epochs[2 e + 1]
+ * (the ragged last batch); loss_epochs: device float[2 n_epochs].  One set of buffers serves every epoch: stream order puts the sampler
+ * of epoch e + 1 behind the last step of epoch e.  Message dropout needs no per-epoch reseed (the LightGCN calls reseed their edge
+ * masks per epoch because those are keyed by the step WITHIN the epoch): its mask is keyed by the descriptor's dropout_step, which
+ * every step advances and which runs on across the epochs of one call exactly as across per-epoch calls. */
+int spex_ngcf_train_bce_sampled_f32(spex_ngcf_step_t *step, const int32_t *d_pop, int32_t n_pop, const int32_t *d_user, int32_t n_users,
+                                    const int32_t *d_pos_off, const int32_t *d_pos_item, int64_t n_pos, const int32_t *d_row_off,
+                                    const int32_t *d_row_rank, uint64_t seed, uint32_t epoch0, int32_t n_epochs, int32_t B,
+                                    int64_t max_steps, int64_t *users, int64_t *items, float *labels, float *loss_epochs, void *stream);
 
 /* NGCF with MORE than one layer (`--layer_size [64,64,..]`, NGCF_SPEX/code/ngcf_parser.py:12; the layer loop of main_rec.py:71-93) —
  * the training step as one call of the library's own launches, L >= 2 layers of width 64:

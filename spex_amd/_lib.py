@@ -104,6 +104,8 @@ SIGNATURES = {
                                                c_vp, c_vp]),
     "spex_sample_bce_epoch": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp,
                                              c_vp]),
+    "spex_sample_ngcf_epoch": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp,
+                                              c_vp]),
     "spex_sample_dual_task_paths": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, ctypes.c_uint64,
                                                    ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "spex_graph_set_values": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
@@ -144,6 +146,10 @@ SIGNATURES = {
                                                            c_vp]),
     "spex_ngcf_step_bce_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "spex_ngcf_epoch_bce_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp]),
+    "spex_ngcf_epoch_bce_sampled_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, ctypes.c_uint64,
+                                                       ctypes.c_uint32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "spex_ngcf_train_bce_sampled_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, ctypes.c_uint64,
+                                                       ctypes.c_uint32, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "spex_dual_task_step_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "spex_dual_task_epoch_f32": (ctypes.c_int, [ctypes.c_void_p, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32,
                                                 ctypes.c_uint32, c_vp]),

@@ -279,6 +279,93 @@ __global__ __launch_bounds__(256) void sample_bce_epoch_kernel(const int32_t *__
     }
 }
 
+// ---- NGCF epochs (include/spex_hip.h: spex_sample_ngcf_epoch states the law word by word; tests restate it from there)
+// h = max(1, ceil(bits / 2)), bits the bit length of m - 1: the Feistel halves of the domain [0, m), m >= 1
+__device__ __forceinline__ uint32_t feistel_half_bits(uint32_t m)
+{
+    const uint32_t bits = m <= 1u ? 0u : 32u - (uint32_t)__clz((int)(m - 1u));
+    return bits <= 2u ? 1u : (bits + 1u) / 2u;
+}
+
+// One thread per OUTPUT slot, as in sample_bce_epoch_kernel: perm names the source sample the slot holds.  The sources are grouped by
+// user — user q owns [6 pos_off[q], 6 pos_off[q + 1]), its 5 c_q negatives first — so a thread finds its user by a binary search over
+// pos_off with the source's positive index x / 6 (every block starts at a multiple of 6), ~12 dependent reads of a table that stays
+// in L2.  A negative is the image of its index under the user's own keyed bijection of [0, n_q): the first 5 c_q images are distinct,
+// which is random.sample's law with no state shared between the threads of one user.
+__global__ __launch_bounds__(256) void sample_ngcf_epoch_kernel(const int32_t *__restrict__ pop, int n_pop, const int32_t *__restrict__ user,
+                                                                int n_users, const int32_t *__restrict__ pos_off,
+                                                                const int32_t *__restrict__ pos_item, uint32_t n_pos,
+                                                                const int32_t *__restrict__ row_off, const int32_t *__restrict__ row_rank,
+                                                                uint32_t n, uint32_t h, BceRoundKeys keys, uint32_t seed_lo, uint32_t seed_hi,
+                                                                uint32_t epoch, int64_t *__restrict__ users, int64_t *__restrict__ items_out,
+                                                                float *__restrict__ labels)
+{
+    const uint32_t stride = gridDim.x * blockDim.x, mask = (1u << h) - 1u;      // (h <= 16; n < 2^31: slot + stride cannot wrap)
+    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < n; slot += stride) {
+        uint32_t x = slot;
+        do {
+            uint32_t l = x >> h, r = x & mask;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const uint32_t f = l ^ (fmix32(r ^ keys.k[a]) & mask);
+                l = r;
+                r = f;
+            }
+            x = (l << h) | r;
+        } while (x >= n);
+        const int p = (int)(x / 6u);                      // p < n_pos: the first q with pos_off[q + 1] > p owns the source
+        int lo = 0, hi = n_users - 1;                     // (pos_off[n_users] = n_pos > p: q = n_users - 1 at the latest)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (pos_off[mid + 1] > p) hi = mid;
+            else lo = mid + 1;
+        }
+        const int q = lo, beg = pos_off[q];
+        const int c = pos_off[q + 1] - beg;
+        const uint32_t i = x - 6u * (uint32_t)beg, k = 5u * (uint32_t)(c > 0 ? c : 0);     // (offsets that keep their promises: i < 6 c)
+        int64_t item = 0;
+        if (i >= k) {
+            const uint32_t at = (uint32_t)beg + (i - k);
+            if (at < n_pos) item = pos_item[at];
+            users[slot] = user[q];
+            items_out[slot] = item;
+            labels[slot] = 1.0f;
+            continue;
+        }
+        const int rbeg = row_off[q];
+        int m = row_off[q + 1] - rbeg;
+        if (m < 0) m = 0;
+        const int n_q = n_pop - m;
+        if (n_q > 0 && i < (uint32_t)n_q) {
+            const Philox4 ka = philox4x32_10((uint32_t)q, 0u, epoch, 5u, seed_lo, seed_hi), kb = philox4x32_10((uint32_t)q, 1u, epoch, 5u, seed_lo, seed_hi);
+            const uint32_t key[6] = {ka.w[0], ka.w[1], ka.w[2], ka.w[3], kb.w[0], kb.w[1]};
+            const uint32_t hq = feistel_half_bits((uint32_t)n_q), mq = (1u << hq) - 1u;
+            uint32_t r_ = i;
+            do {
+                uint32_t l = r_ >> hq, r = r_ & mq;
+#pragma unroll
+                for (int a = 0; a < 6; ++a) {
+                    const uint32_t f = l ^ (fmix32(r ^ key[a]) & mq);
+                    l = r;
+                    r = f;
+                }
+                r_ = (l << hq) | r;
+            } while (r_ >= (uint32_t)n_q);
+            const int rr = (int)r_;
+            int blo = 0, bhi = m;                          // first t with row_rank[rbeg + t] - t > rr: the positives' ranks at or below
+            while (blo < bhi) {
+                const int mid = (blo + bhi) >> 1;
+                if (row_rank[rbeg + mid] - mid > rr) bhi = mid;
+                else blo = mid + 1;
+            }
+            item = pop[rr + blo];                          // rr < n_pop - m and blo <= m: inside the population
+        }
+        users[slot] = user[q];
+        items_out[slot] = item;
+        labels[slot] = 0.0f;
+    }
+}
+
 // ---- dual-task trust paths (include/spex_hip.h: spex_sample_dual_task_paths states the law word by word; tests restate it from there)
 // One 256-thread workgroup per batch.  LDS at capacity CAP (the largest batch the instance serves): the batch's users as int32
 // (-1: outside the tables), an open-addressing table of 2 CAP sample positions, the per-sample candidate counts (then their
@@ -476,6 +563,35 @@ extern "C" int spex_sample_bce_epoch(const int32_t *d_rowptr, const int32_t *d_i
     hipLaunchKernelGGL(sample_bce_epoch_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_rowptr, d_items, n_user_rows,
                        d_pos_user, d_pos_item, (uint32_t)n_pos, (uint32_t)num_ng, num_item, n, h, keys, k0, k1, epoch, d_users, d_items_out,
                        d_labels);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
+
+extern "C" int spex_sample_ngcf_epoch(const int32_t *d_pop, int32_t n_pop, const int32_t *d_user, int32_t n_users, const int32_t *d_pos_off,
+                                      const int32_t *d_pos_item, int64_t n_pos, const int32_t *d_row_off, const int32_t *d_row_rank,
+                                      uint64_t seed, uint32_t epoch, int64_t *d_users, int64_t *d_items_out, float *d_labels, void *stream)
+{
+    SPEX_CHECK_ARG(d_pop && d_user && d_pos_off && d_pos_item && d_row_off && d_row_rank && d_users && d_items_out && d_labels,
+                   "spex_sample_ngcf_epoch: NULL pointer");
+    SPEX_CHECK_ARG(n_pop >= 1 && n_users >= 0 && n_pos >= 0 && (n_pos == 0 || n_users >= 1),
+                   "spex_sample_ngcf_epoch: n_pop=%d n_users=%d n_pos=%lld (needs n_pop >= 1, n_users >= 0, n_pos >= 0, and a user for any positive)",
+                   n_pop, n_users, (long long)n_pos);
+    SPEX_CHECK_ARG(n_pos < ((int64_t)1 << 31) / 6 + 1 && 6 * n_pos < ((int64_t)1 << 31),
+                   "spex_sample_ngcf_epoch: 6 x n_pos=%lld samples: the shuffle needs fewer than 2^31", (long long)n_pos);
+    if (n_pos == 0) return SPEX_OK;
+    const uint32_t n = (uint32_t)(6 * n_pos);
+    uint32_t bits = 0;                                   // bit length of n - 1
+    while (bits < 32 && ((n - 1) >> bits) != 0) ++bits;
+    const uint32_t h = bits <= 2 ? 1u : (bits + 1) / 2;   // max(1, ceil(bits / 2)): the Feistel halves
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    uint32_t a[4], b[4];
+    philox4x32_10_host(0u, 0u, epoch, 6u, k0, k1, a);
+    philox4x32_10_host(1u, 0u, epoch, 6u, k0, k1, b);
+    const BceRoundKeys keys{{a[0], a[1], a[2], a[3], b[0], b[1]}};
+    int64_t blocks = ((int64_t)n + 255) / 256;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(sample_ngcf_epoch_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_pop, n_pop, d_user, n_users,
+                       d_pos_off, d_pos_item, (uint32_t)n_pos, d_row_off, d_row_rank, n, h, keys, k0, k1, epoch, d_users, d_items_out, d_labels);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

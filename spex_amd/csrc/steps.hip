@@ -390,6 +390,37 @@ extern "C" int spex_ngcf_epoch_bce_f32(spex_ngcf_step_t *s, const int64_t *users
     return rc;
 }
 
+// A sampled NGCF epoch: negatives (without replacement, per user), labels and the shuffle drawn on the device (sampler.hip: one launch
+// into the caller's buffers) and consumed by spex_ngcf_epoch_bce_f32 — nothing crosses the host.  Every argument check of both calls
+// comes before the sampler's launch.
+extern "C" int spex_ngcf_epoch_bce_sampled_f32(spex_ngcf_step_t *s, const int32_t *d_pop, int32_t n_pop, const int32_t *d_user, int32_t n_users,
+                                               const int32_t *d_pos_off, const int32_t *d_pos_item, int64_t n_pos, const int32_t *d_row_off,
+                                               const int32_t *d_row_rank, uint64_t seed, uint32_t epoch, int32_t B, int64_t max_steps,
+                                               int64_t *users, int64_t *items, float *labels, float *loss_full, float *loss_ragged, void *stream)
+{
+    SPEX_CHECK_ARG(s && users && items && labels && loss_full && loss_ragged && B >= 1,
+                   "spex_ngcf_epoch_bce_sampled_f32: NULL pointer or B < 1");
+    SPEX_TRY(spex_sample_ngcf_epoch(d_pop, n_pop, d_user, n_users, d_pos_off, d_pos_item, n_pos, d_row_off, d_row_rank, seed, epoch, users, items,
+                                    labels, stream));
+    return spex_ngcf_epoch_bce_f32(s, users, items, labels, 6 * n_pos, B, max_steps, loss_full, loss_ragged, stream);
+}
+
+// Epochs epoch0 .. epoch0 + n_epochs - 1 of the call above, back to back on one stream: the host queues epoch after epoch and never
+// waits.  One set of buffers: epoch e + 1's sampler launch is ordered behind epoch e's last step.  No per-epoch reseed of the message
+// dropout: its mask is keyed by the descriptor's dropout_step, which the steps advance across epochs.
+extern "C" int spex_ngcf_train_bce_sampled_f32(spex_ngcf_step_t *s, const int32_t *d_pop, int32_t n_pop, const int32_t *d_user, int32_t n_users,
+                                               const int32_t *d_pos_off, const int32_t *d_pos_item, int64_t n_pos, const int32_t *d_row_off,
+                                               const int32_t *d_row_rank, uint64_t seed, uint32_t epoch0, int32_t n_epochs, int32_t B,
+                                               int64_t max_steps, int64_t *users, int64_t *items, float *labels, float *loss_epochs, void *stream)
+{
+    SPEX_CHECK_ARG(n_epochs >= 0 && loss_epochs, "spex_ngcf_train_bce_sampled_f32: n_epochs < 0 or NULL loss_epochs");
+    for (int32_t e = 0; e < n_epochs; ++e)
+        SPEX_TRY(spex_ngcf_epoch_bce_sampled_f32(s, d_pop, n_pop, d_user, n_users, d_pos_off, d_pos_item, n_pos, d_row_off, d_row_rank, seed,
+                                                 epoch0 + (uint32_t)e, B, max_steps, users, items, labels, loss_epochs + 2 * (size_t)e,
+                                                 loss_epochs + 2 * (size_t)e + 1, stream));
+    return SPEX_OK;
+}
+
 // The north-star step — 3-layer propagation + fused BPR-SGD over a batch of triples — as ONE call.  For L >= 2, on a graph without
 // rows beyond 1 024 entries and while 6 T <= N (spmm.hip: step_fuses_last; SPEX_STEP_FUSED_LAST=0 / 1 forces either form), it is L
 // launches: L - 1 whole-graph plain launches (the first with the snapshot tail described below) and ONE launch that gathers layer L

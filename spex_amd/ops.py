@@ -702,6 +702,35 @@ def sample_bce_epoch(rowptr, items, pos_user, pos_item, num_ng, num_item, seed, 
     return tuple(t[:n] for t in out)
 
 
+def sample_ngcf_epoch(pop, user, pos_off, pos_item, row_off, row_rank, seed, epoch, out=None):
+    """One NGCF epoch drawn on the GPU, already shuffled (spex_sample_ngcf_epoch; the law is written down in include/spex_hip.h): per
+    user of `user` 5 x (its positives) DISTINCT negatives from `pop` minus the user's positives with label 0, then its positives with
+    label 1, the whole in the order of a keyed bijection of (seed, epoch).  All six tables: device int32 (trainer.ngcf_sampler_tables).
+    out: (users int64, items int64, labels fp32) device tensors of at least n = 6 len(pos_item) elements to draw into (their first n
+    are returned); default: fresh ones.  Returns (users, items, labels) of n elements each."""
+    for t, name in ((pop, "pop"), (user, "user"), (pos_off, "pos_off"), (pos_item, "pos_item"), (row_off, "row_off"), (row_rank, "row_rank")):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise ValueError(f"{name}: need a contiguous torch.int32 CUDA tensor")
+    U, P = user.numel(), pos_item.numel()
+    if pos_off.numel() != U + 1 or row_off.numel() != U + 1 or pop.numel() < 1:
+        raise ValueError("sample_ngcf_epoch: pos_off and row_off need len(user) + 1 elements, pop at least one")
+    n = 6 * P
+    if n >= 2 ** 31:
+        raise ValueError(f"sample_ngcf_epoch: {n} samples: the shuffle needs fewer than 2^31")
+    if out is None:
+        out = tuple(torch.empty(n, dtype=dt, device=pop.device) for dt in (torch.int64, torch.int64, torch.float32))
+    for t, dt in zip(out, (torch.int64, torch.int64, torch.float32)):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= n):
+            raise ValueError("sample_ngcf_epoch: out needs contiguous (int64, int64, fp32) CUDA tensors of at least n elements")
+    if n == 0:                       # (an empty device tensor has no storage to point at)
+        return tuple(t[:0] for t in out)
+    _launch(pop.device, "spex_sample_ngcf_epoch", _ptr(pop), pop.numel(), _ptr(user), U, _ptr(pos_off), _ptr(pos_item), P, _ptr(row_off),
+            _ptr(row_rank), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF,
+            *(ctypes.c_void_p(t.data_ptr()) for t in out))
+    _bump(*out)
+    return tuple(t[:n] for t in out)
+
+
 def sample_dual_task_paths(users, batch_size, path_rowptr, path_idx, paths, path_l, path_tgt, cap, seed, epoch, max_steps=None, out=None):
     """Every batch's trust paths of a shuffled dual-task epoch, chosen on the GPU by one launch (spex_sample_dual_task_paths; the law is
     written down in include/spex_hip.h): all paths that start at one of the batch's users, cut to `cap` by a keyed sample without

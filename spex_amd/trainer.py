@@ -1168,6 +1168,117 @@ class NGCFStepper:
         _bump(self.E0, self.W, acc)
         return acc
 
+    def _sampled_args(self, sampler, batch_size, max_steps, who):
+        m = self.model
+        if sampler.pop.device != self.E0.device:
+            raise ValueError(f"NGCFStepper.{who}: the sampler's tables live on {sampler.pop.device}, the stepper on {self.E0.device}")
+        if self.L != 1 or (self._reference_stream and m.mess_dropout[0] > 0) or sampler.n < 1 or int(batch_size) < 1:
+            raise ValueError(f"NGCFStepper.{who}: needs the single-layer model with the counter-based dropout stream, a sampler with n >= 1 "
+                             "and batch_size >= 1")
+        d = self._prepare_desc(min(int(batch_size), sampler.n))
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        tables = (vp(sampler.pop), sampler.pop.numel(), vp(sampler.user), sampler.user.numel(), vp(sampler.pos_off), vp(sampler.pos_item),
+                  sampler.n_pos, vp(sampler.row_off), vp(sampler.row_rank), sampler.seed & 0xFFFFFFFFFFFFFFFF)
+        loop = (int(batch_size), -1 if max_steps is None else int(max_steps))
+        return d, tables, loop, tuple(vp(t) for t in sampler.epoch_buffers())
+
+    def epoch_sampled(self, sampler, epoch, batch_size, loss_full, loss_ragged, max_steps=None):
+        """Epoch number `epoch` of an NgcfDeviceSampler drawn and trained as ONE native call (spex_ngcf_epoch_bce_sampled_f32): one sampler
+        launch into the sampler's epoch buffers, then epoch()'s loop over them — the state after it is that of
+        epoch(*sampler.draw(epoch), ...)."""
+        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, "epoch_sampled")
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        _launch(self.E0.device, "spex_ngcf_epoch_bce_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop, *bufs,
+                vp(loss_full), vp(loss_ragged))
+        self.t, self.model.dropout_step = d.t, d.dropout_step
+        _bump(self.E0, self.W, loss_full, loss_ragged, *sampler.epoch_buffers())
+
+    def train_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, first_epoch=0):
+        """n_epochs sampled epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
+        (spex_ngcf_train_bce_sampled_f32): no host thread, no synchronisation.  loss_epochs: a contiguous fp32 device tensor of 2 n_epochs
+        elements, zeroed by the caller — epoch e's loss sums of the full batches / of the ragged last one accumulate into elements 2 e
+        and 2 e + 1.  The message-dropout counter runs on across the epochs, as across per-epoch calls."""
+        if not (loss_epochs.is_cuda and loss_epochs.dtype == torch.float32 and loss_epochs.is_contiguous()
+                and loss_epochs.numel() >= 2 * int(n_epochs) and int(n_epochs) >= 0):
+            raise ValueError("NGCFStepper.train_sampled: loss_epochs needs to be a contiguous fp32 device tensor of 2 n_epochs elements")
+        if int(n_epochs) == 0:
+            return
+        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, "train_sampled")
+        _launch(self.E0.device, "spex_ngcf_train_bce_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs), *loop,
+                *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
+        self.t, self.model.dropout_step = d.t, d.dropout_step
+        _bump(self.E0, self.W, loss_epochs, *sampler.epoch_buffers())
+
+
+NGCF_NEG_PER_POS = 5            # train_sample draws 5 |positives| negatives per user (NGCF_SPEX/code/utility/load_data.py:16)
+
+
+def ngcf_sampler_tables(train_items, all_items, users):
+    """The tables the device NGCF sampler draws from (spex_sample_ngcf_epoch), as host int32 arrays (pop, user, pos_off, pos_item,
+    row_off, row_rank): pop — the population, sorted(all_items); user — `users` as given (the epoch's users in the reference's order);
+    pos_off [U + 1] / pos_item — train_items[u] per user in its own order, duplicates kept (a user missing from train_items, or with an
+    empty list, has no positives and takes no part in the epoch); row_off [U + 1] / row_rank — per user the positions within pop of its
+    DISTINCT positives, ascending.  n_q = len(pop) - (row_off[q + 1] - row_off[q]) is the size of user q's complement.  Raises
+    random.sample's ValueError when some user has 5 c_q > n_q (train_sample would raise it there), and ValueError for a positive that is
+    not in all_items."""
+    pop = np.fromiter(sorted(all_items), dtype=np.int64, count=len(all_items))
+    if len(pop) < 1 or pop[0] < 0 or pop[-1] >= 2 ** 31:
+        raise ValueError("ngcf_sampler_tables: the population needs at least one item, ids in [0, 2^31)")
+    users = [int(u) for u in users]
+    lists = [np.asarray(train_items.get(u, ()), dtype=np.int64).reshape(-1) for u in users]
+    pos_off = np.zeros(len(users) + 1, np.int64)
+    row_off = np.zeros(len(users) + 1, np.int64)
+    ranks = []
+    for q, pos in enumerate(lists):
+        r = np.searchsorted(pop, np.unique(pos))
+        if len(pos) and (r.max() >= len(pop) or not np.array_equal(pop[r], np.unique(pos))):
+            raise ValueError(f"ngcf_sampler_tables: user {users[q]} has a positive outside the population")
+        if NGCF_NEG_PER_POS * len(pos) > len(pop) - len(r):
+            raise ValueError("Sample larger than population or is negative")      # (random.sample's own error)
+        ranks.append(r)
+        pos_off[q + 1] = pos_off[q] + len(pos)
+        row_off[q + 1] = row_off[q] + len(r)
+    if (NGCF_NEG_PER_POS + 1) * int(pos_off[-1]) >= 2 ** 31:
+        raise ValueError(f"ngcf_sampler_tables: {6 * int(pos_off[-1])} samples per epoch: the device shuffle needs fewer than 2^31")
+    cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+    return (pop.astype(np.int32), np.asarray(users, np.int64).astype(np.int32), pos_off.astype(np.int32), cat(lists), row_off.astype(np.int32),
+            cat(ranks))
+
+
+class NgcfDeviceSampler:
+    """NGCF epochs drawn on the device (ops.sample_ngcf_epoch): what Data.sample_epoch (train_sample per user: 5 x |positives| DISTINCT
+    negatives from the items seen in training minus the user's own, then the positives) and the DataLoader's shuffle prepare on the host,
+    written by one launch.  The law is the reference's; the stream is neither `random`'s nor torch's, so for the same seed the individual
+    samples differ (the exact-replay path stays Data.sample_epoch).  data: the drop-in Data (train_items, all_items, batch_size); the
+    epoch's users are Data.sample_epoch's: file order, whole blocks of TRAIN_USER_BLOCK users only.  Holds the tables of
+    ngcf_sampler_tables in HBM.  draw(epoch) returns that epoch's (users, items, labels) device tensors — a function of (seed, epoch)
+    alone.  Pass the sampler itself to train_epoch_ngcf / train_epochs_ngcf / NGCFStepper.epoch_sampled and the epoch samples and trains
+    in one native call: no host thread, no global generator.  Not callable and without sample_epoch on purpose: nothing can mistake it
+    for host data."""
+
+    def __init__(self, data, seed=0, device="cuda"):
+        from .dropin.ngcf.utility.load_data import TRAIN_USER_BLOCK
+        users = list(data.train_items.keys())
+        users = users[: len(users) // TRAIN_USER_BLOCK * TRAIN_USER_BLOCK]
+        tables = ngcf_sampler_tables(data.train_items, data.all_items, users)
+        self.device = torch.device(device)
+        self.pop, self.user, self.pos_off, self.pos_item, self.row_off, self.row_rank = (torch.from_numpy(a).to(self.device) for a in tables)
+        self.n_pos = int(tables[3].shape[0])
+        self.n = (NGCF_NEG_PER_POS + 1) * self.n_pos
+        self.seed, self.batch_size = int(seed), getattr(data, "batch_size", None)
+        self._buffers = None          # the buffers of the native epoch calls (epoch_buffers)
+
+    def draw(self, epoch):
+        """Epoch `epoch`'s samples as three fresh device tensors: users int64 [n], items int64 [n], labels fp32 [n]."""
+        return ops.sample_ngcf_epoch(self.pop, self.user, self.pos_off, self.pos_item, self.row_off, self.row_rank, self.seed, epoch)
+
+    def epoch_buffers(self):
+        """(users int64 [n], items int64 [n], labels fp32 [n]) device buffers, allocated once: what the native sampled epochs draw into
+        (stream order keeps one epoch's reads ahead of the next epoch's draw)."""
+        if self._buffers is None:
+            self._buffers = tuple(torch.empty(self.n, dtype=dt, device=self.device) for dt in (torch.int64, torch.int64, torch.float32))
+        return self._buffers
+
 
 def epoch_arrays_ngcf(data):
     """One NGCF epoch's samples as the reference's loop meets them (main_rec.py:118-121): Data.sample_epoch (the `random` stream), then
@@ -1177,19 +1288,47 @@ def epoch_arrays_ngcf(data):
     return us[order], vs[order], rs[order]
 
 
-def train_epochs_ngcf(stepper, data, n_epochs, batch_size=None, after_epoch=None):
+def train_epochs_ngcf(stepper, data, n_epochs, batch_size=None, after_epoch=None, first_epoch=0, max_steps=None):
     """n_epochs x train_epoch_ngcf with the NEXT epoch's samples and shuffle prepared on a second host thread while the current epoch
     runs as one native call (see train_epochs: same generators, same order of draws, same run).  Not when the stepper draws its
     message-dropout noise from torch's generator on the host (the reference stream with a dropout probability above 0): that loop
-    runs sequentially.  Returns the per-epoch loss sums."""
+    runs sequentially.  Returns the per-epoch loss sums.  max_steps: at most that many batches per epoch.
+    data an NgcfDeviceSampler: no second thread and no global generator — epochs first_epoch .. first_epoch + n_epochs - 1 are drawn on
+    the device.  Single-layer stepper with the counter-based dropout stream and no after_epoch: the whole run is ONE native call
+    (NGCFStepper.train_sampled) and one synchronisation at its end; otherwise one train_epoch_ngcf per epoch."""
+    if isinstance(data, NgcfDeviceSampler):
+        return _train_epochs_ngcf_sampled(stepper, data, n_epochs, batch_size, after_epoch, int(first_epoch), max_steps)
     host_noise = stepper._reference_stream and any(p > 0 for p in stepper.model.mess_dropout[:stepper.L])
     totals = _run_epochs(n_epochs, lambda: epoch_arrays_ngcf(data),
-                         lambda arrays: train_epoch_ngcf(stepper, data, batch_size=batch_size, arrays=arrays), after_epoch,
+                         lambda arrays: train_epoch_ngcf(stepper, data, batch_size=batch_size, arrays=arrays, max_steps=max_steps), after_epoch,
                          overlap=not host_noise)
     return [float(t) for t in totals]
 
 
-def train_epoch_ngcf(stepper, data, batch_size=None, pause_gc=True, callbacks=None, step_losses=None, max_steps=None, arrays=None):
+def _ngcf_native_sampled_ok(stepper, sampler):
+    """The sampled native epoch applies: single-layer model, counter-based message dropout, something to draw."""
+    return stepper.L == 1 and sampler.n > 0 and not (stepper._reference_stream and stepper.model.mess_dropout[0] > 0)
+
+
+def _train_epochs_ngcf_sampled(stepper, sampler, n_epochs, batch_size, after_epoch, first_epoch, max_steps):
+    bs = batch_size or sampler.batch_size
+    if after_epoch is None and n_epochs > 0 and _ngcf_native_sampled_ok(stepper, sampler):
+        acc = torch.zeros(n_epochs, 2, 1, dtype=torch.float32, device=stepper.E0.device)
+        with _gc_paused():
+            stepper.train_sampled(sampler, n_epochs, bs, acc, max_steps=max_steps, first_epoch=first_epoch)
+        n_done = min(sampler.n, len(_batch_starts(sampler.n, bs, max_steps)) * bs)
+        host = acc.cpu()                                  # the run's one synchronisation
+        return [float(_sum_of_batch_means(host[e], n_done, bs)) for e in range(n_epochs)]
+    totals = []
+    for e in range(first_epoch, first_epoch + n_epochs):
+        total = train_epoch_ngcf(stepper, sampler, batch_size=bs, max_steps=max_steps, epoch=e)
+        totals.append(total)
+        if after_epoch is not None:
+            after_epoch(e - first_epoch, total)
+    return [float(t) for t in totals]
+
+
+def train_epoch_ngcf(stepper, data, batch_size=None, pause_gc=True, callbacks=None, step_losses=None, max_steps=None, arrays=None, epoch=0):
     """train() of NGCF_SPEX/code/main_rec.py:116-131 without the per-step host work of its DataLoader loop: the epoch's
     samples are drawn like the reference's (Data.sample_epoch: `random` stream), the sample order is the DataLoader's own
     (dataloader_epoch_order: global torch RNG), the shuffled epoch is moved to the device once, and every batch is one
@@ -1197,11 +1336,26 @@ def train_epoch_ngcf(stepper, data, batch_size=None, pause_gc=True, callbacks=No
     callbacks: {k: fn} — fn() is called in front of the epoch's k-th batch (e.g. a mid-epoch evaluation; it must leave the
     model in training mode); step_losses: a list that receives every step's mean loss (synchronises per step); max_steps: stop
     after that many batches.  (stepper.dropout_stream = "reference": the message-dropout noise is the reference's own per-step
-    draw from the global generator — a validation mode, see NGCFStepper.)"""
-    arrays = arrays if arrays is not None else epoch_arrays_ngcf(data)
+    draw from the global generator — a validation mode, see NGCFStepper.)
+    data an NgcfDeviceSampler: epoch number `epoch` is drawn on the device (its law is the reference's, its stream is not) — drawn AND
+    trained in one native call (NGCFStepper.epoch_sampled) where the native epoch applies, drawn by sampler.draw(epoch) for the
+    step-by-step loop otherwise (L >= 2, callbacks, step_losses, the reference dropout stream); neither `random` nor torch's global
+    generator is touched for the samples; arrays is not read."""
+    sampler = data if isinstance(data, NgcfDeviceSampler) else None
     bs = batch_size or data.batch_size
     dev = stepper.E0.device
-    users, items, labels = _upload(dev, *arrays)
+    if sampler is not None:
+        if sampler.pop.device != dev:
+            raise ValueError(f"train_epoch_ngcf: the sampler's tables live on {sampler.pop.device}, the stepper on {dev}")
+        if not callbacks and step_losses is None and _ngcf_native_sampled_ok(stepper, sampler):
+            acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
+            with _gc_paused(pause_gc):
+                stepper.epoch_sampled(sampler, epoch, bs, acc[0], acc[1], max_steps=max_steps)
+            return _sum_of_batch_means(acc, min(sampler.n, len(_batch_starts(sampler.n, bs, max_steps)) * bs), bs)
+        users, items, labels = sampler.draw(epoch)
+    else:
+        arrays = arrays if arrays is not None else epoch_arrays_ngcf(data)
+        users, items, labels = _upload(dev, *arrays)
     n = users.numel()
     starts = _batch_starts(n, bs, max_steps)
     acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
