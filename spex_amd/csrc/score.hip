@@ -159,6 +159,10 @@ __global__ __launch_bounds__(kWave *kScoreWaves) void bpr_layers_kernel(
 //            skipped triple has no rows), reads their rowptr, cuts each into 64-entry segments and numbers the segments of the 12
 //            rows consecutively: S <= 192 work items.  Wave w takes items w, w + 16, ...: one fmaf chain from 0 in entry order,
 //            16 independent gathers per batch, straight from the CSR arrays (spmm_rowlist_kernel's loop); the sum goes to LDS.
+//            The chain of dependent round trips in front of the first gather is indices -> rowptr -> (col, val): the three
+//            indices of a triple are loaded together, and the (col, val) of a wave's NEXT item is requested before the current
+//            item's gathers, so only the first item pays that trip.  (32 gathers in flight were built and measured: faster
+//            while one workgroup runs per CU, slower at two — its 62 VGPRs cost more than the depth saves)
 //   Phase B  behind ONE barrier that every wave reaches, wave k < kFuseTriples owns triple k: each of its rows is y = seg_0;
 //            y = y + seg_1; ... in segment order (no segment: 0) — the association of spmm_chunk_kernel / spmm_rowlist_kernel for
 //            every row of up to kWgRowMax entries, so y is the whole-graph launch's row bit for bit (graphs with longer rows keep
@@ -219,8 +223,9 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
         const int k = lane / 3, role = lane - 3 * k;
         const int64_t t = t_first + k;
         if (t < T) {
+            // the three indices in ONE round trip: a short-circuit chain makes the compiler load each index behind the test of the one before
             const int64_t u = u_idx[t], ip = p_idx[t], in = n_idx[t];
-            if (u >= 0 && u < n_user_rows && ip >= 0 && ip < n_item_rows && in >= 0 && in < n_item_rows) {
+            if ((int)(u >= 0) & (int)(u < n_user_rows) & (int)(ip >= 0) & (int)(ip < n_item_rows) & (int)(in >= 0) & (int)(in < n_item_rows)) {
                 my_row = role == 0 ? (int)u : (int)(n_user_rows + (role == 1 ? ip : in));
                 my_beg = rowptr[my_row];
                 my_deg = rowptr[my_row + 1] - my_beg;
@@ -252,19 +257,31 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
     }
 
     const float *__restrict__ Xl = Xg + lane;
-    for (int w = wave; w < S; w += kScoreWaves) {
-        // item w belongs to row j = the number of rows 1..11 whose first item is <= w (rows without segments share their successor's)
-        const int j = __popcll(__ballot(lane >= 1 && lane < kFuseRows && my_pre <= w));
-        const int sgi = w - __builtin_amdgcn_readlane(my_pre, j);
+    // Item w's (col, val) are REQUESTED one item ahead (a pipeline of depth two: the request of item w + 16 is issued in front of item
+    // w's gathers), so a wave's second and later items cost no metadata round trip; the entries past a segment's end are redirected
+    // when the item is taken up, not when it is requested (that would wait for the request).
+    int cnt_n = 0, col_n = 0;
+    float val_n = 0.0f;
+    auto request = [&](int wi) {
+        // item wi belongs to row j = the number of rows 1..11 whose first item is <= wi (rows without segments share their successor's)
+        const int j = __popcll(__ballot(lane >= 1 && lane < kFuseRows && my_pre <= wi));
+        const int sgi = wi - __builtin_amdgcn_readlane(my_pre, j);
         const int left = __builtin_amdgcn_readlane(my_deg, j) - sgi * kTaskEntries;
         const int e0 = __builtin_amdgcn_readlane(my_beg, j) + sgi * kTaskEntries;
-        const int cnt = left < kTaskEntries ? left : kTaskEntries;
-        int my_col = 0;
-        float my_val = 0.0f;
-        if (lane < cnt) {
-            my_col = col[e0 + lane];
-            my_val = val[e0 + lane];
+        cnt_n = left < kTaskEntries ? left : kTaskEntries;
+        col_n = 0;
+        val_n = 0.0f;
+        if (lane < cnt_n) {
+            col_n = col[e0 + lane];
+            val_n = val[e0 + lane];
         }
+    };
+    if (wave < S) request(wave);
+    for (int w = wave; w < S; w += kScoreWaves) {
+        const int cnt = cnt_n;
+        int my_col = col_n;
+        const float my_val = val_n;
+        if (w + kScoreWaves < S) request(w + kScoreWaves);
         // entries past the segment's end: value 0 on the segment's last real source row (a line already being fetched)
         const int last_col = __builtin_amdgcn_readlane(my_col, (cnt - 1) & 63);
         if (lane >= cnt) my_col = last_col;
