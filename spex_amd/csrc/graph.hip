@@ -216,6 +216,9 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
     std::vector<int4> hub_grp;
     std::vector<int2> hub_fold;
     const bool chunked = true;
+    // SPEX_PACK_IMPLIED=0: the dense chunk layout on every table (read here, at creation: the tests and the A/B timings build both)
+    const char *implied_sw = getenv("SPEX_PACK_IMPLIED");
+    const bool pack_implied = !(implied_sw && implied_sw[0] == '0');
     g->row_ids = (int64_t)n_cols * 256 <= ((int64_t)16 << 20);
     (void)flags;
     const int32_t tile_rows = 0;                 // (round 3's tile mode — at most 64 rows per workgroup, for a fused SpMM + NGCF layer launch
@@ -277,14 +280,39 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
             n_planned += nch;
             return make_int2((int32_t)j.first_chunk, (int32_t)nch);
         };
+        // Implied positions (bin-packed tables; spex_common.h: chunk_stride): once the task table stands, task k's chunks move to
+        // chunk k * stride — the kernel then asks for a wave's first metadata in the same round trip as its task record.  Slots no
+        // task fills keep column 0, value 0, edge 0 and chunk_pad = kChunk: padding to every reader.
+        bool implied = false;
+        auto place_implied = [&]() {
+            const int32_t stride = pack_cap / spex::kChunk;
+            if (!pack_implied || !g->row_ids || (int64_t)task.size() * stride > (int64_t)INT32_MAX / spex::kChunk) return;
+            for (const int4 &t : task)
+                if (t.y > stride) return;                          // (never: a segment is kTaskEntries, a pack at most pack_cap)
+            std::vector<int64_t> moved(jobs.size(), -1);
+            for (size_t k = 0; k < task.size(); ++k) {
+                int4 &t = task[k];
+                if (t.y > 0) {                                      // the job that planned this task's chunks (jobs are in planning order)
+                    const size_t j = (size_t)(std::lower_bound(jobs.begin(), jobs.end(), (int64_t)t.x,
+                                                               [](const ChunkJob &jb, int64_t v) { return jb.first_chunk < v; }) - jobs.begin());
+                    moved[j] = (int64_t)k * stride;
+                }
+                t.x = (int32_t)((int64_t)k * stride);
+            }
+            for (size_t j = 0; j < jobs.size(); ++j) jobs[j].first_chunk = moved[j];
+            n_planned = (int64_t)task.size() * stride;
+            implied = true;
+            g->chunk_stride = stride;
+        };
         auto fill_chunks = [&]() {
+            place_implied();
             const size_t n_slots = (size_t)n_planned * spex::kChunk;
             c_off.resize(n_slots);
             c_val.resize(n_slots);
             c_eid.resize(n_slots);
             if (g->row_ids) c_row.resize(n_slots);
             c_mask.resize((size_t)n_planned);
-            c_pad.resize((size_t)n_planned);
+            c_pad.assign((size_t)n_planned, implied ? (uint8_t)spex::kChunk : (uint8_t)0);
             const bool row_ids = g->row_ids;
             auto fill_job = [&](const ChunkJob &j) {
                 size_t pos = (size_t)j.first_chunk * spex::kChunk, ci = (size_t)j.first_chunk;
@@ -346,6 +374,10 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
             cut[0] = 0;
             for (int p = 1; p < n_thr; ++p) {
                 const int64_t want = n_planned * p / n_thr;
+                if (implied) {                                      // (positions follow the task table, not the job list: split by count)
+                    cut[p] = jobs.size() * (size_t)p / (size_t)n_thr;
+                    continue;
+                }
                 cut[p] = (size_t)(std::lower_bound(jobs.begin(), jobs.end(), want,
                                                    [](const ChunkJob &j, int64_t v) { return j.first_chunk < v; }) - jobs.begin());
             }
@@ -533,9 +565,10 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
     g->tile_rows = tile_rows;
     g->n_wgs = (int32_t)wg_rows.size();
     if (getenv("SPEX_DEBUG_PACK"))
-        fprintf(stderr, "[spex] graph %d x %d nnz %lld: %d tasks = %d workgroups, %lld chunks (%.1f %% padding), tile mode %d (%d workgroups)\n",
+        fprintf(stderr, "[spex] graph %d x %d nnz %lld: %d tasks = %d workgroups, %lld chunks (%.1f %% padding), tile mode %d (%d workgroups), chunk stride %d, chunk table %lld bytes\n",
                 n_rows, n_cols, (long long)nnz, (int)task.size(), (int)task.size() / spex::kWgWaves, (long long)c_mask.size(),
-                nnz ? 100.0 * ((double)c_mask.size() * spex::kChunk - (double)nnz) / (double)nnz : 0.0, tile_rows, g->n_wgs);
+                nnz ? 100.0 * ((double)c_mask.size() * spex::kChunk - (double)nnz) / (double)nnz : 0.0, tile_rows, g->n_wgs, g->chunk_stride,
+                (long long)(c_off.size() * 4 + c_val.size() * 4 + c_eid.size() * 4 + c_row.size() * 4 + c_mask.size() * 4 + c_pad.size()));
     g->n_chunks = (int64_t)c_mask.size();
     g->n_hub = (int32_t)hub_row.size();
     g->n_hub_tasks = (int32_t)hub_grp.size();

@@ -9,6 +9,8 @@
 // wave load, the dot product is a 6-step cross-lane butterfly, the gradient rows are added with hardware float
 // atomics shaped as one contiguous 256-byte wave instruction per row (the full-rate shape on MI355X; duplicates of a
 // user within a batch accumulate correctly).
+#include <type_traits>
+
 #include "spex_common.h"
 
 using namespace spex;
@@ -217,6 +219,9 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
     __shared__ float s_seg[kFuseSegs][kWave];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    // (every kernel argument Phase A reads, requested in ONE scalar trip instead of where each is first used)
+    asm volatile("" ::"s"(T), "s"(n_user_rows), "s"(n_item_rows), "s"(u_idx), "s"(p_idx), "s"(n_idx), "s"(rowptr), "s"(col), "s"(val), "s"(Xg),
+                 "s"(ts), "s"(t0), "s"(t1));
     const int64_t t_first = (int64_t)blockIdx.x * kFuseTriples;
     int my_row = -1, my_beg = 0, my_deg = 0;
     if (lane < kFuseRows) {
@@ -286,6 +291,27 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
         const int last_col = __builtin_amdgcn_readlane(my_col, (cnt - 1) & 63);
         if (lane >= cnt) my_col = last_col;
         float acc = 0.0f;
+#if SPEX_FUSED_QUADS
+        // a chunk gathers its real entries only, four at a time (cnt is wave-uniform: scalar branches) — the segment's last chunk is
+        // the one that is partly filled.  The terms left out were fmaf(0, x, acc) = acc; the chain over the real entries is the same.
+        // (One straight-line body per quad count: guarded quads inside one body cost the kernel 7 VGPRs.)
+        auto gather = [&](auto n_, int c) {
+            constexpr int N = decltype(n_)::value;
+            float x[N];
+#pragma unroll
+            for (int k = 0; k < N; ++k)
+                x[k] = Xl[(size_t)(uint32_t)__builtin_amdgcn_readlane(my_col, c * kChunk + k) * 64];
+#pragma unroll
+            for (int k = 0; k < N; ++k) acc = fmaf(lane_bcast_f(my_val, c * kChunk + k), x[k], acc);
+        };
+        for (int c = 0; c * kChunk < cnt; ++c) {
+            const int rem = cnt - c * kChunk;              // >= 1
+            if (rem > 12) gather(std::integral_constant<int, 16>(), c);
+            else if (rem > 8) gather(std::integral_constant<int, 12>(), c);
+            else if (rem > 4) gather(std::integral_constant<int, 8>(), c);
+            else gather(std::integral_constant<int, 4>(), c);
+        }
+#else
         for (int c = 0; c * kChunk < cnt; ++c) {
             float x[kChunk];
 #pragma unroll
@@ -294,6 +320,7 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
 #pragma unroll
             for (int k = 0; k < kChunk; ++k) acc = fmaf(lane_bcast_f(my_val, c * kChunk + k), x[k], acc);
         }
+#endif
         s_seg[w][lane] = acc;
     }
     __syncthreads();
@@ -317,9 +344,13 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
         const float x = wave_sum(uu * vn) - wave_sum(uu * vp);   // neg_score - pos_score
         lsum = softplus_f(x);
         const float a = a_coef * sigmoid_f(x);
-        atomicAdd(table_w + ou, a * (vn - vp) + b_coef * uu);
-        atomicAdd(table_w + op, -a * uu + b_coef * vp);
-        atomicAdd(table_w + on, a * uu + b_coef * vn);
+        // (the update addresses are formed again here from the scalar rows: kept from the prologue they are three VGPR pairs live
+        //  across the gather loop — the 49th register of a kernel that has to stay within 48)
+        int ru_w = ru, rp_w = rp, rn_w = rn;
+        asm volatile("" : "+s"(ru_w), "+s"(rp_w), "+s"(rn_w));
+        atomicAdd(table_w + (size_t)ru_w * kWave + lane, a * (vn - vp) + b_coef * uu);
+        atomicAdd(table_w + (size_t)rp_w * kWave + lane, -a * uu + b_coef * vp);
+        atomicAdd(table_w + (size_t)rn_w * kWave + lane, a * uu + b_coef * vn);
     }
     if (loss_sum) group_loss_add(lsum, loss_sum, loss_cells);
 }

@@ -116,6 +116,11 @@ int sum_parts(const float *parts, int32_t n_parts, int64_t stride, int32_t n, fl
         }                                                                                       \
     } while (0)
 
+// A/B switch of the one-call BPR step's fused launch (score.hip: bpr_fused_last_kernel), for scratch builds: 0 = the form before.
+#ifndef SPEX_FUSED_QUADS
+#define SPEX_FUSED_QUADS 1         // a segment's last chunk gathers its real entries only, four at a time
+#endif
+
 constexpr int kWave = 64;          // CDNA wavefront
 constexpr int kWavesPerBlock = 4;  // 256-thread workgroups
 constexpr int kLongRow = 128;      // generic kernel / hub path: rows with more stored entries are cut into segments
@@ -329,6 +334,11 @@ struct spex_graph {
     uint32_t *chunk_eid = nullptr;  // [n_chunks * 16] edge id of each entry (keep-mask index); read only under dropout
     bool row_ids = false;           // tasks pack non-adjacent rows (cache-resident graphs): the kernel reads chunk_row
     int32_t *chunk_row = nullptr;   // [n_chunks * 16] output row of each entry, only when row_ids
+    // Implied positions (bin-packed tables, unless SPEX_PACK_IMPLIED=0): task k's chunks start at chunk k * chunk_stride
+    // (chunk_stride = the pack capacity in chunks: 4, or 5 / 6 where the packer raised it), so the d == 64 kernel requests a wave's
+    // first 64 entries of metadata together with its task record; task.x is still stored (= k * chunk_stride) and the slots no task
+    // fills are padding (column 0, value 0, edge 0, chunk_pad = kChunk).  0: the dense layout (tables that stream from HBM).
+    int32_t chunk_stride = 0;
     // Tile mode (spex_graph_create_ex, SPEX_GRAPH_TILE_ROWS): every workgroup of the task table completes at most kTileRows rows,
     // task.w bits 16-23 = the workgroup-local slot of the task's first completed row — what the fused NGCF layer kernel needs
     // to hold a workgroup's rows in LDS.  0 = ordinary table.

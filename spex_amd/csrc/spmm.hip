@@ -283,7 +283,8 @@ __device__ __forceinline__ void snapshot_rows(const SnapArgs &s, const float *__
         const int which = j < s.T ? 0 : (j < 2 * s.T ? 1 : 2);
         const int64_t t = j - which * s.T;
         const int64_t u = s.u[t], ip = s.ip[t], in = s.in[t];
-        const bool ok = u >= 0 && u < s.n_user_rows && ip >= 0 && ip < s.n_item_rows && in >= 0 && in < s.n_item_rows;
+        // (one round trip for the three indices: a short-circuit chain makes the compiler load each behind the test of the one before)
+        const bool ok = (int)(u >= 0) & (int)(u < s.n_user_rows) & (int)(ip >= 0) & (int)(ip < s.n_item_rows) & (int)(in >= 0) & (int)(in < s.n_item_rows);
         if (ok) my_row = which == 0 ? (int)u : s.n_user_rows + (int)(which == 1 ? ip : in);
     }
     const float *__restrict__ Xl = X + lane;
@@ -317,11 +318,16 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
     int n_tasks, float *__restrict__ Y,
     const float *epi_in, float epi_div, float out_div, float *acc_out,   // may alias each other (running sum in place): no __restrict__
     float *__restrict__ partial,
-    const DropArgs drop, const int xcd_contiguous, const HubFold hf_args, const SnapArgs snap)
+    const DropArgs drop, const int xcd_contiguous, const HubFold hf_args, const SnapArgs snap, const int chunk_stride)
 {
     __shared__ float s_part[kWgWaves][kWave];  // segment sums of the rows this workgroup combines
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    // Every kernel argument the prologue reads, requested in ONE scalar trip: left to itself the compiler loads them where they are
+    // first used — behind the tail test, behind the XCD remap, behind the bounds test: three dependent waits in front of the first
+    // vector load.
+    asm volatile("" ::"s"(n_tasks), "s"(xcd_contiguous), "s"(chunk_stride), "s"(snap.table_wgs), "s"(chunk_off), "s"(chunk_val), "s"(chunk_row),
+                 "s"(chunk_mask), "s"(task));
     // The unmasked plain form may carry a snapshot tail (SnapArgs): whole workgroups behind the table's, decided once, here, on
     // scalar values; they touch neither s_part nor the hub tickets.  Only these instantiations read `snap`.
     constexpr bool kTail = EPI == 0 && !MASKED && FOLD;
@@ -339,6 +345,22 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
     const int wg = xcd_contiguous ? xcd_contiguous_block(blockIdx.x, n_wg) : (int)blockIdx.x;
     const int tid = wg * kWgWaves + wave;
     if (tid >= n_tasks) return;  // whole workgroups only (n_tasks is a multiple of kWgWaves)
+    // Implied positions (chunk_stride != 0, bin-packed tables: spex_common.h): task tid's chunks start at chunk tid * chunk_stride
+    // whatever the task record says, so its first super-chunk's metadata — all 64 lanes, the four mask words — is requested HERE, in
+    // the same round trip as the record, instead of behind it; the lanes beyond the task's chunks are cut off once the record is in (a
+    // null task loads and discards: every position below n_tasks * chunk_stride chunks exists, and chunk_stride >= 4).
+    const bool implied = ROWIDS && chunk_stride != 0;
+    uint32_t pre_off = 0u, pre_mask = 0u, pre_eid = 0u;
+    int pre_row = 0;
+    float pre_val = 0.0f;
+    if (implied) {
+        const size_t c0 = (size_t)tid * (size_t)chunk_stride, e = c0 * kChunk + lane;
+        pre_off = __builtin_nontemporal_load(chunk_off + e);
+        pre_val = __builtin_nontemporal_load(chunk_val + e);
+        pre_row = __builtin_nontemporal_load(chunk_row + e);
+        if (MASKED) pre_eid = __builtin_nontemporal_load(drop.chunk_eid + e);
+        pre_mask = __builtin_nontemporal_load(chunk_mask + c0 + (lane & 3));
+    }
     const int4 t = task[tid];
     const int kind = t.w & 3;
     const float *__restrict__ Xl = X + lane;
@@ -389,7 +411,8 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
     if (ROWIDS && kind == 3) {
         typedef float f4 __attribute__((ext_vector_type(4)));
         const int count = t.w >> 4;
-        const int my_r = lane < count ? chunk_row[(size_t)t.x * kChunk + lane] : -1;
+        int my_r = -1;
+        if (lane < count) my_r = implied ? pre_row : chunk_row[(size_t)t.x * kChunk + lane];
         const int sub = lane & 15, grp = lane >> 4;
         const f4 zero = (f4)(0.0f);
         for (int k0 = 0; k0 < count; k0 += 16) {
@@ -424,19 +447,31 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
         }
     }
     const int n_ch = kind == 3 ? 0 : t.y;              // (kind 3: handled above)
-    for (int sc = 0; sc < n_ch; sc += 4) {
+    // One super-chunk (<= 4 chunks from chunk t.x + sc).  first: the one requested in front of the task record (implied positions) —
+    // bin-packed instantiations run it as a call of its own in front of the loop, so that the requested values are not live across
+    // the loop (as loop-carried values they cost the epilogue forms their 65th and 66th VGPR); a task has more than one super-chunk
+    // only where the packer raised the pack capacity.
+    auto super_chunk = [&](const int sc, const bool first) __attribute__((always_inline)) {
         const int nc = (n_ch - sc < 4) ? n_ch - sc : 4;  // chunks in this super-chunk (wave-uniform)
         uint32_t my_off = 0u, my_mask = 0u, own_off = 0u;
         unsigned long long drop_bits = 0ull;                 // MASKED: entries of this super-chunk that are dropped (wave-uniform)
         int my_row = 0;
         float my_val = 0.0f;
         if (lane < nc * kChunk) {
-            const size_t e = (size_t)(t.x + sc) * kChunk + lane;
-            my_off = __builtin_nontemporal_load(chunk_off + e);   // metadata is read once per launch
-            my_val = __builtin_nontemporal_load(chunk_val + e);
-            if (ROWIDS) my_row = __builtin_nontemporal_load(chunk_row + e);
+            uint32_t eid = 0u;
+            if (first) {
+                my_off = pre_off;
+                my_val = pre_val;
+                my_row = pre_row;
+                if (MASKED) eid = pre_eid;
+            } else {
+                const size_t e = (size_t)(t.x + sc) * kChunk + lane;
+                my_off = __builtin_nontemporal_load(chunk_off + e);   // metadata is read once per launch
+                my_val = __builtin_nontemporal_load(chunk_val + e);
+                if (ROWIDS) my_row = __builtin_nontemporal_load(chunk_row + e);
+                if (MASKED) eid = __builtin_nontemporal_load(drop.chunk_eid + e);
+            }
             if (MASKED) {
-                const uint32_t eid = __builtin_nontemporal_load(drop.chunk_eid + e);
                 bool kept;
                 if (drop.mode == 1) {
                     kept = drop.keep[eid] != 0;
@@ -459,7 +494,8 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
             const uint32_t stand_in = (uint32_t)__builtin_amdgcn_readlane((int)my_off, src);   // wave-uniform
             if (dropped) my_off = kept_lanes ? stand_in : own_off;
         }
-        if (lane < nc) my_mask = __builtin_nontemporal_load(chunk_mask + t.x + sc + lane);
+        if (first) my_mask = pre_mask;                       // (lane c < 4 holds chunk c's word; words beyond nc are not read)
+        else if (lane < nc) my_mask = __builtin_nontemporal_load(chunk_mask + t.x + sc + lane);
         float ep[kChunk];
 #pragma unroll
         for (int u = 0; u < kChunk; ++u) ep[u] = 0.0f;
@@ -510,6 +546,23 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
                 }
             }
         }
+    };
+    if (ROWIDS) {
+        if (n_ch > 0) {
+            const int nc0 = n_ch < 4 ? n_ch : 4;
+            if (!implied && lane < nc0 * kChunk) {      // the dense layout: the same values, requested behind the record
+                const size_t e = (size_t)t.x * kChunk + lane;
+                pre_off = __builtin_nontemporal_load(chunk_off + e);
+                pre_val = __builtin_nontemporal_load(chunk_val + e);
+                pre_row = __builtin_nontemporal_load(chunk_row + e);
+                if (MASKED) pre_eid = __builtin_nontemporal_load(drop.chunk_eid + e);
+                if (lane < nc0) pre_mask = __builtin_nontemporal_load(chunk_mask + t.x + lane);   // (the table ends with its last chunk)
+            }
+            super_chunk(0, true);
+        }
+        for (int sc = 4; sc < n_ch; sc += 4) super_chunk(sc, false);
+    } else {
+        for (int sc = 0; sc < n_ch; sc += 4) super_chunk(sc, false);
     }
     if (kind == 0 && t.y == 0 && t.z >= 0) {  // a row without stored entries: y = 0, the epilogue still applies
         float e = 0.0f;
@@ -936,11 +989,11 @@ void launch_chunk_v(bool masked, bool row_ids, dim3 grid, dim3 block, hipStream_
         if (V == 1 && (!M || hub.tag != 0u))                                                                           \
             hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, true>), grid, block, 0, stream, X, g->chunk_off,          \
                                g->chunk_val, g->chunk_mask, g->chunk_row, g->task, g->n_tasks, Y, epi_in, epi_div,     \
-                               out_div, acc_out, g->partial, da, xcd_contig, hub, snap);                               \
+                               out_div, acc_out, g->partial, da, xcd_contig, hub, snap, g->chunk_stride);              \
         else if (V == 1)                                                                                               \
             hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, !M>), grid, block, 0, stream, X, g->chunk_off,            \
                                g->chunk_val, g->chunk_mask, g->chunk_row, g->task, g->n_tasks, Y, epi_in, epi_div,     \
-                               out_div, acc_out, g->partial, da, xcd_contig, hub, snap);                               \
+                               out_div, acc_out, g->partial, da, xcd_contig, hub, snap, g->chunk_stride);              \
         else                                                                                                           \
             hipLaunchKernelGGL((spmm_chunk_wide_kernel<EPI, M, R, (V == 1 ? 2 : V)>), grid, block, 0, stream, X,       \
                                g->chunk_off, g->chunk_val, g->chunk_mask, g->chunk_row, g->task, g->n_tasks, Y, epi_in, \
