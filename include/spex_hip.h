@@ -151,6 +151,60 @@ int spex_propagate_f32(const spex_graph_t *g, const float *E0, float *mean_out, 
 int spex_propagate_bwd_f32(const spex_graph_t *gt, const float *g_out, float *grad_E0, float *ws, int32_t L,
                            int32_t d, void *stream);
 
+/* ------------------------------------------------------------------------------------------------ bf16 gather tables
+ * Mixed precision for the propagation, d == 64 only (any other d: SPEX_ERR_UNSUPPORTED): the GATHER SOURCE is a bf16 table
+ * ([rows, 64] row-major, uint16_t bit patterns: 128-byte rows, one L2 line instead of two), everything else stays fp32 —
+ * bf16 -> fp32 widening is exact and every product and sum is the fp32 fmaf chain of spex_spmm_f32 in the same order.  Rounding
+ * enters only where a table is rounded to become a gather source.  fp32 stays the default: nothing calls these unasked.
+ *
+ * spex_cast_bf16_f32: X16[i] = bf16(X[i]), round to nearest even, for i < n; NaN stays NaN, +-0 and +-Inf are preserved, finite
+ * values beyond the largest bf16 round to Inf (what torch.Tensor.to(torch.bfloat16) returns).  Any element-aligned pointers; 16-byte
+ * aligned X and 8-byte aligned X16 take the vectorised kernel.
+ */
+int spex_cast_bf16_f32(const float *X, uint16_t *X16, int64_t n, void *stream);
+
+/* spex_spmm_f32 gathering from X16 ([n_cols, 64] bf16) — with Xw = float(X16), per output element the same chain:
+ *   y[r,:]       = sum_e val[e] * Xw[col[e],:]              (acc = fmaf(val, widen(x16), acc) in the task's entry order; segments of
+ *                                                            rows of 65..1 024 entries added through LDS in segment order)
+ *   if add_in:     y += add_in[r,:] / add_div
+ *   if Y:          Y[r,:] = y                               (fp32)
+ *   if Y16:        Y16[r,:] = bf16(y), round to nearest even (the next layer's gather source: no cast pass between layers)
+ *   if acc_out:    acc_out[r,:] = (acc_in[r,:] + y) / acc_div
+ * At least one of Y, Y16, acc_out; add_in and acc_out in one launch: SPEX_ERR_UNSUPPORTED.  The result equals spex_spmm_f32's on Xw
+ * BIT FOR BIT for every row of at most 1 024 entries, also under an edge mask on the handle (applied entry by entry with
+ * spex_spmm_f32's rule: a dropped entry's gathered value is replaced by 0 and it re-reads a kept entry's source row, a kept value
+ * is divided by keep_prob).  Rows beyond 1 024 entries leave one partial row per 64-entry segment in the handle's scratch and a small
+ * second launch adds them in segment order (spex_spmm_f32's SPEX_HUB_FOLD=0 schedule; stream ordering of the scratch as there).
+ * The launch reads the handle's task and chunk tables: no second copy of the matrix; a handle without them (a source table beyond a
+ * 32-bit offset) returns SPEX_ERR_UNSUPPORTED.
+ * Alignment: X16, Y16, Y, add_in, acc_in, acc_out 16-byte aligned (the kernel itself needs 2 bytes for a gathered element and 8
+ * for the rows it writes four columns at a time; 16 is what every row of a contiguous [*, 64] tensor has).  acc_in may equal acc_out;
+ * X16 must not alias an output, nor the outputs each other.  All checks run before anything touches the device: NULL X16 / graph, no
+ * output, aliasing, misalignment, a zero divisor -> SPEX_ERR_INVALID.
+ */
+int spex_spmm_bf16_f32(const spex_graph_t *g, const uint16_t *X16, float *Y, uint16_t *Y16, const float *add_in, float add_div,
+                       const float *acc_in, float *acc_out, float acc_div, int32_t d, void *stream);
+
+/* spex_propagate_f32 with bf16 gather sources (n_rows == n_cols):
+ *   E16^0 = bf16(E0);   y_l = A E16^(l-1) in fp32 (l = 1..L);   E16^l = bf16(y_l) for l < L (written by launch l itself);
+ *   mean_out = (E0 + y_1 + ... + y_L) / (L+1).
+ * The running sum takes the EXACT fp32 E0 and the fp32 products y_l, formed by the acc_out epilogue exactly as spex_propagate_f32
+ * forms it (acc_div = L+1 on the last launch): rounding enters only through the gather sources.  One cast launch + L SpMM launches;
+ * bit-identical to spex_cast_bf16_f32 followed by L spex_spmm_bf16_f32 calls (Y16, acc_out).  L == 0: mean_out = E0.
+ * ws16: 2 * n_rows * d bf16 elements (ping-pong gather tables).  E0, mean_out, ws16: distinct, 16-byte aligned.
+ */
+int spex_propagate_bf16_f32(const spex_graph_t *g, const float *E0, float *mean_out, uint16_t *ws16 /* 2 * n_rows * d */, int32_t L,
+                            int32_t d, void *stream);
+
+/* Backward of the above w.r.t. E0, straight-through (the rounding of a gather source is treated as the identity):
+ *   G_L = g_out/(L+1);   G_l = g_out/(L+1) + A^T bf16(G_(l+1));   grad_E0 = G_0
+ * — g_out/(L+1) is formed once in fp32 (ws) and is every launch's add_in operand (add_div = 1); its rounding is the first gather
+ * source and each launch but the last writes bf16(G_l) for the next; the last writes grad_E0 in fp32.  gt: the handle of A^T.
+ * ws: n_rows * d floats; ws16: 2 * n_rows * d bf16 elements.  g_out, grad_E0, ws, ws16: distinct, 16-byte aligned.  L == 0: a copy.
+ */
+int spex_propagate_bwd_bf16_f32(const spex_graph_t *gt, const float *g_out, float *grad_E0, float *ws /* n_rows * d */,
+                                uint16_t *ws16 /* 2 * n_rows * d */, int32_t L, int32_t d, void *stream);
+
 /* ------------------------------------------------------------------------------------------------ scoring
  * Replaces LightGCN.forward, utility1/model.py:111-121 (gather rows, elementwise product, sum, BCEWithLogitsLoss)
  * and NGCF compute_rec_loss, NGCF_SPEX/code/main_rec.py:89-91,96-100 — plus their autograd backward into the two

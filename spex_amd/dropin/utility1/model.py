@@ -62,7 +62,29 @@ class LightGCN(BasicModel):
         #               on Epinion2) — the validation mode: with the same seed a run drops the same edges as main_rec.py
         #               --dropout 1 and reproduces its losses step by step (tests: G12-dropout goldens).
         self.dropout_stream = os.environ.get("SPEX_DROPOUT_STREAM", "philox")
+        # What the propagation GATHERS from (SPEX_GATHER_DTYPE, read here like SPEX_DROPOUT_STREAM so that the unchanged driver can
+        # run mixed): "fp32" (default) or "bf16" — every layer gathers from a bf16 rounding of its input table while products, sums
+        # and the layer mean stay fp32 (SpexGraph.propagate(..., gather_dtype=torch.bfloat16)); the backward is straight-through.
+        self.gather_dtype = self._parse_gather_dtype(os.environ.get("SPEX_GATHER_DTYPE", "fp32"))
+        if self.gather_dtype == torch.bfloat16:
+            if isinstance(self.Graph, (list, tuple)):
+                raise ValueError("SPEX_GATHER_DTYPE=bf16 does not support --A_split: the bf16 propagation runs on the whole "
+                                 "graph (row-block folds gather fp32 only); drop one of the two")
+            if self.latent_dim != 64:
+                raise ValueError(f"SPEX_GATHER_DTYPE=bf16 needs --recdim 64 (got {self.latent_dim})")
         self._cache = None            # (version_u, version_i, light_out) for eval mode
+
+    @staticmethod
+    def _parse_gather_dtype(name):
+        try:
+            return {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}[name.strip().lower()]
+        except KeyError:
+            raise ValueError(f"SPEX_GATHER_DTYPE must be 'fp32' or 'bf16' (got {name!r})") from None
+
+    def _gather_arg(self):
+        """The trailing gather_dtype argument of the autograd Functions: () for fp32 (the call sites as they always were)."""
+        # (getattr: the dual-task model of model_expert_s.py borrows this class's propagation methods without its constructor — fp32)
+        return (torch.bfloat16,) if getattr(self, "gather_dtype", None) == torch.bfloat16 else ()
 
     # ------------------------------------------------------------------ parameter storage
     def _fuse_tables(self):
@@ -127,11 +149,13 @@ class LightGCN(BasicModel):
         if use_cache and self._cache is not None and self._cache[0] == (uw._version, iw._version, uw.data_ptr()):
             return self._cache[1]
         if isinstance(self.Graph, (list, tuple)):
+            if self._gather_arg():                        # (the attribute was set after construction)
+                raise ValueError("gather_dtype=bf16 does not support --A_split folds")
             out = self._light_out_folds(uw, iw)
         else:
             mask = self._mask_for_step()
             graph_t = self._transposed() if mask is not None else self.Graph  # A_hat is symmetric without dropout
-            out = ops.PropagateMean.apply(uw, iw, self.Graph, graph_t, self.n_layers, mask)
+            out = ops.PropagateMean.apply(uw, iw, self.Graph, graph_t, self.n_layers, mask, *self._gather_arg())
         if use_cache:
             self._cache = ((uw._version, iw._version, uw.data_ptr()), out)
         return out
@@ -177,7 +201,7 @@ class LightGCN(BasicModel):
             mask = self._mask_for_step()
             graph_t = self._transposed() if mask is not None else self.Graph
             return ops.LightGCNBCELoss.apply(uw, iw, self.Graph, graph_t, self.n_layers, mask, ops._idx(users, dev),
-                                             ops._idx(items, dev), labels.to(device=dev, dtype=torch.float32))
+                                             ops._idx(items, dev), labels.to(device=dev, dtype=torch.float32), *self._gather_arg())
         light_out = self._light_out()
         n_u = self.num_users + 1
         if flag == 1:

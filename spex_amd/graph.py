@@ -137,6 +137,30 @@ def _bump(*tensors):
         torch._C._increment_version(ts)      # takes an ITERABLE of tensors (a bare tensor would be iterated row by row)
 
 
+def _gather_bf16(gather_dtype):
+    """The `gather_dtype` argument of propagate / propagate_bwd: False for None / torch.float32, True for torch.bfloat16."""
+    if gather_dtype is None or gather_dtype == torch.float32:
+        return False
+    if gather_dtype == torch.bfloat16:
+        return True
+    raise ValueError(f"gather_dtype must be None, torch.float32 or torch.bfloat16 (got {gather_dtype!r})")
+
+
+def cast_bf16(X, out=None):
+    """X.to(torch.bfloat16) (round to nearest even) by the library's streaming kernel: the first gather table of the bf16
+    propagation.  See spex_cast_bf16_f32."""
+    if not (X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()):
+        raise ValueError("cast_bf16: need a contiguous fp32 tensor on the GPU")
+    if out is None:
+        out = torch.empty(X.shape, dtype=torch.bfloat16, device=X.device)
+    if not (out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape == X.shape and out.device == X.device):
+        raise ValueError("cast_bf16: out must be a contiguous bf16 tensor of X's shape on X's device")
+    if X.numel():
+        _launch(_device_of(X.device), "spex_cast_bf16_f32", _ptr(X), _ptr(out), X.numel())
+        _bump(out)
+    return out
+
+
 class SpexGraph:
     """A CSR matrix (or a row block of one) resident in HBM.  Stands where the reference keeps its
     torch.sparse.FloatTensor `Graph` (dataloader.py:221-222; model.py:38)."""
@@ -240,8 +264,16 @@ class SpexGraph:
             t = cache[key] = torch.empty(shape, dtype=torch.float32, device=self.device)
         return t
 
+    def _scratch16(self, key, shape):
+        """`_scratch` for the bf16 gather tables of the mixed-precision propagation."""
+        cache = self.__dict__.setdefault("_scratch_cache", {})
+        t = cache.get(key)
+        if t is None or t.shape != shape:
+            t = cache[key] = torch.empty(shape, dtype=torch.bfloat16, device=self.device)
+        return t
+
     def release_workspace(self):
-        """Drop the cached propagate / propagate_bwd workspaces (up to five [N, d] tables per handle)."""
+        """Drop the cached propagate / propagate_bwd workspaces (up to five [N, d] tables per handle, and the bf16 ones)."""
         self.__dict__.pop("_scratch_cache", None)
 
     # -- kernels
@@ -269,6 +301,37 @@ class SpexGraph:
             _bump(Y, acc_out)
         return Y if Y is not None else acc_out
 
+    def _chk16(self, t, rows, d, name):
+        if t is None:
+            return
+        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()):
+            raise ValueError(f"{name}: need a contiguous bf16 tensor on the GPU")
+        if t.device != self.device:
+            raise ValueError(f"{name}: tensor on {t.device}, graph on {self.device}")
+        if t.shape != (rows, d):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != {(rows, d)}")
+
+    def _chk_ws16(self, ws, n, d):
+        if not (ws.is_cuda and ws.dtype == torch.bfloat16 and ws.is_contiguous() and ws.device == self.device and ws.numel() >= 2 * n * d):
+            raise ValueError(f"ws: need a contiguous bf16 tensor of at least 2 x {n} x {d} elements on {self.device}")
+
+    def spmm_bf16(self, X16, Y=None, Y16=None, add_in=None, add_div=1.0, acc_in=None, acc_out=None, acc_div=1.0):
+        """spmm() gathering from the bf16 table X16 (d == 64), all arithmetic fp32: Y = y (fp32), Y16 = bf16(y) — the next
+        layer's gather source —, acc_out = (acc_in + y)/acc_div, any subset (none given: Y is allocated).  Bit-identical to
+        spmm(X16.float(), ...) on every row of at most 1 024 entries.  See spex_spmm_bf16_f32."""
+        d = X16.shape[1]
+        self._chk16(X16, self.n_cols, d, "X16")
+        if Y is None and Y16 is None and acc_out is None:
+            Y = torch.empty((self.n_rows, d), dtype=torch.float32, device=X16.device)
+        for t, nm in ((Y, "Y"), (add_in, "add_in"), (acc_in, "acc_in"), (acc_out, "acc_out")):
+            self._chk(t, self.n_rows, d, nm)
+        self._chk16(Y16, self.n_rows, d, "Y16")
+        if self.n_rows > 0:     # (an empty tensor has a NULL data_ptr; nothing to launch anyway)
+            _launch(self.device, "spex_spmm_bf16_f32", self._h, _ptr(X16), _ptr(Y), _ptr(Y16), _ptr(add_in), float(add_div),
+                    _ptr(acc_in), _ptr(acc_out), float(acc_div), d)
+            _bump(Y, Y16, acc_out)
+        return Y if Y is not None else (acc_out if acc_out is not None else Y16)
+
     def spmm_rows(self, X, idx_a, idx_b=None, off_a=0, off_b=0, Y=None, acc_in=None, acc_out=None, acc_div=1.0):
         """The product for the listed rows only (idx_a + off_a, idx_b + off_b; device int64), other rows of Y / acc_out
         untouched.  d = 64, 128 or 256, no edge dropout.  See spex_spmm_rowlist_f32."""
@@ -284,24 +347,49 @@ class SpexGraph:
         _bump(Y, acc_out)
         return Y if Y is not None else acc_out
 
-    def propagate(self, E0, n_layers, mean_out=None, layers_out=None, ws=None):
-        """LightGCN.computer() (model.py:66-97) on a whole graph: returns mean(E0..EL)."""
+    def propagate(self, E0, n_layers, mean_out=None, layers_out=None, ws=None, gather_dtype=None):
+        """LightGCN.computer() (model.py:66-97) on a whole graph: returns mean(E0..EL).
+        gather_dtype: None / torch.float32 — every layer gathers fp32 rows; torch.bfloat16 (d == 64) — the layers gather from
+        bf16 roundings of E0 and of each layer's output while the layer sum stays exact fp32 (spex_propagate_bf16_f32; `ws`, if
+        given, is then a bf16 [2, N, d] tensor, and layers_out is not available)."""
         n, d = E0.shape
         self._chk(E0, self.n_cols, d, "E0")
         if mean_out is None:
             mean_out = torch.empty_like(E0)
+        if _gather_bf16(gather_dtype):
+            if layers_out is not None:
+                raise ValueError("propagate: layers_out is not available with gather_dtype=torch.bfloat16")
+            self._chk(mean_out, self.n_rows, d, "mean_out")
+            if ws is None:
+                ws = self._scratch16("fwd16", (2, n, d))
+            self._chk_ws16(ws, n, d)
+            if n > 0:     # (an empty tensor has a NULL data_ptr; nothing to launch anyway)
+                _launch(self.device, "spex_propagate_bf16_f32", self._h, _ptr(E0), _ptr(mean_out), _ptr(ws), int(n_layers), d)
+                _bump(mean_out)
+            return mean_out
         if layers_out is None and ws is None and n_layers > 1:
             ws = self._scratch("fwd", (2, n, d), E0.device)
         _launch(self.device, "spex_propagate_f32", self._h, _ptr(E0), _ptr(mean_out), _ptr(layers_out), _ptr(ws), int(n_layers), d)
         _bump(mean_out, layers_out)
         return mean_out
 
-    def propagate_bwd(self, g_out, n_layers, grad_E0=None, ws=None):
-        """Gradient of propagate() w.r.t. E0; `self` must be the handle of A^T."""
+    def propagate_bwd(self, g_out, n_layers, grad_E0=None, ws=None, gather_dtype=None):
+        """Gradient of propagate() w.r.t. E0; `self` must be the handle of A^T.  gather_dtype=torch.bfloat16: the straight-through
+        backward of the bf16 propagation (spex_propagate_bwd_bf16_f32; `ws`, if given, is then a bf16 [2, N, d] tensor)."""
         n, d = g_out.shape
         self._chk(g_out, self.n_rows, d, "g_out")
         if grad_E0 is None:
             grad_E0 = torch.empty_like(g_out)
+        if _gather_bf16(gather_dtype):
+            self._chk(grad_E0, self.n_rows, d, "grad_E0")
+            if ws is None:
+                ws = self._scratch16("bwd16", (2, n, d))
+            self._chk_ws16(ws, n, d)
+            gs = self._scratch("bwd16_gs", (n, d), g_out.device)
+            if n > 0:
+                _launch(self.device, "spex_propagate_bwd_bf16_f32", self._h, _ptr(g_out), _ptr(grad_E0), _ptr(gs), _ptr(ws), int(n_layers), d)
+                _bump(grad_E0)
+            return grad_E0
         if ws is None:
             ws = self._scratch("bwd", (3, n, d), g_out.device)
         _launch(self.device, "spex_propagate_bwd_f32", self._h, _ptr(g_out), _ptr(grad_E0), _ptr(ws), int(n_layers), d)

@@ -798,19 +798,21 @@ class PropagateMean(torch.autograd.Function):
 
     graph / graph_t: SpexGraph of A and of A^T (the same object for the symmetric LightGCN adjacency without dropout).
     mask: None or (mode, keep_tensor, keep_prob, seed) applied identically in forward and backward.
+    gather_dtype (optional, trailing): None / torch.float32, or torch.bfloat16 — bf16 gather tables in forward and (straight
+    through) backward, SpexGraph.propagate(..., gather_dtype=...).
     """
 
     @staticmethod
-    def forward(ctx, user_w, item_w, graph, graph_t, n_layers, mask):
+    def forward(ctx, user_w, item_w, graph, graph_t, n_layers, mask, gather_dtype=None):
         E0 = _flat_tables(user_w, item_w)
         if mask is not None:
             graph.set_edge_mask(*mask)
         try:
-            out = graph.propagate(E0, n_layers)
+            out = graph.propagate(E0, n_layers, gather_dtype=gather_dtype)
         finally:
             if mask is not None:
                 graph.set_edge_mask(0)
-        ctx.graph_t, ctx.n_layers, ctx.mask, ctx.n_user_rows = graph_t, n_layers, mask, user_w.shape[0]
+        ctx.graph_t, ctx.n_layers, ctx.mask, ctx.n_user_rows, ctx.gather_dtype = graph_t, n_layers, mask, user_w.shape[0], gather_dtype
         return out
 
     @staticmethod
@@ -820,12 +822,12 @@ class PropagateMean(torch.autograd.Function):
         if ctx.mask is not None:
             gt.set_edge_mask(*ctx.mask)
         try:
-            gE0 = gt.propagate_bwd(g_out, ctx.n_layers)
+            gE0 = gt.propagate_bwd(g_out, ctx.n_layers, gather_dtype=ctx.gather_dtype)
         finally:
             if ctx.mask is not None:
                 gt.set_edge_mask(0)
         u = ctx.n_user_rows
-        return gE0[:u], gE0[u:], None, None, None, None
+        return gE0[:u], gE0[u:], None, None, None, None, None
 
 
 class PropagateMeanFolds(torch.autograd.Function):
@@ -918,12 +920,12 @@ class LightGCNBCELoss(torch.autograd.Function):
     step is host-bound under the reference's driver loop)."""
 
     @staticmethod
-    def forward(ctx, user_w, item_w, graph, graph_t, n_layers, mask, u_idx, i_idx, labels):
+    def forward(ctx, user_w, item_w, graph, graph_t, n_layers, mask, u_idx, i_idx, labels, gather_dtype=None):
         E0 = _flat_tables(user_w, item_w)
         if mask is not None:
             graph.set_edge_mask(*mask)
         try:
-            light_out = graph.propagate(E0, n_layers)
+            light_out = graph.propagate(E0, n_layers, gather_dtype=gather_dtype)
         finally:
             if mask is not None:
                 graph.set_edge_mask(0)
@@ -931,7 +933,7 @@ class LightGCNBCELoss(torch.autograd.Function):
         B = u_idx.numel()
         need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         loss_sum, grad = _score_bce_table_grad(light_out, n_u, u_idx, i_idx, labels, need)
-        ctx.grad, ctx.graph_t, ctx.n_layers, ctx.mask, ctx.n_user_rows = grad, graph_t, n_layers, mask, n_u
+        ctx.grad, ctx.graph_t, ctx.n_layers, ctx.mask, ctx.n_user_rows, ctx.gather_dtype = grad, graph_t, n_layers, mask, n_u, gather_dtype
         return (loss_sum / B).reshape(())
 
     @staticmethod
@@ -941,13 +943,13 @@ class LightGCNBCELoss(torch.autograd.Function):
         if ctx.mask is not None:
             gt.set_edge_mask(*ctx.mask)
         try:
-            gE0 = gt.propagate_bwd(grad, ctx.n_layers)      # linear in `grad`: the upstream scalar is applied after
+            gE0 = gt.propagate_bwd(grad, ctx.n_layers, gather_dtype=ctx.gather_dtype)      # linear in `grad`: the upstream scalar is applied after
         finally:
             if ctx.mask is not None:
                 gt.set_edge_mask(0)
         gE0 = gE0 * g
         u = ctx.n_user_rows
-        return gE0[:u], gE0[u:], None, None, None, None, None, None, None
+        return gE0[:u], gE0[u:], None, None, None, None, None, None, None, None
 
 
 class BPRLoss(torch.autograd.Function):
