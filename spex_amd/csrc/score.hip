@@ -211,17 +211,18 @@ __device__ __forceinline__ void group_loss_add(float wave_partial, float *loss_s
 }
 template <bool SNAP>
 __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
-    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, const float *__restrict__ Xg,
+    // The head of Phase A's dependent chain — the triples' indices, their bounds, the row pointers — comes FIRST, 14 dwords: this file
+    // is compiled with kernel-argument preloading (csrc/Makefile), which hands a wave its leading arguments in user SGPRs, as many as
+    // fit beside the kernarg pointer.  The arguments behind them arrive by one scalar trip under the index loads.
+    const int64_t *__restrict__ u_idx, const int64_t *__restrict__ p_idx, const int64_t *__restrict__ n_idx, const int32_t *__restrict__ rowptr,
+    int64_t T, int64_t n_user_rows, int64_t n_item_rows,
+    const int32_t *__restrict__ col, const float *__restrict__ val, const float *__restrict__ Xg,
     const float *__restrict__ ts, const float *__restrict__ t0, const float *__restrict__ t1, float div, float *table_w,
-    const int64_t *__restrict__ u_idx, const int64_t *__restrict__ p_idx, const int64_t *__restrict__ n_idx, int64_t T,
-    int64_t n_user_rows, int64_t n_item_rows, float a_coef, float b_coef, float *loss_sum, unsigned long long *loss_cells)
+    float a_coef, float b_coef, float *loss_sum, unsigned long long *loss_cells)
 {
     __shared__ float s_seg[kFuseSegs][kWave];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // (every kernel argument Phase A reads, requested in ONE scalar trip instead of where each is first used)
-    asm volatile("" ::"s"(T), "s"(n_user_rows), "s"(n_item_rows), "s"(u_idx), "s"(p_idx), "s"(n_idx), "s"(rowptr), "s"(col), "s"(val), "s"(Xg),
-                 "s"(ts), "s"(t0), "s"(t1));
     const int64_t t_first = (int64_t)blockIdx.x * kFuseTriples;
     int my_row = -1, my_beg = 0, my_deg = 0;
     if (lane < kFuseRows) {
@@ -237,6 +238,9 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
             }
         }
     }
+    // (the arguments that are not preloaded, in ONE scalar trip instead of where each is first used — asked for at the top of the
+    // kernel, waited for here, behind the two vector round trips above)
+    asm volatile("" ::"s"(col), "s"(val), "s"(Xg), "s"(ts), "s"(t0), "s"(t1));
     int my_nseg = (my_deg + kTaskEntries - 1) / kTaskEntries;
     if (my_nseg > kWgWaves) my_nseg = kWgWaves;        // (never on a graph the step sends here; keeps s_seg's bound local)
     int my_pre = 0;                                    // lane j: segments of the rows in front of row j; lane 12: all of them
@@ -875,13 +879,13 @@ int spex::bpr_sgd_fused_last(const spex_graph_t *g, const float *Xg, const float
         if (rc) return rc;
     }
     if (snap)
-        hipLaunchKernelGGL(bpr_fused_last_kernel<true>, dim3((unsigned)blocks), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, g->rowptr, g->col,
-                           g->val, Xg, snap, t0, t1, div, table_w, u, i_pos, i_neg, T, n_user_rows, n_item_rows, -lr / (float)T, -lr * reg / (float)T,
-                           loss_sum, g->loss_cell);
+        hipLaunchKernelGGL(bpr_fused_last_kernel<true>, dim3((unsigned)blocks), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, u, i_pos, i_neg,
+                           g->rowptr, T, n_user_rows, n_item_rows, g->col, g->val, Xg, snap, t0, t1, div, table_w, -lr / (float)T,
+                           -lr * reg / (float)T, loss_sum, g->loss_cell);
     else
-        hipLaunchKernelGGL(bpr_fused_last_kernel<false>, dim3((unsigned)blocks), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, g->rowptr, g->col,
-                           g->val, Xg, snap, t0, t1, div, table_w, u, i_pos, i_neg, T, n_user_rows, n_item_rows, -lr / (float)T, -lr * reg / (float)T,
-                           loss_sum, g->loss_cell);
+        hipLaunchKernelGGL(bpr_fused_last_kernel<false>, dim3((unsigned)blocks), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, u, i_pos, i_neg,
+                           g->rowptr, T, n_user_rows, n_item_rows, g->col, g->val, Xg, snap, t0, t1, div, table_w, -lr / (float)T,
+                           -lr * reg / (float)T, loss_sum, g->loss_cell);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

@@ -313,12 +313,18 @@ __device__ __forceinline__ void snapshot_rows(const SnapArgs &s, const float *__
 // FOLD instantiation only on a graph that HAS hubs — where it replaces a ~5 us dependent fix-up launch per product.
 template <int EPI, bool MASKED, bool ROWIDS, bool FOLD>
 __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
-    const float *__restrict__ X, const uint32_t *__restrict__ chunk_off, const float *__restrict__ chunk_val,
-    const uint32_t *__restrict__ chunk_mask, const int32_t *__restrict__ chunk_row, const int4 *__restrict__ task,
-    int n_tasks, float *__restrict__ Y,
+    // What the prologue reads comes FIRST, 14 dwords of it: this file is compiled with kernel-argument preloading (Makefile), which
+    // hands a wave the leading arguments in user SGPRs — as many as fit beside the kernarg pointer, 14 — so the prologue's first
+    // vector loads wait on no scalar trip at all.  (table_wgs is SnapArgs' field of the same name, out here because a struct
+    // argument ends the preloaded run.)  Where the firmware does not preload, the compiler's compatibility prologue loads the same
+    // registers in one trip: the form before.
+    const uint32_t *__restrict__ chunk_off, const float *__restrict__ chunk_val, const int32_t *__restrict__ chunk_row,
+    const uint32_t *__restrict__ chunk_mask, const int4 *__restrict__ task, const int n_tasks, const int xcd_contiguous,
+    const int chunk_stride, const int table_wgs,
+    const float *__restrict__ X, float *__restrict__ Y,
     const float *epi_in, float epi_div, float out_div, float *acc_out,   // may alias each other (running sum in place): no __restrict__
     float *__restrict__ partial,
-    const DropArgs drop, const int xcd_contiguous, const HubFold hf_args, const SnapArgs snap, const int chunk_stride)
+    const DropArgs drop, const HubFold hf_args, const SnapArgs snap)
 {
     __shared__ float s_part[kWgWaves][kWave];  // segment sums of the rows this workgroup combines
     const int lane = threadIdx.x & (kWave - 1);
@@ -326,13 +332,13 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
     // Every kernel argument the prologue reads, requested in ONE scalar trip: left to itself the compiler loads them where they are
     // first used — behind the tail test, behind the XCD remap, behind the bounds test: three dependent waits in front of the first
     // vector load.
-    asm volatile("" ::"s"(n_tasks), "s"(xcd_contiguous), "s"(chunk_stride), "s"(snap.table_wgs), "s"(chunk_off), "s"(chunk_val), "s"(chunk_row),
+    asm volatile("" ::"s"(n_tasks), "s"(xcd_contiguous), "s"(chunk_stride), "s"(table_wgs), "s"(chunk_off), "s"(chunk_val), "s"(chunk_row),
                  "s"(chunk_mask), "s"(task));
     // The unmasked plain form may carry a snapshot tail (SnapArgs): whole workgroups behind the table's, decided once, here, on
     // scalar values; they touch neither s_part nor the hub tickets.  Only these instantiations read `snap`.
     constexpr bool kTail = EPI == 0 && !MASKED && FOLD;
-    if (kTail && (int)blockIdx.x >= snap.table_wgs) {
-        const int64_t slot0 = ((int64_t)((int)blockIdx.x - snap.table_wgs) * kWgWaves + wave) * kWave;
+    if (kTail && (int)blockIdx.x >= table_wgs) {
+        const int64_t slot0 = ((int64_t)((int)blockIdx.x - table_wgs) * kWgWaves + wave) * kWave;
         if (slot0 < 3 * snap.T) snapshot_rows(snap, X, slot0, lane);
         return;
     }
@@ -341,7 +347,7 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
     // all the heavy workgroups).  A graph whose whole source table sits in cache instead prefers each XCD to walk a
     // contiguous range of workgroups (user rows and item rows of the bipartite graph then gather from different
     // halves of the table in different L2s: 76 % vs 71 % L2 hits on Epinion2).  Placement is a speed matter only.
-    const int n_wg = kTail ? snap.table_wgs : (int)gridDim.x;       // (the table's workgroups: a tail does not move them)
+    const int n_wg = kTail ? table_wgs : (int)gridDim.x;       // (the table's workgroups: a tail does not move them)
     const int wg = xcd_contiguous ? xcd_contiguous_block(blockIdx.x, n_wg) : (int)blockIdx.x;
     const int tid = wg * kWgWaves + wave;
     if (tid >= n_tasks) return;  // whole workgroups only (n_tasks is a multiple of kWgWaves)
@@ -987,13 +993,15 @@ void launch_chunk_v(bool masked, bool row_ids, dim3 grid, dim3 block, hipStream_
 #define SPEX_GO(M, R)                                                                                                  \
     do {                                                                                                               \
         if (V == 1 && (!M || hub.tag != 0u))                                                                           \
-            hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, true>), grid, block, 0, stream, X, g->chunk_off,          \
-                               g->chunk_val, g->chunk_mask, g->chunk_row, g->task, g->n_tasks, Y, epi_in, epi_div,     \
-                               out_div, acc_out, g->partial, da, xcd_contig, hub, snap, g->chunk_stride);              \
+            hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, true>), grid, block, 0, stream, g->chunk_off,             \
+                               g->chunk_val, g->chunk_row, g->chunk_mask, g->task, g->n_tasks, xcd_contig,             \
+                               g->chunk_stride, snap.table_wgs, X, Y, epi_in, epi_div, out_div, acc_out, g->partial,   \
+                               da, hub, snap);                                                                         \
         else if (V == 1)                                                                                               \
-            hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, !M>), grid, block, 0, stream, X, g->chunk_off,            \
-                               g->chunk_val, g->chunk_mask, g->chunk_row, g->task, g->n_tasks, Y, epi_in, epi_div,     \
-                               out_div, acc_out, g->partial, da, xcd_contig, hub, snap, g->chunk_stride);              \
+            hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, !M>), grid, block, 0, stream, g->chunk_off,               \
+                               g->chunk_val, g->chunk_row, g->chunk_mask, g->task, g->n_tasks, xcd_contig,             \
+                               g->chunk_stride, snap.table_wgs, X, Y, epi_in, epi_div, out_div, acc_out, g->partial,   \
+                               da, hub, snap);                                                                         \
         else                                                                                                           \
             hipLaunchKernelGGL((spmm_chunk_wide_kernel<EPI, M, R, (V == 1 ? 2 : V)>), grid, block, 0, stream, X,       \
                                g->chunk_off, g->chunk_val, g->chunk_mask, g->chunk_row, g->task, g->n_tasks, Y, epi_in, \

@@ -6,6 +6,11 @@
 //   K2  lane == column, v_readlane pre-scaled byte offset -> buffer_load_dword soffset      (no scalar address math)
 //   K3  as K2 but indices / values come in by wave-uniform (scalar) loads, 16 at a time
 //   K4  16 lanes x float4 per row, 4 rows per wave instruction, per-group index stream      (what spmm v3 does)
+//   K12 K1, but the blocks of XCD x (blockIdx & 7 == x: blocks are dealt round-robin) gather only from eighth x of the
+//       table: no line is filled into more than one L2 — the ceiling of any placement
+//   K13 K1, but the blocks of XCDs 0-3 gather from rows [3 186, n) and those of XCDs 4-7 from rows [0, 3 186): the
+//       footprint of Epinion2's bipartite adjacency when each side's rows have four XCDs to themselves
+//   (K12 / K13 run on the 4 MB table only: they are about the per-XCD fill of a cache-resident table)
 //
 // build: hipcc -O3 --offload-arch=gfx950 tools/gather_bench.hip -o gather_bench ; run: ./gather_bench
 #include <hip/hip_runtime.h>
@@ -281,6 +286,36 @@ int main(int argc, char **argv)
             printf("  K%d%s  %9.1f us   %7.0f GB/s (264 B/gather)   %6.2f G gathers/s   check %.1f\n", k,
                    k == 4 ? "(x4,4 in flight)" : k == 5 ? "(x4,8)" : k == 6 ? "(x4,16)" : k == 7 ? "(K1, 32 in flight)" : k == 8 ? "(K1, 64 in flight)" : k == 9 ? "(K1, 8 in flight)" : k == 10 ? "(K1, 1024-thread blocks)" : k == 11 ? "(K1 behind a descriptor load)" : "", best * 1e3, gb / (best * 1e-3),
                    n_idx / (best * 1e-3) / 1e9, hy[0]);
+        }
+        // K12 / K13: K1 over index lists whose range depends on the block's XCD (blockIdx & 7)
+        for (int k = 12; k <= 13 && c.rows == 15593; ++k) {
+            const size_t split = 3186;
+            uint64_t s2 = 0x9E3779B97F4A7C15ull;
+            for (size_t i = 0; i < n_idx; ++i) {
+                s2 ^= s2 << 13; s2 ^= s2 >> 7; s2 ^= s2 << 17;
+                const size_t xcd = (i / ((size_t)per_wave * 4)) & 7;       // 4 waves per block
+                size_t lo, hi;
+                if (k == 12) { lo = c.rows * xcd / 8; hi = c.rows * (xcd + 1) / 8; }
+                else if (xcd < 4) { lo = split; hi = c.rows; }
+                else { lo = 0; hi = split; }
+                h[i] = (int)(lo + s2 % (hi - lo));
+            }
+            CK(hipMemcpy(idx, h.data(), n_idx * 4, hipMemcpyHostToDevice));
+            float best = 1e30f;
+            for (int rep = 0; rep < 6; ++rep) {
+                CK(hipEventRecord(e0));
+                hipLaunchKernelGGL(k1, grid, block, 0, 0, X, idx, val, Y, per_wave);
+                CK(hipEventRecord(e1));
+                CK(hipEventSynchronize(e1));
+                float ms;
+                CK(hipEventElapsedTime(&ms, e0, e1));
+                if (rep > 0 && ms < best) best = ms;
+            }
+            std::vector<float> hy(64);
+            CK(hipMemcpy(hy.data(), Y, 256, hipMemcpyDeviceToHost));
+            printf("  K%d%s  %9.1f us   %7.0f GB/s (264 B/gather)   %6.2f G gathers/s   check %.1f\n", k,
+                   k == 12 ? "(K1, XCD x gathers eighth x of the table)" : "(K1, XCDs 0-3 gather rows >= 3186, XCDs 4-7 rows < 3186)", best * 1e3,
+                   (double)n_idx * 264.0 / 1e9 / (best * 1e-3), n_idx / (best * 1e-3) / 1e9, hy[0]);
         }
         CK(hipFree(desc));
         CK(hipFree(X)); CK(hipFree(Y)); CK(hipFree(val)); CK(hipFree(idx)); CK(hipFree(off));
