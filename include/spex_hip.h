@@ -917,10 +917,12 @@ enum {
     SPEX_STEP_BPR_DENSE = 8,            /* exact BPR step only: force the dense form of the fast path (gradient rows into g_out, all-pull
                                          * backward) ... */
     SPEX_STEP_BPR_PUSH = 16,            /* ... or the push form, whatever T; neither flag: chosen by T (see spex_lightgcn_step_bpr_adam_f32) */
-    SPEX_STEP_WIDE = 32                 /* exact BPR step only: this descriptor's tables and slots are d wide with d = 128 or 256.  The BCE step
+    SPEX_STEP_WIDE = 32,                /* exact BPR step only: this descriptor's tables and slots are d wide with d = 128 or 256.  The BCE step
                                          * needs no such flag (it took the three widths from its first version); the BPR entry point promised
                                          * d == 64 ONLY and rejects a descriptor whose d says otherwise — callers rely on that rejection for a
                                          * 64-wide descriptor with a wrong d, which would gather out of bounds — so a wider d is an opt-in */
+    SPEX_STEP_BF16_GATHER = 64          /* the one-call LightGCN steps (BCE, exact BPR) and every epoch over them: bf16 gather tables, d == 64
+                                         * and L = 2 or 3 only; the descriptor's E0_16 / ws16 fields are read (see spex_lightgcn_step_t) */
 };
 /* The north-star step — LightGCN L-layer propagation + the fused BPR gather + dot + sigmoid + SGD kernel over T triples — as one
  * call of at most L + 1 launches: EVERY whole-graph layer in the plain form (no epilogue operand, one output stream); the layer-1 launch also sets
@@ -946,6 +948,30 @@ int spex_lightgcn_step_bpr_f32(const spex_graph_t *g, float *E0, float *sum1, fl
                                const int64_t *u, const int64_t *i_pos, const int64_t *i_neg, int64_t T, float lr, float reg,
                                float *loss_sum, void *stream);
 
+/* The four d == 64 batch-sized middles with a bf16 gather source (SPEX_STEP_BF16_GATHER's launches): the arguments of
+ * spex_lightgcn_batch_f32, spex_lightgcn_batch_slots_f32, spex_lightgcn_bpr_batch_f32 and spex_lightgcn_bpr_batch_slots_f32 with
+ * X16 ([N, 64] bf16, rows of 128 bytes) for X.  Only the last layer's gather reads X16, widened exactly; acc_in, every sum, the
+ * scores, the loss, the gradient rows, the L2 counts and the push (fp32 slots) are the fp32 kernel's statements: on
+ * Xw = float(X16) a call returns what its fp32 sibling returns on Xw (slots forms: bit for bit; push forms: up to the order of
+ * the float atomics), and a forward row of at most 1 024 entries is spex_spmm_bf16_f32's row bit for bit, under an edge mask too.
+ * d != 64: SPEX_ERR_UNSUPPORTED. */
+int spex_lightgcn_batch_bf16_f32(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, float acc_div, const int64_t *users,
+                                 const int64_t *items, const float *labels, int32_t B, int32_t n_user_rows, float grad_scale,
+                                 float push_scale, float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d,
+                                 void *stream);
+int spex_lightgcn_batch_slots_bf16_f32(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, float acc_div,
+                                       const int64_t *users, const int64_t *items, const float *labels, int32_t B, int32_t n_user_rows,
+                                       float grad_scale, float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d,
+                                       void *stream);
+int spex_lightgcn_bpr_batch_bf16_f32(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, float acc_div, const int64_t *users,
+                                     const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows, float grad_scale,
+                                     float push_scale, float weight_decay, const float *E0, int32_t *row_counts, float *loss_sum,
+                                     float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream);
+int spex_lightgcn_bpr_batch_slots_bf16_f32(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, float acc_div,
+                                           const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows,
+                                           float grad_scale, float weight_decay, const float *E0, int32_t *row_counts, float *loss_sum,
+                                           float *loss_per_sample, float *grad_slots, int32_t d, void *stream);
+
 typedef struct spex_lightgcn_step {
     const spex_graph_t *graph, *graph_t;     /* A and A^T (the same handle for the symmetric LightGCN adjacency) */
     float *E0, *m, *v;
@@ -953,13 +979,38 @@ typedef struct spex_lightgcn_step {
     int32_t slot_capacity, n_user_rows, L, d;
     float lr, beta1, beta2, eps;
     int32_t t;
-    int32_t flags;                           /* SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE / _PUSH, SPEX_STEP_WIDE */
+    int32_t flags;                           /* SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE / _PUSH, SPEX_STEP_WIDE, SPEX_STEP_BF16_GATHER */
     /* appended for spex_lightgcn_step_bpr_adam_f32 / spex_lightgcn_epoch_bpr_f32 (the BCE entry points never read them): */
     float weight_decay;                      /* >= 0: upstream LightGCN's L2 term on the E0 rows of the batch */
     int32_t *row_counts;                     /* [2, N] int32, all-zero before the first call: per-row occurrence counts, by step parity.
                                               * Only spex_lightgcn_step_bpr_adam_f32 (and the epochs over it) keeps the tables: a caller
                                               * that advances t by ANY other call must clear both before the next BPR step */
+    /* appended for SPEX_STEP_BF16_GATHER (without the flag no entry point reads them): */
+    uint16_t *E0_16;                         /* [N, 64] bf16: the shadow of E0.  Contract: E0_16 == bf16(E0) (spex_cast_bf16_f32) on entry;
+                                              * every call leaves it so */
+    uint16_t *ws16;                          /* [2, N, 64] bf16: the later layers' gather tables, then the backward's */
 } spex_lightgcn_step_t;
+/* flags & SPEX_STEP_BF16_GATHER — the mixed-precision mode of spex_propagate_bf16_f32 carried through the one-call steps, d == 64,
+ * L = 2 or 3 (spex_lightgcn_step_bce_f32, spex_lightgcn_step_bpr_adam_f32 and, through them, every epoch, sampled-epoch and
+ * train_*_sampled call).  Rounding enters only where a table becomes a gather source; every product, sum and the layer mean stay
+ * fp32, and the backward is straight-through, as in spex_propagate_bwd_bf16_f32.
+ *   forward:   y_1 = A E0_16 (spex_spmm_bf16_f32: fp32 Y into ws_fwd[0], Y16 = bf16(y_1) into ws16[0] from the same register);
+ *              L == 3: y_2 = A bf16(y_1) into ws_fwd[1] and ws16[1].  The batch kernel (spex_lightgcn_batch_bf16_f32 and its three
+ *              siblings) gathers the last layer at the batch's rows from bf16(y_(L-1)) and forms
+ *              light_r = (((E0[r] + y_1[r]) (+ y_2[r])) + y_L[r]) / (L + 1) with the exact fp32 E0 — spex_propagate_bf16_f32's mean_out
+ *              rows; scores, loss, gradient rows, L2 counts and the push are the fp32 kernel's statements on fp32 slots.
+ *   backward, push form: P = (g + A^T g) / (L + 1) arrives in fp32 as without the flag; one spex_cast_bf16_f32 launch makes it a
+ *              gather source in ws16[0] (the forward's bf16 tables are dead by then).  L == 3: G16 = bf16(A^T bf16(P)) (bf16 output
+ *              only, ws16[1]), grad_E0 = A^T G16, and the Adam pass adds P.  L == 2: grad_E0 = A^T bf16(P), the Adam pass adds
+ *              g_out / (L + 1).  2 L + 1 launches.
+ *   backward, dense form (BPR, large T) and SPEX_STEP_DETERMINISTIC: spex_propagate_bwd_bf16_f32(graph_t, g_out, grad_E0, ws_bwd,
+ *              ws16, L, 64) in place of spex_propagate_bwd_f32; the same buffers are left all-zero for the next step.
+ *   Adam:      writes the new E0 and E0_16 = bf16(new E0), round to nearest even, from the same register: after every step E0_16
+ *              equals spex_cast_bf16_f32(E0) bit for bit, and no cast launch opens a step.
+ *   Edge dropout: the handles' mask, in the whole-graph launches (spex_spmm_bf16_f32) and entry by entry in the batch kernels.
+ * Refused before anything touches the device (t is not advanced): any other d or L, or a handle without chunk tables ->
+ * SPEX_ERR_UNSUPPORTED; E0_16 or ws16 NULL, not 16-byte aligned, or overlapping each other or another buffer of the descriptor, and
+ * SPEX_STEP_WIDE together with the flag -> SPEX_ERR_INVALID.  A caller that writes E0 itself re-casts it (spex_cast_bf16_f32) first. */
 /* (On a descriptor shared with the exact BPR step: this call advances t and leaves row_counts alone.  The BPR step counts into the
  * table of its own t's parity and relies on the step before it to have cleared that table, so clear both tables — one memset of
  * 8 N bytes — between a BPR step and the next one whenever a BCE step, or a BCE epoch, ran in between; an odd number of BCE steps

@@ -83,6 +83,14 @@ SIGNATURES = {
                                                    c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "spex_lightgcn_bpr_batch_slots_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp,
                                                          c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "spex_lightgcn_batch_bf16_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp,
+                                                    c_vp, c_i32, c_vp]),
+    "spex_lightgcn_batch_slots_bf16_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp,
+                                                          c_i32, c_vp]),
+    "spex_lightgcn_bpr_batch_bf16_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp,
+                                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "spex_lightgcn_bpr_batch_slots_bf16_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp,
+                                                              c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "spex_lightgcn_bpr_batch_wide_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp,
                                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "spex_lightgcn_bpr_batch_slots_wide_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp,
@@ -184,7 +192,8 @@ class LightGCNStepDesc(ctypes.Structure):
                                      "grad_E0", "grad_slots")]
                 + [(n, c_i32) for n in ("slot_capacity", "n_user_rows", "L", "d")]
                 + [(n, c_f32) for n in ("lr", "beta1", "beta2", "eps")] + [("t", c_i32), ("flags", c_i32)]
-                + [("weight_decay", c_f32), ("row_counts", c_vp)])      # the exact BPR step's (spex_lightgcn_step_bpr_adam_f32)
+                + [("weight_decay", c_f32), ("row_counts", c_vp)]       # the exact BPR step's (spex_lightgcn_step_bpr_adam_f32)
+                + [("E0_16", c_vp), ("ws16", c_vp)])                    # SPEX_STEP_BF16_GATHER's bf16 tables
 
 
 STEP_DETERMINISTIC = 1          # spex_hip.h: SPEX_STEP_DETERMINISTIC
@@ -193,6 +202,7 @@ STEP_PIPELINED = 4              # spex_hip.h: SPEX_STEP_PIPELINED
 STEP_BPR_DENSE = 8              # spex_hip.h: SPEX_STEP_BPR_DENSE
 STEP_BPR_PUSH = 16              # spex_hip.h: SPEX_STEP_BPR_PUSH
 STEP_WIDE = 32                  # spex_hip.h: SPEX_STEP_WIDE (exact BPR step at d = 128 / 256)
+STEP_BF16_GATHER = 64           # spex_hip.h: SPEX_STEP_BF16_GATHER (bf16 gather tables in the one-call LightGCN steps, d = 64, L = 2 / 3)
 
 
 class NGCFStepDesc(ctypes.Structure):

@@ -27,14 +27,23 @@ __device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, flo
 // L2: the exact BPR step's pass — gradient += l2.scale * l2.count[row] * p[row] (rows of 64 / 128 / 256 parameters: 1 << l2.shift
 // float4 steps, shift = 4 / 5 / 6), the other parity's count table cleared by the thread that holds a row's first columns, and the
 // whole gradient stored to l2.g_store.
-template <bool L2>
-__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *g,
-                                                   float *__restrict__ m, float *__restrict__ v, int64_t n4,
-                                                   int64_t rem, float w1, float beta2, float w2, float bc2_sqrt,
-                                                   float eps, float step_size, float *zero_buf, float *zero_buf2,
-                                                   const float *__restrict__ loss_rows, int n_loss, float *loss_sum,
-                                                   const spex::SmallAdam small, const int main_blocks, const float *add_g,
-                                                   const float add_div, const spex::L2Rows l2)
+// SHADOW (adam_shadow_kernel): p16 also receives bf16(the updated parameter), round to nearest even, from the register that is stored
+// to p — the bf16 gather table of the one-call steps' next forward.  The one body serves both kernels.
+__device__ __forceinline__ uint16_t bf16_rne(float v)       // spmm_bf16.hip's rounding: what spex_cast_bf16_f32 returns
+{
+    const uint32_t u = __float_as_uint(v);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x0040u);
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+template <bool L2, bool SHADOW>
+__device__ __forceinline__ void adam_body(float *__restrict__ p, const float *g,
+                                          float *__restrict__ m, float *__restrict__ v, int64_t n4,
+                                          int64_t rem, float w1, float beta2, float w2, float bc2_sqrt,
+                                          float eps, float step_size, float *zero_buf, float *zero_buf2,
+                                          const float *__restrict__ loss_rows, int n_loss, float *loss_sum,
+                                          const spex::SmallAdam small, const int main_blocks, const float *add_g,
+                                          const float add_div, const spex::L2Rows l2, uint16_t *__restrict__ p16)
 {
     // A second, small parameter block rides in the same launch (the NGCF step's layer weights: 8 320 parameters whose gradient
     // arrives as partial blocks — a launch of their own cost the step ~5 us of ramp for 33 workgroups): the blocks behind the
@@ -92,6 +101,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
         adam1(P.z, G.z, M.z, V.z, w1, beta2, w2, bc2_sqrt, eps, step_size);
         adam1(P.w, G.w, M.w, V.w, w1, beta2, w2, bc2_sqrt, eps, step_size);
         reinterpret_cast<float4 *>(p)[i] = P;
+        if constexpr (SHADOW) {
+            typedef unsigned short h4 __attribute__((ext_vector_type(4)));
+            h4 h;
+            h[0] = bf16_rne(P.x); h[1] = bf16_rne(P.y); h[2] = bf16_rne(P.z); h[3] = bf16_rne(P.w);
+            reinterpret_cast<h4 *>(p16)[i] = h;
+        }
         reinterpret_cast<float4 *>(m)[i] = M;
         reinterpret_cast<float4 *>(v)[i] = V;
         if (zero_buf) reinterpret_cast<float4 *>(zero_buf)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -107,13 +122,43 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
     }
 }
 
+template <bool L2>
+__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *g,
+                                                   float *__restrict__ m, float *__restrict__ v, int64_t n4,
+                                                   int64_t rem, float w1, float beta2, float w2, float bc2_sqrt,
+                                                   float eps, float step_size, float *zero_buf, float *zero_buf2,
+                                                   const float *__restrict__ loss_rows, int n_loss, float *loss_sum,
+                                                   const spex::SmallAdam small, const int main_blocks, const float *add_g,
+                                                   const float add_div, const spex::L2Rows l2)
+{
+    adam_body<L2, false>(p, g, m, v, n4, rem, w1, beta2, w2, bc2_sqrt, eps, step_size, zero_buf, zero_buf2, loss_rows, n_loss, loss_sum, small,
+                         main_blocks, add_g, add_div, l2, nullptr);
+}
+
+// (whole float4s only: the caller passes rem == 0)
+template <bool L2>
+__global__ __launch_bounds__(256) void adam_shadow_kernel(float *__restrict__ p, const float *g,
+                                                          float *__restrict__ m, float *__restrict__ v, int64_t n4,
+                                                          int64_t rem, float w1, float beta2, float w2, float bc2_sqrt,
+                                                          float eps, float step_size, float *zero_buf, float *zero_buf2,
+                                                          const float *__restrict__ loss_rows, int n_loss, float *loss_sum,
+                                                          const spex::SmallAdam small, const int main_blocks, const float *add_g,
+                                                          const float add_div, const spex::L2Rows l2, uint16_t *__restrict__ p16)
+{
+    adam_body<L2, true>(p, g, m, v, n4, rem, w1, beta2, w2, bc2_sqrt, eps, step_size, zero_buf, zero_buf2, loss_rows, n_loss, loss_sum, small,
+                        main_blocks, add_g, add_div, l2, p16);
+}
+
 }  // namespace
 
 // Internal form with a second buffer to clear (the one-call training step keeps its push target all-zero this way).
 int spex::adam_step_z2(float *p, const float *g, float *m, float *v, int64_t n, int32_t t, float lr, float beta1, float beta2,
                        float eps, float *zero_buf, float *zero_buf2, void *stream, const float *loss_rows, int32_t n_loss, float *loss_sum,
-                       const spex::SmallAdam *small_in, const float *add_g, float add_div, const spex::L2Rows *l2_in)
+                       const spex::SmallAdam *small_in, const float *add_g, float add_div, const spex::L2Rows *l2_in, uint16_t *p16)
 {
+    SPEX_CHECK_ARG(!p16 || (n % 4 == 0 && (((uintptr_t)p16) & 7) == 0 && (const void *)p16 != (const void *)p && (const void *)p16 != (const void *)g
+                            && (const void *)p16 != (const void *)m && (const void *)p16 != (const void *)v),
+                   "spex_adam_step_f32: the bf16 output takes whole float4s, an 8-byte aligned buffer, and aliases no other");
     spex::L2Rows l2{};
     if (l2_in) l2 = *l2_in;
     SPEX_CHECK_ARG(!l2_in || (l2.shift >= 4 && l2.shift <= 6 && n % ((int64_t)4 << l2.shift) == 0 && (((uintptr_t)l2.g_store) & 15) == 0
@@ -141,12 +186,17 @@ int spex::adam_step_z2(float *p, const float *g, float *m, float *v, int64_t n, 
     if (blocks < 1) blocks = 1;
     if (blocks > 2048) blocks = 2048;
     const int64_t small_blocks = (small.n + 255) / 256;
-#define SPEX_ADAM_GO(KERNEL)                                                                                                              \
+#define SPEX_ADAM_GO(KERNEL, ...)                                                                                                            \
     hipLaunchKernelGGL(KERNEL, dim3((unsigned)(blocks + small_blocks)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, rem,          \
                        1.0f - beta1, beta2, 1.0f - beta2, bc2_sqrt, eps, step_size, zero_buf, zero_buf2, loss_rows, (int)n_loss, loss_sum, \
-                       small, (int)blocks, add_g, add_div, l2)
-    if (l2_in) SPEX_ADAM_GO(adam_kernel<true>);
-    else SPEX_ADAM_GO(adam_kernel<false>);
+                       small, (int)blocks, add_g, add_div, __VA_ARGS__)
+    if (p16) {
+        if (l2_in) SPEX_ADAM_GO(adam_shadow_kernel<true>, l2, p16);
+        else SPEX_ADAM_GO(adam_shadow_kernel<false>, l2, p16);
+    } else {
+        if (l2_in) SPEX_ADAM_GO(adam_kernel<true>, l2);
+        else SPEX_ADAM_GO(adam_kernel<false>, l2);
+    }
 #undef SPEX_ADAM_GO
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;

@@ -28,9 +28,11 @@ struct L2Rows {             // the exact BPR step's L2 term, applied by its Adam
 int adam_step_z2(float *p, const float *g, float *m, float *v, int64_t n, int32_t t, float lr, float beta1, float beta2, float eps,
                  float *zero_buf, float *zero_buf2, void *stream, const float *loss_rows = nullptr, int32_t n_loss = 0,
                  float *loss_sum = nullptr, const SmallAdam *small = nullptr, const float *add_g = nullptr, float add_div = 1.0f,
-                 const L2Rows *l2 = nullptr);
+                 const L2Rows *l2 = nullptr, uint16_t *p16 = nullptr);
                                                // add_g: gradient = g + add_g / add_div (add_g may be zero_buf: read, then cleared);   // optim.hip: spex_adam_step_f32 with a second buffer to clear and the step's
                                                // per-sample losses to fold into an accumulator
+                                               // p16: also receives bf16(the updated p), round to nearest even, from the same register —
+                                               // the bf16 gather table of the next step; 8-byte aligned, n % 4 == 0
 
 int dual_task_adam(float *p, float *m, float *v, const float *g_E0, float *g_raw, float *g_user, float *g_small, float *g_prop,
                    float *push_zero, float *loss, float *loss_acc, float *prec, int64_t n_table, int64_t n_user, int64_t n_trust,
@@ -63,6 +65,26 @@ int lightgcn_bpr_batch_slots_layers(const spex_graph_t *g, const float *X, const
                                     float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
                                     int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0, int32_t *row_counts,
                                     float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream);
+// batch_bf16.hip: the four d == 64 forms above with the last layer gathered from a bf16 table (X16: rows of 128 bytes); everything
+// else — the layer sum from the fp32 tables, scores, loss, gradient rows, L2 counts, the push into fp32 slots — is the same statement
+int lightgcn_batch_bf16_layers(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, const float *acc2, const float *acc3,
+                               float acc_div, const int64_t *users, const int64_t *items, const float *labels, int32_t B,
+                               int32_t n_user_rows, float grad_scale, float push_scale, float *loss_sum, float *loss_per_sample, float *g_out,
+                               float *G, int32_t d, void *stream);
+int lightgcn_batch_slots_bf16_layers(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, const float *acc2, const float *acc3,
+                                     float acc_div, const int64_t *users, const int64_t *items, const float *labels, int32_t B,
+                                     int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample, float *grad_slots,
+                                     int32_t d, void *stream);
+int lightgcn_bpr_batch_bf16_layers(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, const float *acc2, const float *acc3,
+                                   float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
+                                   int32_t n_user_rows, float grad_scale, float push_scale, float weight_decay, const float *E0,
+                                   int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d,
+                                   void *stream);
+int lightgcn_bpr_batch_slots_bf16_layers(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, const float *acc2,
+                                         const float *acc3, float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg,
+                                         int32_t T, int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0,
+                                         int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d,
+                                         void *stream);
 int gated_batch_fwd_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3, float acc_div,
                            const float *raw, const float *att_u, const float *att_i, const int64_t *users, const int64_t *items,
                            const float *labels, int32_t B, int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample,

@@ -17,6 +17,71 @@ using namespace spex;
         if (rc_ != SPEX_OK) return rc_; \
     } while (0)
 
+// ---- SPEX_STEP_BF16_GATHER (d == 64, L = 2 or 3): the whole-graph launches of the LightGCN steps gather from bf16
+//      tables.  Everything a flagged descriptor must satisfy, checked before anything touches the device.
+static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return b != nullptr && a0 < b0 + (b_bytes ? b_bytes : 1) && b0 < a0 + a_bytes;
+}
+
+static int bf16_step_check(const spex_lightgcn_step_t *s, const char *who)
+{
+    SPEX_CHECK_ARG((s->flags & SPEX_STEP_WIDE) == 0, "%s: SPEX_STEP_BF16_GATHER does not combine with SPEX_STEP_WIDE (bf16 gather tables are d == 64 only)", who);
+    if (s->d != 64 || (s->L != 2 && s->L != 3)) {
+        spex::set_error("%s: SPEX_STEP_BF16_GATHER takes d == 64 and L = 2 or 3 (got d = %d, L = %d): L = 1 has no whole-graph forward launch, "
+                        "L >= 4 runs the fused running-sum schedule — run those without the flag", who, s->d, s->L);
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    const spex_graph *g = s->graph, *gt = s->graph_t;
+    if (g->n_rows > 0 && (g->task == nullptr || gt->task == nullptr)) {
+        spex::set_error("%s: SPEX_STEP_BF16_GATHER: the handle has no chunked task table (its source table exceeds a 32-bit offset): run without the flag", who);
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    SPEX_CHECK_ARG(s->E0_16 && s->ws16, "%s: SPEX_STEP_BF16_GATHER needs E0_16 ([N, 64] bf16) and ws16 ([2, N, 64] bf16): NULL %s", who,
+                   s->E0_16 ? "ws16" : "E0_16");
+    SPEX_CHECK_ARG((((uintptr_t)s->E0_16) & 15) == 0, "%s: E0_16 must be 16-byte aligned", who);
+    SPEX_CHECK_ARG((((uintptr_t)s->ws16) & 15) == 0, "%s: ws16 must be 16-byte aligned", who);
+    const size_t sz = (size_t)g->n_rows * 64, f = sizeof(float), h = sizeof(uint16_t);
+    struct { const void *p; size_t bytes; } other[] = {
+        {s->E0, sz * f}, {s->m, sz * f}, {s->v, sz * f}, {s->light_out, sz * f}, {s->ws_fwd, 2 * sz * f}, {s->lo_batch, 0}, {s->g_out, sz * f},
+        {s->ws_bwd, 3 * sz * f}, {s->grad_E0, sz * f}, {s->grad_slots, (size_t)s->slot_capacity * 64 * f}, {s->row_counts, 2 * (size_t)g->n_rows * sizeof(int32_t)}};
+    for (const auto &o : other) {
+        SPEX_CHECK_ARG(!ranges_overlap(s->E0_16, sz * h, o.p, o.bytes), "%s: E0_16 aliases another buffer of the descriptor", who);
+        SPEX_CHECK_ARG(!ranges_overlap(s->ws16, 2 * sz * h, o.p, o.bytes), "%s: ws16 aliases another buffer of the descriptor", who);
+    }
+    SPEX_CHECK_ARG(!ranges_overlap(s->ws16, 2 * sz * h, s->E0_16, sz * h), "%s: ws16 aliases E0_16", who);
+    return SPEX_OK;
+}
+
+// The step's L - 1 whole-graph forward launches from the shadow: y_l in fp32 into ws_fwd[l - 1] and bf16(y_l) into ws16[l - 1] from
+// the same register.  *last16 = bf16(y_(L-1)), the batch kernel's gather source.
+static int bf16_forward(const spex_lightgcn_step_t *s, size_t sz, const uint16_t **last16, void *stream)
+{
+    const uint16_t *cur = s->E0_16;
+    for (int32_t l = 0; l + 1 < s->L; ++l) {
+        uint16_t *nxt = s->ws16 + (size_t)l * sz;
+        SPEX_TRY(spex_spmm_bf16_f32(s->graph, cur, s->ws_fwd + (size_t)l * sz, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, 64, stream));
+        cur = nxt;
+    }
+    *last16 = cur;
+    return SPEX_OK;
+}
+
+// The push form's pull products from P = (g + A^T g) / (L + 1) (fp32, the push target): one cast makes it a gather source (the
+// forward's bf16 tables are dead: ws16 is reused); L == 3: G16 = bf16(A^T bf16(P)), bf16 output only, then grad_E0 = A^T G16; L == 2:
+// grad_E0 = A^T bf16(P).  All plain: the Adam pass adds P (L == 3) or g_out / (L + 1) (L == 2) exactly as in the fp32 step.
+static int bf16_backward_push(const spex_lightgcn_step_t *s, size_t sz, const float *P, void *stream)
+{
+    SPEX_TRY(spex_cast_bf16_f32(P, s->ws16, (int64_t)sz, stream));
+    const uint16_t *src = s->ws16;
+    if (s->L == 3) {
+        SPEX_TRY(spex_spmm_bf16_f32(s->graph_t, src, nullptr, s->ws16 + sz, nullptr, 1.0f, nullptr, nullptr, 1.0f, 64, stream));
+        src = s->ws16 + sz;
+    }
+    return spex_spmm_bf16_f32(s->graph_t, src, s->grad_E0, nullptr, nullptr, 1.0f, nullptr, nullptr, 1.0f, 64, stream);
+}
+
 extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t *users, const int64_t *items,
                                           const float *labels, int32_t B, float *loss_sum, void *stream)
 {
@@ -37,6 +102,8 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
                    "spex_lightgcn_step_bce_f32: graph and graph_t must carry the same edge-dropout mask");
     SPEX_CHECK_ARG(g->mask_mode == 0 || (gt != g && L >= 2),
                    "spex_lightgcn_step_bce_f32: edge dropout needs L >= 2 and graph_t = the transposed handle (with its edge-id permutation)");
+    const bool bf16 = (s->flags & SPEX_STEP_BF16_GATHER) != 0;
+    if (bf16) SPEX_TRY(bf16_step_check(s, "spex_lightgcn_step_bce_f32"));
     const size_t sz = (size_t)g->n_rows * d;
     const bool det = (s->flags & SPEX_STEP_DETERMINISTIC) != 0;
     // ---- forward: layers 0 .. L-2 over the whole graph; the last layer is taken at the batch's rows only.  For L <= 3 the whole-graph
@@ -45,7 +112,10 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
     //      reads — in the fused epilogues' order; deeper models keep the running sum fused into the launches.
     const bool plain = L >= 2 && L <= 3;
     const float *cur = s->E0;
-    for (int32_t l = 0; l + 1 < L; ++l) {
+    const uint16_t *cur16 = nullptr;             // SPEX_STEP_BF16_GATHER: the batch kernel's gather source, bf16(y_(L-1))
+    uint16_t *shadow = bf16 ? s->E0_16 : nullptr;   // ... and the Adam pass's second output
+    if (bf16) SPEX_TRY(bf16_forward(s, sz, &cur16, stream));
+    for (int32_t l = 0; !bf16 && l + 1 < L; ++l) {
         float *nxt = s->ws_fwd + (size_t)(l & 1) * sz;
         if (plain) SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
         else SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, l == 0 ? s->E0 : s->light_out, s->light_out, 1.0f, d, stream));
@@ -61,12 +131,18 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
         //      model.py:115-116), and the whole backward runs in pull form (each output row one chain in ascending column order,
         //      like the reference's sparse addmm).  Per-sample losses: head of lo_batch, summed in order by the Adam pass.
         float *loss_rows = s->lo_batch;
-        SPEX_TRY(spex::lightgcn_batch_slots_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, items, labels, B, n_u,
-                                                   1.0f / (float)B, nullptr, loss_rows, s->grad_slots, d, stream));
+        if (bf16)
+            SPEX_TRY(spex::lightgcn_batch_slots_bf16_layers(g, cur16, sum0, sum1, sum2, (float)(L + 1), users, items, labels, B, n_u,
+                                                            1.0f / (float)B, nullptr, loss_rows, s->grad_slots, d, stream));
+        else
+            SPEX_TRY(spex::lightgcn_batch_slots_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, items, labels, B, n_u,
+                                                       1.0f / (float)B, nullptr, loss_rows, s->grad_slots, d, stream));
         SPEX_TRY(spex_reduce_slots_f32(users, B, 0, items, B, n_u, g->n_rows, s->grad_slots, d, 1.0f, s->g_out, 0, d, stream));
-        SPEX_TRY(spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream));
+        if (bf16) SPEX_TRY(spex_propagate_bwd_bf16_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, s->ws16, L, d, stream));
+        else SPEX_TRY(spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream));
         SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, s->t + 1, s->lr, s->beta1, s->beta2, s->eps, s->g_out,
-                                    s->ws_bwd /* keeps the fast path's push target all-zero */, stream, loss_rows, B, loss_sum));
+                                    s->ws_bwd /* keeps the fast path's push target all-zero */, stream, loss_rows, B, loss_sum, nullptr,
+                                    nullptr, 1.0f, nullptr, shadow));
         s->t += 1;
         return SPEX_OK;
     }
@@ -76,16 +152,21 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
         //      A[r, c] g[r] — (g_out and G are all-zero here: the Adam pass below clears them for the next step; first call: the caller)
         float *G = s->ws_bwd;
         const bool all_plain = L == 3;              // (see below: nothing reads the dense d loss / d light_out then — it is not formed)
-        SPEX_TRY(spex::lightgcn_batch_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, items, labels, B, n_u, 1.0f / (float)B,
-                                             1.0f / (float)(L + 1), nullptr, s->grad_slots /* per-sample losses, summed by the Adam pass */,
-                                             all_plain ? nullptr : s->g_out, G, d, stream));
+        if (bf16)
+            SPEX_TRY(spex::lightgcn_batch_bf16_layers(g, cur16, sum0, sum1, sum2, (float)(L + 1), users, items, labels, B, n_u, 1.0f / (float)B,
+                                                      1.0f / (float)(L + 1), nullptr, s->grad_slots, all_plain ? nullptr : s->g_out, G, d, stream));
+        else
+            SPEX_TRY(spex::lightgcn_batch_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, items, labels, B, n_u, 1.0f / (float)B,
+                                                 1.0f / (float)(L + 1), nullptr, s->grad_slots /* per-sample losses, summed by the Adam pass */,
+                                                 all_plain ? nullptr : s->g_out, G, d, stream));
         // ---- L-1 pull-form products G_l = g / (L+1) + A^T G_{l+1}.  The last one (l = 0) runs in the PLAIN form: its g / (L+1) term
         //      is added by the Adam pass, which reads g_out anyway to clear it (one epilogue stream less on a 15 us launch).
         //      L == 3 (the reference's depth): BOTH run plain.  With P = G_2 = (g + A^T g) / 4 the gradient is
         //      A^T (A^T P + g/4) + g/4 = A^T (A^T P) + (A^T g / 4 + g / 4) = A^T (A^T P) + P — and P is the push target, which the
         //      Adam pass touches anyway (to clear it): it adds P instead of g / 4.  No epilogue operand left in the backward.
         const float *c2 = G;
-        for (int32_t l = L - 2; l >= 0; --l) {
+        if (bf16) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
+        for (int32_t l = L - 2; !bf16 && l >= 0; --l) {
             float *nxt = l == 0 ? s->grad_E0 : s->ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;   // ws_bwd[1], [2], [1] ...: never the source, never G
             if (l == 0 || all_plain) SPEX_TRY(spex_spmm_f32(gt, c2, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
             else SPEX_TRY(spex_spmm_f32(gt, c2, nxt, s->g_out, (float)(L + 1), nullptr, nullptr, 1.0f, d, stream));
@@ -93,7 +174,8 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
         }
         SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, s->t + 1, s->lr, s->beta1, s->beta2, s->eps,
                                     all_plain ? nullptr : s->g_out /* untouched (all-zero) in the all-plain step */, s->ws_bwd, stream,
-                                    s->grad_slots, B, loss_sum, nullptr, all_plain ? G : s->g_out, all_plain ? 1.0f : (float)(L + 1)));
+                                    s->grad_slots, B, loss_sum, nullptr, all_plain ? G : s->g_out, all_plain ? 1.0f : (float)(L + 1), nullptr,
+                                    shadow));
         s->t += 1;
         return SPEX_OK;
     } else {    // L == 1: the last layer at the batch's rows, scoring, then grad = (g + A^T g) / 2 as one pull-form product
@@ -178,6 +260,8 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     const spex_graph *g = s->graph, *gt = s->graph_t;
     const int32_t L = s->L, d = s->d, n_u = s->n_user_rows;
     SPEX_CHECK_ARG(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_rows, "%s: square graphs of one size", who);
+    const bool bf16 = (s->flags & SPEX_STEP_BF16_GATHER) != 0;
+    if (bf16) SPEX_TRY(bf16_step_check(s, who));
     if ((s->flags & SPEX_STEP_WIDE) != 0) {
         if (d != 128 && d != 256) {
             spex::set_error("%s: SPEX_STEP_WIDE takes d = 128 or 256 (got %d); d == 64 runs without the flag — the widths are 64, 128 and 256", who, d);
@@ -209,7 +293,10 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     // ---- forward: layers 0 .. L-2 over the whole graph (plain for L <= 3), the last layer at the batch's rows only
     const bool plain = L >= 2 && L <= 3;
     const float *cur = s->E0;
-    for (int32_t l = 0; l + 1 < L; ++l) {
+    const uint16_t *cur16 = nullptr;             // SPEX_STEP_BF16_GATHER: the batch kernel's gather source, bf16(y_(L-1))
+    uint16_t *shadow = bf16 ? s->E0_16 : nullptr;   // ... and the Adam pass's second output
+    if (bf16) SPEX_TRY(bf16_forward(s, sz, &cur16, stream));
+    for (int32_t l = 0; !bf16 && l + 1 < L; ++l) {
         float *nxt = s->ws_fwd + (size_t)(l & 1) * sz;
         if (plain) SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
         else SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, l == 0 ? s->E0 : s->light_out, s->light_out, 1.0f, d, stream));
@@ -217,16 +304,33 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     }
     const float *sum0 = plain || L == 1 ? s->E0 : s->light_out;
     const float *sum1 = plain ? s->ws_fwd : nullptr, *sum2 = plain && L == 3 ? s->ws_fwd + sz : nullptr;
+    // the batch launch in its four forms: slots (G and g_out NULL, slots given) or atomics, from the fp32 or the bf16 table
+    auto batch = [&](float push_scale, float *loss_rows, float *slots, float *dense, float *G) -> int {
+        int32_t *counts = l2.count ? cnt : nullptr;
+        if (slots)
+            return bf16 ? spex::lightgcn_bpr_batch_slots_bf16_layers(g, cur16, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u,
+                                                                     1.0f / (float)T, wd, s->E0, counts, nullptr, loss_rows, slots, d, stream)
+                        : spex::lightgcn_bpr_batch_slots_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u,
+                                                                1.0f / (float)T, wd, s->E0, counts, nullptr, loss_rows, slots, d, stream);
+        return bf16 ? spex::lightgcn_bpr_batch_bf16_layers(g, cur16, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u, 1.0f / (float)T,
+                                                           push_scale, wd, s->E0, counts, nullptr, loss_rows, dense, G, d, stream)
+                    : spex::lightgcn_bpr_batch_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u, 1.0f / (float)T,
+                                                      push_scale, wd, s->E0, counts, nullptr, loss_rows, dense, G, d, stream);
+    };
+    // the whole backward in pull form from the dense d loss / d light_out
+    auto backward_dense = [&]() -> int {
+        return bf16 ? spex_propagate_bwd_bf16_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, s->ws16, L, d, stream)
+                    : spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream);
+    };
     if (det) {
         float *loss_rows = s->lo_batch;
-        SPEX_TRY(spex::lightgcn_bpr_batch_slots_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u, 1.0f / (float)T, wd,
-                                                       s->E0, l2.count ? cnt : nullptr, nullptr, loss_rows, s->grad_slots, d, stream));
+        SPEX_TRY(batch(0.0f, loss_rows, s->grad_slots, nullptr, nullptr));
         SPEX_TRY(spex_reduce_slots_f32(users, T, 0, nullptr, 0, 0, g->n_rows, s->grad_slots, d, 1.0f, s->g_out, 0, d, stream));
         SPEX_TRY(spex_reduce_slots_f32(pos, T, n_u, neg, T, n_u, g->n_rows, s->grad_slots + (size_t)T * d, d, 1.0f, s->g_out, 1, d, stream));
-        SPEX_TRY(spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream));
+        SPEX_TRY(backward_dense());
         SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, t_next, s->lr, s->beta1, s->beta2, s->eps, s->g_out,
                                     s->ws_bwd /* keeps the fast path's push target all-zero */, stream, loss_rows, T, loss_sum, nullptr,
-                                    nullptr, 1.0f, &l2));
+                                    nullptr, 1.0f, &l2, shadow));
         s->t = t_next;
         return SPEX_OK;
     }
@@ -235,12 +339,11 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     if (dense) {
         // ---- large batches: the same launch with the push skipped — the gradient rows go to the dense g_out with atomics — and the
         //      whole backward in pull form (L products: their cost does not grow with T, the push's does)
-        SPEX_TRY(spex::lightgcn_bpr_batch_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u, 1.0f / (float)T, 0.0f, wd,
-                                                 s->E0, l2.count ? cnt : nullptr, nullptr, s->grad_slots, s->g_out, nullptr, d, stream));
-        SPEX_TRY(spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream));
+        SPEX_TRY(batch(0.0f, s->grad_slots, nullptr, s->g_out, nullptr));
+        SPEX_TRY(backward_dense());
         SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, t_next, s->lr, s->beta1, s->beta2, s->eps, s->g_out,
                                     s->ws_bwd /* propagate_bwd's scaled gradient: the push target stays all-zero */, stream, s->grad_slots, T,
-                                    loss_sum, nullptr, nullptr, 1.0f, &l2));
+                                    loss_sum, nullptr, nullptr, 1.0f, &l2, shadow));
         s->t = t_next;
         return SPEX_OK;
     }
@@ -249,12 +352,10 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     //      with the push target P added instead — A^T (A^T P) + P, the identity derived at spex_lightgcn_step_bce_f32
     float *G = s->ws_bwd;
     const bool no_dense = L == 3 || L == 1;        // nothing reads the dense d loss / d light_out then: it is not formed
-    SPEX_TRY(spex::lightgcn_bpr_batch_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u, 1.0f / (float)T,
-                                             1.0f / (float)(L + 1), wd, s->E0, l2.count ? cnt : nullptr, nullptr,
-                                             s->grad_slots /* per-triple losses, summed by the Adam pass */, no_dense ? nullptr : s->g_out, G,
-                                             d, stream));
+    SPEX_TRY(batch(1.0f / (float)(L + 1), s->grad_slots /* per-triple losses, summed by the Adam pass */, nullptr, no_dense ? nullptr : s->g_out, G));
     const float *c2 = G;
-    for (int32_t l = L - 2; l >= 0; --l) {
+    if (bf16) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
+    for (int32_t l = L - 2; !bf16 && l >= 0; --l) {
         float *nxt = l == 0 ? s->grad_E0 : s->ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;
         if (l == 0 || L == 3) SPEX_TRY(spex_spmm_f32(gt, c2, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
         else SPEX_TRY(spex_spmm_f32(gt, c2, nxt, s->g_out, (float)(L + 1), nullptr, nullptr, 1.0f, d, stream));
@@ -263,7 +364,7 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     // (L == 1: the push target IS the gradient — read, stored to grad_E0 and cleared by the same pass)
     SPEX_TRY(spex::adam_step_z2(s->E0, L == 1 ? G : s->grad_E0, s->m, s->v, (int64_t)sz, t_next, s->lr, s->beta1, s->beta2, s->eps,
                                 no_dense ? nullptr : s->g_out, s->ws_bwd, stream, s->grad_slots, T, loss_sum, nullptr,
-                                L == 1 ? nullptr : (L == 3 ? G : s->g_out), L == 3 ? 1.0f : (float)(L + 1), &l2));
+                                L == 1 ? nullptr : (L == 3 ? G : s->g_out), L == 3 ? 1.0f : (float)(L + 1), &l2, shadow));
     s->t = t_next;
     return SPEX_OK;
 }

@@ -574,6 +574,91 @@ def lightgcn_bpr_batch_wide(graph, X, acc_in, acc_div, users, pos, neg, n_user_r
                       n_user_rows, grad_scale, push_scale, loss_sum, g_out, G, loss_per_sample, weight_decay, E0, row_counts)
 
 
+# ---- the four d == 64 batch kernels with a bf16 gather source (batch_bf16.hip; SPEX_STEP_BF16_GATHER's launches):
+#      X16 = a bf16 [N, 64] table for X; every other argument, and everything computed behind the gather, as in the fp32 sibling.
+def _bf16_batch_args(name, graph, X16, acc_in, idx, labels, tables, loss_sum, loss_per_sample, E0=None, row_counts=None, weight_decay=0.0):
+    n = graph.n_rows
+    if not (X16.is_cuda and X16.dtype == torch.bfloat16 and X16.is_contiguous() and X16.shape == (n, 64)):
+        raise ValueError(f"{name}: X16 must be a contiguous bf16 [{n}, 64] device tensor (bf16 gather tables are d == 64 only)")
+    for t, nm in ((acc_in, "acc_in"), (E0, "E0")) + tuple(tables):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (n, 64)):
+            raise ValueError(f"{name}: {nm} must be a contiguous fp32 [{n}, 64] device tensor")
+    k = idx[0].numel()
+    for t in idx:
+        if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == k):
+            raise ValueError(f"{name}: the index tensors must be contiguous int64 device tensors of one length")
+    if labels is not None and not (labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous() and labels.numel() == k):
+        raise ValueError(f"{name}: labels must be a contiguous fp32 device tensor of the batch's length")
+    for t, m, nm in ((loss_sum, 1, "loss_sum"), (loss_per_sample, k, "loss_per_sample")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= m):
+            raise ValueError(f"{name}: {nm} must be a contiguous fp32 device tensor of >= {m} elements")
+    if loss_sum is None and loss_per_sample is None:
+        raise ValueError(f"{name}: needs loss_sum or loss_per_sample")
+    if weight_decay > 0 and E0 is None:
+        raise ValueError(f"{name}: weight_decay > 0 needs E0")
+    if row_counts is not None and not (row_counts.is_cuda and row_counts.dtype == torch.int32 and row_counts.is_contiguous()
+                                       and row_counts.numel() >= n):
+        raise ValueError(f"{name}: row_counts must be a contiguous int32 device tensor of >= {n} elements")
+    return k
+
+
+def _bf16_slots_ok(name, grad_slots, rows):
+    if not (grad_slots.is_cuda and grad_slots.dtype == torch.float32 and grad_slots.is_contiguous() and grad_slots.dim() == 2
+            and grad_slots.shape[0] >= rows and grad_slots.shape[1] == 64):
+        raise ValueError(f"{name}: grad_slots must be a contiguous fp32 [>= {rows}, 64] device tensor")
+
+
+def lightgcn_batch_slots_bf16(graph, X16, acc_in, acc_div, users, items, labels, n_user_rows, grad_scale, grad_slots, loss_sum=None,
+                              loss_per_sample=None):
+    """spex_lightgcn_batch_slots_bf16_f32: lightgcn_batch_slots gathering its last layer from the bf16 table X16."""
+    B = _bf16_batch_args("lightgcn_batch_slots_bf16", graph, X16, acc_in, (users, items), labels, (), loss_sum, loss_per_sample)
+    _bf16_slots_ok("lightgcn_batch_slots_bf16", grad_slots, 2 * B)
+    _launch(X16.device, "spex_lightgcn_batch_slots_bf16_f32", graph._h, _ptr(X16), _ptr(acc_in), float(acc_div), _ptr(users), _ptr(items),
+            _ptr(labels), B, int(n_user_rows), float(grad_scale), _ptr(loss_sum), _ptr(loss_per_sample), _ptr(grad_slots), 64)
+    _bump(loss_sum, loss_per_sample, grad_slots)
+
+
+def lightgcn_batch_bf16(graph, X16, acc_in, acc_div, users, items, labels, n_user_rows, grad_scale, push_scale, loss_sum, g_out, G,
+                        loss_per_sample=None):
+    """spex_lightgcn_batch_bf16_f32: lightgcn_batch gathering its last layer from the bf16 table X16 (g_out, G: fp32, accumulated)."""
+    B = _bf16_batch_args("lightgcn_batch_bf16", graph, X16, acc_in, (users, items), labels, ((g_out, "g_out"), (G, "G")), loss_sum,
+                         loss_per_sample)
+    if g_out is None or G is None:
+        raise ValueError("lightgcn_batch_bf16: needs g_out and G")
+    _launch(X16.device, "spex_lightgcn_batch_bf16_f32", graph._h, _ptr(X16), _ptr(acc_in), float(acc_div), _ptr(users), _ptr(items),
+            _ptr(labels), B, int(n_user_rows), float(grad_scale), float(push_scale), _ptr(loss_sum), _ptr(loss_per_sample), _ptr(g_out),
+            _ptr(G), 64)
+    _bump(loss_sum, loss_per_sample, g_out, G)
+    return loss_sum if loss_per_sample is None else loss_per_sample
+
+
+def lightgcn_bpr_batch_slots_bf16(graph, X16, acc_in, acc_div, users, pos, neg, n_user_rows, grad_scale, grad_slots, loss_sum=None,
+                                  loss_per_sample=None, weight_decay=0.0, E0=None, row_counts=None):
+    """spex_lightgcn_bpr_batch_slots_bf16_f32: lightgcn_bpr_batch_slots gathering its last layer from the bf16 table X16."""
+    T = _bf16_batch_args("lightgcn_bpr_batch_slots_bf16", graph, X16, acc_in, (users, pos, neg), None, (), loss_sum, loss_per_sample, E0,
+                         row_counts, weight_decay)
+    _bf16_slots_ok("lightgcn_bpr_batch_slots_bf16", grad_slots, 3 * T)
+    _launch(X16.device, "spex_lightgcn_bpr_batch_slots_bf16_f32", graph._h, _ptr(X16), _ptr(acc_in), float(acc_div), _ptr(users), _ptr(pos),
+            _ptr(neg), T, int(n_user_rows), float(grad_scale), float(weight_decay), _ptr(E0), _ptr(row_counts), _ptr(loss_sum),
+            _ptr(loss_per_sample), _ptr(grad_slots), 64)
+    _bump(loss_sum, loss_per_sample, grad_slots, row_counts)
+
+
+def lightgcn_bpr_batch_bf16(graph, X16, acc_in, acc_div, users, pos, neg, n_user_rows, grad_scale, push_scale, loss_sum, g_out, G,
+                            loss_per_sample=None, weight_decay=0.0, E0=None, row_counts=None):
+    """spex_lightgcn_bpr_batch_bf16_f32: lightgcn_bpr_batch gathering its last layer from the bf16 table X16 (g_out / G: fp32; None:
+    not formed / no push)."""
+    T = _bf16_batch_args("lightgcn_bpr_batch_bf16", graph, X16, acc_in, (users, pos, neg), None, ((g_out, "g_out"), (G, "G")), loss_sum,
+                         loss_per_sample, E0, row_counts, weight_decay)
+    if G is None and g_out is None:
+        raise ValueError("lightgcn_bpr_batch_bf16: needs the push target G and / or the dense g_out")
+    _launch(X16.device, "spex_lightgcn_bpr_batch_bf16_f32", graph._h, _ptr(X16), _ptr(acc_in), float(acc_div), _ptr(users), _ptr(pos), _ptr(neg),
+            T, int(n_user_rows), float(grad_scale), float(push_scale), float(weight_decay), _ptr(E0), _ptr(row_counts), _ptr(loss_sum),
+            _ptr(loss_per_sample), _ptr(g_out), _ptr(G), 64)
+    _bump(loss_sum, loss_per_sample, g_out, G, row_counts)
+    return loss_sum if loss_per_sample is None else loss_per_sample
+
+
 def gated_batch_fwd(graph, X, acc_in, acc_div, raw, att_u, att_i, users, items, labels, n_user_rows, grad_scale, loss_sum, lo_batch,
                     grad_slots, loss_per_sample=None):
     """Forward half of the dual-task rec branch's batch-sized middle as one launch (spex_gated_batch_fwd_f32): last layer + layer

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .graph import _bump, _launch
+from .graph import _bump, _gather_bf16, _launch, cast_bf16
 
 
 def _deterministic_default(deterministic):
@@ -51,8 +51,14 @@ def _drop_desc(stepper):
 
 class LightGCNStepper:
     def __init__(self, graph, E0, n_user_rows, n_layers=3, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph_t=None, deterministic=None,
-                 weight_decay=0.0):
-        """weight_decay: the L2 coefficient of step_bpr_exact / epoch_bpr (upstream LightGCN's `decay`: weight_decay / 2 * the squared
+                 weight_decay=0.0, gather_dtype=None):
+        """gather_dtype: None / torch.float32, or torch.bfloat16 (width 64 and n_layers 2 or 3 only; ValueError otherwise) — the
+        whole-graph launches of step_bce / step_bpr_exact, of the native epochs and of the sampled epochs gather from bf16 tables
+        (rows of 128 bytes) while every product, sum and the layer mean stay fp32 and E0, m, v stay fp32 (SPEX_STEP_BF16_GATHER,
+        DESIGN.md 4.19).  The stepper keeps `E0_16`, a bf16 shadow of E0 that the one-call step's Adam pass writes beside E0; the
+        stepper's own other paths re-cast it when needed.  A caller that writes `stepper.E0` itself calls refresh_gather_table()
+        before the next step.  Pays on graphs that stream from HBM; slower on cache-resident ones.  step_bpr_sgd stays fp32.
+        weight_decay: the L2 coefficient of step_bpr_exact / epoch_bpr (upstream LightGCN's `decay`: weight_decay / 2 * the squared
         norms of the batch's E0 rows, over T, added to the mean BPR loss); the BCE steps do not read it.
         deterministic (default: SPEX_DETERMINISTIC=1 in the environment): the step takes every sum in a fixed order — no float
         atomics (spex_lightgcn_step_t.flags & SPEX_STEP_DETERMINISTIC): per-sample gradient rows added per table row in ascending
@@ -86,11 +92,36 @@ class LightGCNStepper:
         self.grad_slots = None        # per-sample gradient rows (_slots), allocated for the largest batch seen
         self._desc = None             # the one-call step's descriptor (_prepare_desc)
         self._ws0_clean = False       # ws_bwd[0] is all-zero (the one-call step's push target)
+        self.gather_dtype = torch.bfloat16 if _gather_bf16(gather_dtype) else None
+        self.E0_16 = self.ws16 = None
+        if self.gather_dtype is not None:
+            if d != 64 or self.L not in (2, 3):
+                raise ValueError(f"LightGCNStepper(gather_dtype=torch.bfloat16): bf16 gather tables take an embedding width of 64 and "
+                                 f"n_layers 2 or 3 (got width {d}, n_layers {self.L})")
+            self.E0_16 = torch.empty((n, d), dtype=torch.bfloat16, device=dev)       # bf16(E0): see _shadow_current
+            self.ws16 = torch.zeros((2, n, d), dtype=torch.bfloat16, device=dev)     # the later layers' gather tables, then the backward's
+        self._shadow_current = False  # E0_16 == bf16(E0) (kept so by the bf16 one-call step's Adam pass; every other writer of E0 clears it)
         self.t = 0
+
+    def refresh_gather_table(self):
+        """Re-cast the bf16 gather table from E0 (one streaming launch).  For callers that write `stepper.E0` themselves — loading a
+        checkpoint into it, a manual update: the one-call steps of a gather_dtype=torch.bfloat16 stepper read E0_16, not E0, in their
+        first layer, and trust it to equal bf16(E0).  The stepper's own methods keep track themselves.  No-op without gather_dtype."""
+        if self.gather_dtype is not None:
+            cast_bf16(self.E0, out=self.E0_16)
+            self._shadow_current = True
 
     # -- pieces
     def propagate(self):
+        if self.gather_dtype is not None:
+            return self.graph.propagate(self.E0, self.L, mean_out=self.light_out, ws=self.ws16, gather_dtype=self.gather_dtype)
         return self.graph.propagate(self.E0, self.L, mean_out=self.light_out, ws=self.ws_fwd)
+
+    def _propagate_bwd(self):
+        """grad_E0 from the dense g_out, all in pull form (with gather_dtype: the straight-through bf16 backward)."""
+        if self.gather_dtype is not None:
+            return self.graph_t.propagate_bwd(self.g_out, self.L, grad_E0=self.grad_E0, ws=self.ws16, gather_dtype=self.gather_dtype)
+        return self.graph_t.propagate_bwd(self.g_out, self.L, grad_E0=self.grad_E0, ws=self.ws_bwd)
 
     def propagate_for_batch(self, users, items):
         """The propagation as the training step needs it: layers 1 .. L-1 over the whole graph, the LAST layer only at the
@@ -122,7 +153,8 @@ class LightGCNStepper:
         if batch_rows_only and loss_acc is not None and self._one_call_ok(users, items, labels):
             return self._step_bce_one_call(users, items, labels, loss_acc)
         masked = getattr(self.graph, "mask_mode", 0) != 0        # (the row-list kernel of the launch-by-launch form takes no mask)
-        lo = self.propagate_for_batch(users, items) if batch_rows_only and not masked else self.propagate()
+        bf16 = self.gather_dtype is not None                     # (... and there is none for a bf16 table: the whole-graph propagation)
+        lo = self.propagate_for_batch(users, items) if batch_rows_only and not masked and not bf16 else self.propagate()
         B = users.numel()
         self._slots(B)
         if self.deterministic:
@@ -132,15 +164,20 @@ class LightGCNStepper:
                                         want_gamma=False, grad_slots=self.grad_slots)
             ops.reduce_slots(users, items, self.n_u, self.E0.shape[0], self.grad_slots, self.g_out)
             self._ws0_clean = False
-            self.graph_t.propagate_bwd(self.g_out, self.L, grad_E0=self.grad_E0, ws=self.ws_bwd)
+            self._propagate_bwd()
         else:
             _, loss_sum = ops.score_bce(lo[:self.n_u], lo[self.n_u:], users, items, labels, self.g_out[:self.n_u],
                                         self.g_out[self.n_u:], 1.0 / B, loss_sum=loss_acc, want_gamma=False, grad_slots=self.grad_slots)
-            self.backward_from_batch_rows(users, items)
+            if bf16:
+                self._ws0_clean = False
+                self._propagate_bwd()
+            else:
+                self.backward_from_batch_rows(users, items)
         self._clear_row_counts()
         self.t += 1
         ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps,
                       zero=self.g_out)
+        self._shadow_current = False
         return None if loss_acc is not None else loss_sum / B
 
     def _slots(self, B, rows_per_sample=2):
@@ -186,6 +223,8 @@ class LightGCNStepper:
         if not self._ws0_clean:                          # another path used the workspace: restore the all-zero push target
             self.ws_bwd[0].zero_()
             self._ws0_clean = True
+        if self.gather_dtype is not None and not self._shadow_current:      # another path wrote E0: the shadow is stale
+            self.refresh_gather_table()
         if self._desc is None:
             p = lambda t: t.data_ptr()
             self._desc = _lib.LightGCNStepDesc(
@@ -193,13 +232,16 @@ class LightGCNStepper:
                 light_out=p(self.light_out), ws_fwd=p(self.ws_fwd), lo_batch=p(self.lo_batch), g_out=p(self.g_out),
                 ws_bwd=p(self.ws_bwd), grad_E0=p(self.grad_E0), grad_slots=p(self.grad_slots),
                 slot_capacity=self.grad_slots.shape[0], n_user_rows=self.n_u, L=self.L, d=self.E0.shape[1],
-                lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, t=self.t, flags=0)
+                lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, t=self.t, flags=0,
+                E0_16=None if self.E0_16 is None else p(self.E0_16), ws16=None if self.ws16 is None else p(self.ws16))
         d = self._desc
         d.t, d.lr = self.t, self.lr
         d.flags = _lib.STEP_DETERMINISTIC if self.deterministic else 0
         d.flags |= {None: 0, "push": _lib.STEP_BPR_PUSH, "dense": _lib.STEP_BPR_DENSE}[self.bpr_backward]     # (the BCE step ignores them)
         if self.E0.shape[1] in (128, 256):
             d.flags |= _lib.STEP_WIDE       # the exact BPR step's opt-in: every table and slot of this descriptor is d wide
+        if self.gather_dtype is not None:
+            d.flags |= _lib.STEP_BF16_GATHER
         d.weight_decay = self.weight_decay
         d.row_counts = None if self.row_counts is None else self.row_counts.data_ptr()
         return d
@@ -211,7 +253,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_step_bce_f32", ctypes.byref(d), ctypes.c_void_p(users.data_ptr()),
                 ctypes.c_void_p(items.data_ptr()), ctypes.c_void_p(labels.data_ptr()), B, ctypes.c_void_p(loss_acc.data_ptr()))
         self.t = d.t
-        _bump(self.E0, self.m, self.v, loss_acc)
+        _bump(self.E0, self.m, self.v, loss_acc, self.E0_16)
         return None
 
     def epoch_bce(self, users, items, labels, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
@@ -229,7 +271,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bce_f32", ctypes.byref(d), vp(users), vp(items), vp(labels), users.numel(), int(batch_size),
                 -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
         self.t = d.t
-        _bump(self.E0, self.m, self.v, loss_full, loss_ragged)
+        _bump(self.E0, self.m, self.v, loss_full, loss_ragged, self.E0_16)
 
     def backward_from_batch_rows(self, users, items):
         """grad_E0 from g_out (non-zero on the batch's rows only).  The first product of the backward pass, A^T g, touches
@@ -269,8 +311,10 @@ class LightGCNStepper:
             _launch(self.E0.device, "spex_lightgcn_step_bpr_f32", self.graph._h, p(self.E0), p(self.light_out), p(self.ws_fwd), self.n_u,
                     self.L, 64, p(users), p(pos), p(neg), T, float(self.lr if lr is None else lr), float(reg), p(self.loss_acc))
             _bump(self.E0, self.loss_acc, self.light_out)
+            self._shadow_current = False
             return self.loss_acc
-        self.propagate()
+        self.graph.propagate(self.E0, self.L, mean_out=self.light_out, ws=self.ws_fwd)      # (fp32 on every stepper: this step has no bf16 form)
+        self._shadow_current = False
         lo = self.light_out
         ops.bpr_sgd_step(lo[:self.n_u], lo[self.n_u:], self.E0[:self.n_u], self.E0[self.n_u:], users, pos, neg,
                          self.lr if lr is None else lr, reg, loss_sum=self.loss_acc)
@@ -304,7 +348,7 @@ class LightGCNStepper:
                                      self.g_out[self.n_u:], 1.0 / T)
         self._ws0_clean = False
         self._clear_row_counts()                 # (the one-call step's count tables go by step parity: this step advances t without them)
-        self.graph_t.propagate_bwd(self.g_out, self.L, grad_E0=self.grad_E0, ws=self.ws_bwd)
+        self._propagate_bwd()
         if self.weight_decay > 0:
             dev = self.E0.device
             rows = torch.cat([users.to(dev), pos.to(dev) + self.n_u, neg.to(dev) + self.n_u])
@@ -314,6 +358,7 @@ class LightGCNStepper:
         self.t += 1
         ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps,
                       zero=self.g_out)          # invariant of both exact steps: g_out is all-zero between steps
+        self._shadow_current = False
         if loss_acc is not None:
             loss_acc += loss_sum
             return None
@@ -332,7 +377,7 @@ class LightGCNStepper:
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         _launch(self.E0.device, "spex_lightgcn_step_bpr_adam_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), T, vp(loss_acc))
         self.t = d.t
-        _bump(self.E0, self.m, self.v, self.grad_E0, loss_acc)
+        _bump(self.E0, self.m, self.v, self.grad_E0, loss_acc, self.E0_16)
         return None
 
     def epoch_bpr(self, users, pos, neg, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
@@ -347,7 +392,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bpr_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), users.numel(), int(batch_size),
                 -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
         self.t = d.t
-        _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged)
+        _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged, self.E0_16)
 
     # -- sampled epochs: the triples drawn on the device by the same native call that trains on them
     def _one_call_bpr_shape_ok(self):
@@ -378,7 +423,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bpr_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
                 int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
         self.t = d.t
-        _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged, *sampler.epoch_buffers())
+        _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged, self.E0_16, *sampler.epoch_buffers())
 
     def train_bpr_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
         """n_epochs sampled epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
@@ -394,7 +439,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_train_bpr_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
                 *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
         self.t = d.t
-        _bump(self.E0, self.m, self.v, self.grad_E0, loss_epochs, *sampler.epoch_buffers())
+        _bump(self.E0, self.m, self.v, self.grad_E0, loss_epochs, self.E0_16, *sampler.epoch_buffers())
 
     # -- sampled BCE epochs: negatives, labels and the shuffle drawn on the device by the same native call that trains on them
     def _one_call_bce_shape_ok(self):
@@ -426,7 +471,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bce_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
                 int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
         self.t = d.t
-        _bump(self.E0, self.m, self.v, loss_full, loss_ragged, *sampler.epoch_buffers())
+        _bump(self.E0, self.m, self.v, loss_full, loss_ragged, self.E0_16, *sampler.epoch_buffers())
 
     def train_bce_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
         """n_epochs sampled BCE epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
@@ -443,7 +488,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_train_bce_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
                 *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
         self.t = d.t
-        _bump(self.E0, self.m, self.v, loss_epochs, *sampler.epoch_buffers())
+        _bump(self.E0, self.m, self.v, loss_epochs, self.E0_16, *sampler.epoch_buffers())
 
 
 def dataloader_epoch_order(n):
