@@ -11,10 +11,6 @@ namespace batchk {
 
 constexpr int kBatchParts = 3, kBatchRunsPerPart = 16;      // measured: see the table at the top of batch.hip
 
-__device__ __forceinline__ float lane_bcast(float v, int src)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 #ifdef SPEX_STAMPS   // debug build only (tools/batch_stamps.py): phase stamps of workgroup 0 / wave 0, wall_clock64 = 100 MHz
@@ -106,13 +102,6 @@ __device__ __forceinline__ float segment_sum_masked(const int32_t *__restrict__ 
 // ---- the same two segments gathering from a bf16 table (rows of 128 bytes; Xl = X16 + lane): two gathered entries share a register
 //      (low / high half, as in spmm_bf16.hip), widening is a shift or a mask and exact, and the fmaf chain is the one above — on
 //      Xw = float(X16) these return what the fp32 forms return on Xw, bit for bit.
-typedef unsigned short h2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float widen_pair(h2 p, int hi)
-{
-    const uint32_t w = __builtin_bit_cast(uint32_t, p);
-    return __uint_as_float(hi ? (w & 0xFFFF0000u) : (w << 16));
-}
-
 __device__ __forceinline__ float segment_sum(const int32_t *__restrict__ col, const float *__restrict__ val, const uint16_t *__restrict__ Xl,
                                              int e0, int cnt, int lane, float acc)
 {

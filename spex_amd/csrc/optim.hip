@@ -29,13 +29,6 @@ __device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, flo
 // whole gradient stored to l2.g_store.
 // SHADOW (adam_shadow_kernel): p16 also receives bf16(the updated parameter), round to nearest even, from the register that is stored
 // to p — the bf16 gather table of the one-call steps' next forward.  The one body serves both kernels.
-__device__ __forceinline__ uint16_t bf16_rne(float v)       // spmm_bf16.hip's rounding: what spex_cast_bf16_f32 returns
-{
-    const uint32_t u = __float_as_uint(v);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x0040u);
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
 template <bool L2, bool SHADOW>
 __device__ __forceinline__ void adam_body(float *__restrict__ p, const float *g,
                                           float *__restrict__ m, float *__restrict__ v, int64_t n4,
@@ -104,7 +97,7 @@ __device__ __forceinline__ void adam_body(float *__restrict__ p, const float *g,
         if constexpr (SHADOW) {
             typedef unsigned short h4 __attribute__((ext_vector_type(4)));
             h4 h;
-            h[0] = bf16_rne(P.x); h[1] = bf16_rne(P.y); h[2] = bf16_rne(P.z); h[3] = bf16_rne(P.w);
+            h[0] = spex::bf16_rne(P.x); h[1] = spex::bf16_rne(P.y); h[2] = spex::bf16_rne(P.z); h[3] = spex::bf16_rne(P.w);
             reinterpret_cast<h4 *>(p16)[i] = h;
         }
         reinterpret_cast<float4 *>(m)[i] = M;

@@ -27,11 +27,6 @@ __device__ __forceinline__ float wave_sum(float v)
     return wave_sum_f32(v);
 }
 
-__device__ __forceinline__ float lane_bcast_f(float v, int src)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
-
 __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -306,7 +301,7 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
             for (int k = 0; k < N; ++k)
                 x[k] = Xl[(size_t)(uint32_t)__builtin_amdgcn_readlane(my_col, c * kChunk + k) * 64];
 #pragma unroll
-            for (int k = 0; k < N; ++k) acc = fmaf(lane_bcast_f(my_val, c * kChunk + k), x[k], acc);
+            for (int k = 0; k < N; ++k) acc = fmaf(lane_bcast(my_val, c * kChunk + k), x[k], acc);
         };
         for (int c = 0; c * kChunk < cnt; ++c) {
             const int rem = cnt - c * kChunk;              // >= 1
@@ -322,7 +317,7 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
             for (int k = 0; k < kChunk; ++k)
                 x[k] = Xl[(size_t)(uint32_t)__builtin_amdgcn_readlane(my_col, c * kChunk + k) * 64];
 #pragma unroll
-            for (int k = 0; k < kChunk; ++k) acc = fmaf(lane_bcast_f(my_val, c * kChunk + k), x[k], acc);
+            for (int k = 0; k < kChunk; ++k) acc = fmaf(lane_bcast(my_val, c * kChunk + k), x[k], acc);
         }
 #endif
         s_seg[w][lane] = acc;
@@ -694,11 +689,11 @@ __global__ __launch_bounds__(kWave *kScoreWaves) void bpr_bucket_update_kernel(c
                             a.coef[t_mine] = c_mine;
                         }
 #pragma unroll
-                        for (int j = 0; j < kBatch; ++j) acc += lane_bcast_f(c_mine, j) * xa[j];   // (lanes >= nb hold 0)
+                        for (int j = 0; j < kBatch; ++j) acc += lane_bcast(c_mine, j) * xa[j];   // (lanes >= nb hold 0)
                     } else {
 #pragma unroll
                         for (int j = 0; j < kBatch; ++j)
-                            if (j < nb) acc += lane_bcast_f(m_c, i + j) * xa[j];
+                            if (j < nb) acc += lane_bcast(m_c, i + j) * xa[j];
                     }
                 }
                 i = run_end;

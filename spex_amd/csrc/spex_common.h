@@ -116,7 +116,11 @@ int bpr_sgd_layers(const float *snap, const float *t0, const float *t1, const fl
                    int64_t n_item_rows, const int64_t *u, const int64_t *i_pos, const int64_t *i_neg, int64_t T, float lr, float reg,
                    float *loss_sum, void *stream);    // score.hip: the fused BPR-SGD kernel reading rows as (((snap +) t0 + t1) + t2) / div
 int scale_div(const float *in, float *out, float div, int64_t n, void *stream);                          // spmm.hip: out = in / div
-int zero_f32(float *x, int64_t n, void *stream);                                                       // rows.hip: x[0 : n] = 0 (a kernel launch)
+// spmm.hip: what a launch that WRITES the handle's scratch does first (spex_graph::scratch_mu) — takes the lock into `lock` (held until the
+// caller's kernels are queued), makes `stream` wait for what the scratch's last user has queued, and records `stream` as that user
+int order_scratch(const spex_graph_t *g, hipStream_t stream, std::unique_lock<std::mutex> &lock);
+int ensure_partial(spex_graph_t *g, int32_t d);                                                        // spmm.hip: the scratch holds n_seg partial rows of d floats
+int zero_f32(float *x, int64_t n, void *stream);                                                      // rows.hip: x[0 : n] = 0 (a kernel launch)
 int sum_ordered(const float *x, int32_t n, float scale, float *out, int accumulate, void *stream);     // rows.hip: fixed-order sum
 int sum_parts(const float *parts, int32_t n_parts, int64_t stride, int32_t n, float *out, int accumulate,
               void *stream);                                                                        // rows.hip: partial blocks, in order
@@ -190,6 +194,30 @@ __device__ __forceinline__ float row16_sum_f32(float v)
     v += dpp_f32<0x122>(v);         // row_ror:2
     v += dpp_f32<0x121>(v);         // row_ror:1
     return v;
+}
+
+// Lane src's value to every lane, through an SGPR (src is wave-uniform).
+__device__ __forceinline__ float lane_bcast(float v, int src)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
+
+// fp32 -> bf16, round to nearest even; NaN stays NaN (quiet), +-0 and +-Inf are preserved, the largest finite fp32 rounds to Inf.
+// The library's one rounding: spex_cast_bf16_f32, the Y16 outputs, the Adam launch's shadow table.
+__device__ __forceinline__ uint16_t bf16_rne(float v)
+{
+    const uint32_t u = __float_as_uint(v);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x0040u);
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+// bf16 -> fp32 is exact: the 16 bits become the high half of the word.  Two gathered entries share a register (low / high half):
+// widening is a shift or a mask.
+typedef unsigned short h2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float widen_pair(h2 p, int hi)
+{
+    const uint32_t w = __builtin_bit_cast(uint32_t, p);
+    return __uint_as_float(hi ? (w & 0xFFFF0000u) : (w << 16));
 }
 }  // namespace spex
 

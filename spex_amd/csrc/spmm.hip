@@ -10,8 +10,9 @@
 // two 128-byte lines) and the arithmetic (one fmaf chain per output element in ascending column order — bit for bit
 // the order of the reference's CPU kernel):
 //
-//   spmm_chunk_kernel  d == 64, the tuned path (described at its definition): 16-wave workgroups, one wave per
-//                      <= 64-entry task read from the chunked task table, long rows summed through LDS.
+//   spmm_chunk_kernel  d == 64, the tuned path: 16-wave workgroups, one wave per <= 64-entry task read from the chunked task
+//                      table, long rows summed through LDS.  Its body (chunk_body) is written and described in spmm_chunk.h, which
+//                      it shares with the bf16-table kernel of spmm_bf16.hip.
 //   spmm_rows_kernel   any d: one wave per row (or per kSegLen-entry segment of a row with more than kLongRow entries), walking
 //                      the plain CSR in column tiles of 64; segment sums go through global scratch and
 //                      spmm_long_fixup_kernel adds them in segment order.  Correct everywhere, tuned nowhere.
@@ -25,9 +26,10 @@
 // or Philox draw keyed by the entry's edge id — so forward, backward and all layers of a step drop the same edges.
 #include <mutex>
 
-#include "spex_common.h"
+#include "spmm_chunk.h"
 
 using namespace spex;
+using namespace spex::chunkk;
 
 namespace {
 
@@ -62,11 +64,6 @@ __device__ __forceinline__ bool edge_kept(const SpmmParams &p, int eid)
     // floor(rand + keep_prob) with rand a 24-bit uniform in [0,1), as torch.rand produces (model.py:50-51)
     const float u = (float)(philox_first((uint32_t)eid, p.seed_lo, p.seed_hi) >> 8) * 5.9604644775390625e-8f;
     return (u + p.keep_prob) >= 1.0f;
-}
-
-__device__ __forceinline__ float lane_bcast(float v, int src)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
 }
 
 // Accumulate entries [beg, end) of one row into acc for the column this lane owns.
@@ -158,13 +155,6 @@ __device__ __forceinline__ void finish_row(const SpmmParams &p, int r, int c, fl
     if (p.acc_out) p.acc_out[o] = (p.acc_in[o] + y) / p.acc_div;
 }
 
-// Blocks are dealt round-robin over the 8 XCDs; remap so that each XCD walks a contiguous range of row blocks
-// (neighbouring rows share the cache lines where one row's (col,val) run ends and the next begins).  Speed only.
-__device__ __forceinline__ int xcd_contiguous_block(int bid, int nblk)
-{
-    return ((nblk & 7) == 0) ? (bid & 7) * (nblk >> 3) + (bid >> 3) : bid;
-}
-
 // Generic-d kernel: one wave per task.  Tasks [0, n_seg) are long-row segments (heaviest work first), tasks
 // [n_seg, n_seg + n_rows) are rows; rows longer than kLongRow are left to their segments.
 template <bool MASKED>
@@ -196,121 +186,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void spmm_rows_kernel(const 
 }
 
 
-// ---------------------------------------------------------------------------------------------------------------
-// d == 64 kernel: 16-wave workgroups, one wave per TASK (a run of <= 4 sixteen-entry chunks, see spex_common.h),
-// lane == embedding column.
-//
-// What was measured on MI355X on the way here (tools/gather_bench.hip, profiles/r01*):
-//   * random 256-byte row gathers run at the same rate — 6.1 TB/s from HBM, 15-24 TB/s from L2 / Infinity Cache —
-//     whether a row is fetched as 64 x 4 B or 16 x 16 B lanes, with 8 or 64 rows in flight per wave: the memory system,
-//     not the load shape, sets the ceiling;
-//   * what separates an SpMM from that ceiling is everything it issues AROUND the gathers.  The first version (one
-//     wave per row, rows walked with per-entry row-boundary tests and 64-bit scalar address arithmetic) spent 15 scalar
-//     + 6 vector instructions per gathered row and saturated the CU's scalar unit at a third of the gather rate;
-//   * feeding the per-entry metadata through scalar loads (s_load_dwordx16) starves on scalar-cache misses as soon
-//     as the matrix streams from HBM (29 ms vs 13 ms per launch on a 2^23-node graph); buffer loads with a scalar
-//     offset are ~25 % slower than global loads when the source table is cache-resident.
-// Hence this shape:
-//   * per 64 entries the wave loads source-row index, value (and, for bin-packed tasks, output row) with ONE coalesced
-//     vector load each — lane k holds entry k — and hands them to the scalar side with v_readlane;
-//   * per 16-entry chunk: 16 independent `global_load_dword` (scalar row base + lane offset) issued back to back,
-//     then 16 x { v_fmac; s_bitcmp on the chunk's end-of-row mask; branch }.  A row's epilogue operand (running layer
-//     sum, or g/(L+1)) is fetched in the same batch as its last gather, so emitting a row never waits on a
-//     dependent load;
-//   * tasks are padded to whole chunks with value-0 entries on the task's last real source row (an L1 hit);
-//   * rows of 65..1024 entries are cut into 64-entry segments that all sit in one workgroup; their sums meet in LDS
-//     and are added in segment order by the row's first wave: deterministic, no atomics, no second launch.  Rows beyond
-//     1024 entries (hubs) go through global scratch: their segments lead the task table in groups of 16 adjacent waves, a
-//     group is summed through LDS the same way and leaves ONE partial row, and the hub's last group to arrive (a ticket in
-//     memory, no waiting) adds the groups in order and runs the epilogue — inside this launch (HubFold; the wide kernels
-//     and SPEX_HUB_FOLD=0 leave one partial row per segment to spmm_long_fixup_kernel instead).
-// The accumulation is one fmaf chain per output element in ascending column order (bit-exact vs the reference's CPU
-// kernel) for every row that fits a task; segmented rows re-associate <= 16 partial sums.
-
-// Edge dropout (MASKED): lane k decides for its own entry (injected mask byte or Philox draw keyed by the entry's edge
-// id, so forward / backward / every layer of a step agree); a dropped entry keeps its slot with value 0 and the
-// source row of the super-chunk's first kept entry (already being fetched), so it costs no extra traffic — and its
-// gathered value is REPLACED by 0 before the fmaf (a wave-uniform select per entry), so that it contributes exactly
-// nothing, as in the reference, where the entry is gone from the matrix: multiplying instead would turn a stand-in row
-// holding Inf / NaN (a diverged table) into 0 * Inf = NaN on a row that never referenced it.
-// In-kernel fold of the rows beyond kWgRowMax entries (tag != 0; spex_common.h: hub_grp / hub_fold / hub_ticket).  tag == 0: the
-// hub segments leave one partial row each and spmm_long_fixup_kernel adds them (the wide kernels, and SPEX_HUB_FOLD=0).
-#ifndef SPEX_EPI_NT
-#define SPEX_EPI_NT 1
-#endif
-#if SPEX_EPI_NT
-#define SPEX_EPI_LOAD(p) __builtin_nontemporal_load(p)
-#else
-#define SPEX_EPI_LOAD(p) (*(p))
-#endif
-
-struct HubFold {
-    const int4 *grp;
-    const int2 *fold;
-    unsigned long long *ticket;
-    uint32_t tag;
-};
-
-struct DropArgs {
-    const uint32_t *chunk_eid;
-    const uint8_t *keep;
-    int mode;
-    float keep_prob;
-    uint32_t seed_lo, seed_hi;
-};
-
-// Snapshot tail of the plain launch (the one-call BPR step's layer 1): workgroups [table_wgs, gridDim.x) run no task; they copy
-// the rows of X (= E^0, the launch's gather source: already in the L2s) that the step's T triples name into the compact buffer
-// out[3 T][64] — slot j: row u[j] (j < T), n_user_rows + i_pos[j - T] (T <= j < 2 T), n_user_rows + i_neg[j - 2 T] — so that
-// the BPR kernel behind the propagation, which adds its updates into E^0 while other waves still read it, finds the OLD rows
-// there and layer 1 needs no running-sum epilogue over the whole table.  grid == table_wgs (every other launch): no tail.
-struct SnapArgs {
-    const int64_t *u, *ip, *in;
-    float *out;              // [ceil(3 T / 64) * 64][64]
-    int64_t T;
-    int32_t n_user_rows, n_item_rows;
-    int32_t table_wgs;       // workgroups of the task table (the XCD remap is evaluated against this count)
-};
-
-// One wave per 64 slots: lane k resolves slot slot0 + k, then 256-byte row loads in independent batches of kChunk, each followed
-// by its stores (the chunk loop's shape).  A slot of a triple the BPR kernel skips (an index out of range) never gathers: it
-// re-reads row 0 and stores zeros, as do the slots beyond 3 T of the last wave (the buffer is whole waves long).
-__device__ __forceinline__ void snapshot_rows(const SnapArgs &s, const float *__restrict__ X, int64_t slot0, int lane)
-{
-    const int64_t j = slot0 + lane;
-    int my_row = -1;
-    if (j < 3 * s.T) {
-        const int which = j < s.T ? 0 : (j < 2 * s.T ? 1 : 2);
-        const int64_t t = j - which * s.T;
-        const int64_t u = s.u[t], ip = s.ip[t], in = s.in[t];
-        // (one round trip for the three indices: a short-circuit chain makes the compiler load each behind the test of the one before)
-        const bool ok = (int)(u >= 0) & (int)(u < s.n_user_rows) & (int)(ip >= 0) & (int)(ip < s.n_item_rows) & (int)(in >= 0) & (int)(in < s.n_item_rows);
-        if (ok) my_row = which == 0 ? (int)u : s.n_user_rows + (int)(which == 1 ? ip : in);
-    }
-    const float *__restrict__ Xl = X + lane;
-    float *__restrict__ out = s.out + (size_t)slot0 * 64 + lane;
-#pragma unroll 1
-    for (int b = 0; b < kWave; b += kChunk) {      // (rolled: the tail is 4 batches of code in an instantiation whose loop it must not crowd)
-        float x[kChunk];
-#pragma unroll
-        for (int k = 0; k < kChunk; ++k) {
-            const int r = __builtin_amdgcn_readlane(my_row, b + k);
-            x[k] = Xl[(size_t)(uint32_t)(r < 0 ? 0 : r) * 64];
-        }
-#pragma unroll
-        for (int k = 0; k < kChunk; ++k) {
-            const int r = __builtin_amdgcn_readlane(my_row, b + k);
-            __builtin_nontemporal_store(r < 0 ? 0.0f : x[k], out + (size_t)(b + k) * 64);
-        }
-    }
-}
-
-// EPI 0: Y = y;  1: Y = y (optional), acc_out = (acc_in + y) / epi_div;  2: Y = (y + add_in / epi_div) / out_div.
-// ROWIDS: a task's rows are listed per entry (bin-packed tasks) instead of being adjacent from task.z.
-// FOLD: the hub fold is compiled in.  The unmasked instantiations always carry it (it costs their chunk loop nothing); the
-// edge-dropout ones sit ~20 scalar registers higher (the Philox key schedule lives in SGPRs) and with the fold's operands live across
-// the loop they schedule worse (<0, MASKED> 13.1 -> 15.7 us on Epinion2, a graph without a single hub), so a masked launch takes the
-// FOLD instantiation only on a graph that HAS hubs — where it replaces a ~5 us dependent fix-up launch per product.
+// The d == 64 kernel (chunk_body, spmm_chunk.h: described there) on an fp32 gather table, with the in-kernel hub fold (FOLD).
 template <int EPI, bool MASKED, bool ROWIDS, bool FOLD>
 __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
     // What the prologue reads comes FIRST, 14 dwords of it: this file is compiled with kernel-argument preloading (Makefile), which
@@ -326,317 +202,14 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_kernel(
     float *__restrict__ partial,
     const DropArgs drop, const HubFold hf_args, const SnapArgs snap)
 {
-    __shared__ float s_part[kWgWaves][kWave];  // segment sums of the rows this workgroup combines
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // Every kernel argument the prologue reads, requested in ONE scalar trip: left to itself the compiler loads them where they are
     // first used — behind the tail test, behind the XCD remap, behind the bounds test: three dependent waits in front of the first
     // vector load.
     asm volatile("" ::"s"(n_tasks), "s"(xcd_contiguous), "s"(chunk_stride), "s"(table_wgs), "s"(chunk_off), "s"(chunk_val), "s"(chunk_row),
                  "s"(chunk_mask), "s"(task));
-    // The unmasked plain form may carry a snapshot tail (SnapArgs): whole workgroups behind the table's, decided once, here, on
-    // scalar values; they touch neither s_part nor the hub tickets.  Only these instantiations read `snap`.
-    constexpr bool kTail = EPI == 0 && !MASKED && FOLD;
-    if (kTail && (int)blockIdx.x >= table_wgs) {
-        const int64_t slot0 = ((int64_t)((int)blockIdx.x - table_wgs) * kWgWaves + wave) * kWave;
-        if (slot0 < 3 * snap.T) snapshot_rows(snap, X, slot0, lane);
-        return;
-    }
-    // Workgroups are sorted heaviest-first and dealt round-robin over the 8 XCDs by the dispatcher, which gives every
-    // XCD the same mix of weights: right for a graph that streams from HBM (+14 % on Epinion2x538 over handing XCD 0
-    // all the heavy workgroups).  A graph whose whole source table sits in cache instead prefers each XCD to walk a
-    // contiguous range of workgroups (user rows and item rows of the bipartite graph then gather from different
-    // halves of the table in different L2s: 76 % vs 71 % L2 hits on Epinion2).  Placement is a speed matter only.
-    const int n_wg = kTail ? table_wgs : (int)gridDim.x;       // (the table's workgroups: a tail does not move them)
-    const int wg = xcd_contiguous ? xcd_contiguous_block(blockIdx.x, n_wg) : (int)blockIdx.x;
-    const int tid = wg * kWgWaves + wave;
-    if (tid >= n_tasks) return;  // whole workgroups only (n_tasks is a multiple of kWgWaves)
-    // Implied positions (chunk_stride != 0, bin-packed tables: spex_common.h): task tid's chunks start at chunk tid * chunk_stride
-    // whatever the task record says, so its first super-chunk's metadata — all 64 lanes, the four mask words — is requested HERE, in
-    // the same round trip as the record, instead of behind it; the lanes beyond the task's chunks are cut off once the record is in (a
-    // null task loads and discards: every position below n_tasks * chunk_stride chunks exists, and chunk_stride >= 4).
-    const bool implied = ROWIDS && chunk_stride != 0;
-    uint32_t pre_off = 0u, pre_mask = 0u, pre_eid = 0u;
-    int pre_row = 0;
-    float pre_val = 0.0f;
-    if (implied) {
-        const size_t c0 = (size_t)tid * (size_t)chunk_stride, e = c0 * kChunk + lane;
-        pre_off = __builtin_nontemporal_load(chunk_off + e);
-        pre_val = __builtin_nontemporal_load(chunk_val + e);
-        pre_row = __builtin_nontemporal_load(chunk_row + e);
-        if (MASKED) pre_eid = __builtin_nontemporal_load(drop.chunk_eid + e);
-        pre_mask = __builtin_nontemporal_load(chunk_mask + c0 + (lane & 3));
-    }
-    const int4 t = task[tid];
-    const int kind = t.w & 3;
-    const float *__restrict__ Xl = X + lane;
-    const float *El = (EPI ? epi_in : X) + lane;
-    int row = t.z;
-    float acc = 0.0f;
-
-    // v / div for a wave-uniform divisor, as REAL branches: written `if (div != 1.0f) v = v / div;` the compiler computes the quotient
-    // always and selects (an fp32 division is ~11 vector instructions; two per emitted row in the backward form — 0.4 M of the launch's
-    // 3 M vector instructions on Epinion2, spent on divisors that are 1.0 in most launches).  A power-of-two divisor (L + 1 = 4: the
-    // reference's depth) is one exact multiply — x / 2^k == x * 2^-k bit for bit.  (The empty asm keeps each arm from being speculated.)
-    const float epi_inv = 1.0f / epi_div, out_inv = 1.0f / out_div;      // (once per wave; exact for a power of two)
-    auto scaled = [](float v, float div, float inv) {
-        if (div != 1.0f) {
-            if ((__float_as_uint(div) & 0x007FFFFFu) == 0u) {
-                v = v * inv;
-                asm volatile("" : "+v"(v));
-            } else {
-                v = v / div;
-                asm volatile("" : "+v"(v));
-            }
-        }
-        return v;
-    };
-    auto emit = [&](int r, float y, float e) {
-        const size_t o = (size_t)r * 64 + lane;
-        // outputs are streamed (non-temporal): they should not evict the gather source from the XCD's L2
-        if (EPI == 0) {
-            __builtin_nontemporal_store(y, Y + o);
-        } else if (EPI == 1) {
-            const float s = scaled(e + y, epi_div, epi_inv);
-            if (Y) __builtin_nontemporal_store(y, Y + o);     // both stores after the last use of a loaded value
-            __builtin_nontemporal_store(s, acc_out + o);
-        } else {
-            const float s = scaled(y + scaled(e, epi_div, epi_inv), out_div, out_inv);
-            __builtin_nontemporal_store(s, Y + o);
-        }
-    };
-
-    // Metadata of up to 4 chunks (64 entries) per vector load — lane k holds entry k — handed to the scalar side with
-    // v_readlane.  (Feeding it through s_load instead starves on scalar-cache misses once the matrix streams from
-    // HBM: 29 ms vs 13 ms per launch on a 2^23-node graph.)
-    // A LIST of rows without stored entries (kind 3, bin-packed tables only; <= 64 rows, lane k holds the k-th row id): y = 0, the
-    // epilogue still applies.  Done on the VECTOR side, four rows per instruction (16 lanes x float4 per row), sixteen rows' operands
-    // in flight: taken one row at a time through the scalar emit path (load, wait, store) the list was a chain of up to 64 dependent
-    // round trips — 32 us on the Weibo shape with its 2 441 empty rows, whose epilogue launches took twice as long as its plain ones —
-    // and batching THAT path held sixteen row ids in SGPRs across the chunk loop (+1.5 us on Epinion2's <1> launch).
-    if (ROWIDS && kind == 3) {
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        const int count = t.w >> 4;
-        int my_r = -1;
-        if (lane < count) my_r = implied ? pre_row : chunk_row[(size_t)t.x * kChunk + lane];
-        const int sub = lane & 15, grp = lane >> 4;
-        const f4 zero = (f4)(0.0f);
-        for (int k0 = 0; k0 < count; k0 += 16) {
-            int r[4];
-            f4 e[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                r[j] = __shfl(my_r, (k0 + 4 * j + grp) & 63, kWave);
-                if (k0 + 4 * j + grp >= count) r[j] = -1;
-                e[j] = zero;
-                if (EPI != 0 && r[j] >= 0) e[j] = *reinterpret_cast<const f4 *>(epi_in + (size_t)r[j] * 64 + sub * 4);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (r[j] < 0) continue;
-                const size_t o = (size_t)r[j] * 64 + sub * 4;
-                if (EPI == 0) {
-                    __builtin_nontemporal_store(zero, reinterpret_cast<f4 *>(Y + o));
-                } else if (EPI == 1) {
-                    f4 sv = e[j] + zero;
-                    if (epi_div != 1.0f) sv = sv / epi_div;
-                    if (Y) __builtin_nontemporal_store(zero, reinterpret_cast<f4 *>(Y + o));
-                    __builtin_nontemporal_store(sv, reinterpret_cast<f4 *>(acc_out + o));
-                } else {
-                    f4 ev = e[j];
-                    if (epi_div != 1.0f) ev = ev / epi_div;
-                    f4 sv = zero + ev;
-                    if (out_div != 1.0f) sv = sv / out_div;
-                    __builtin_nontemporal_store(sv, reinterpret_cast<f4 *>(Y + o));
-                }
-            }
-        }
-    }
-    const int n_ch = kind == 3 ? 0 : t.y;              // (kind 3: handled above)
-    // One super-chunk (<= 4 chunks from chunk t.x + sc).  first: the one requested in front of the task record (implied positions) —
-    // bin-packed instantiations run it as a call of its own in front of the loop, so that the requested values are not live across
-    // the loop (as loop-carried values they cost the epilogue forms their 65th and 66th VGPR); a task has more than one super-chunk
-    // only where the packer raised the pack capacity.
-    auto super_chunk = [&](const int sc, const bool first) __attribute__((always_inline)) {
-        const int nc = (n_ch - sc < 4) ? n_ch - sc : 4;  // chunks in this super-chunk (wave-uniform)
-        uint32_t my_off = 0u, my_mask = 0u, own_off = 0u;
-        unsigned long long drop_bits = 0ull;                 // MASKED: entries of this super-chunk that are dropped (wave-uniform)
-        int my_row = 0;
-        float my_val = 0.0f;
-        if (lane < nc * kChunk) {
-            uint32_t eid = 0u;
-            if (first) {
-                my_off = pre_off;
-                my_val = pre_val;
-                my_row = pre_row;
-                if (MASKED) eid = pre_eid;
-            } else {
-                const size_t e = (size_t)(t.x + sc) * kChunk + lane;
-                my_off = __builtin_nontemporal_load(chunk_off + e);   // metadata is read once per launch
-                my_val = __builtin_nontemporal_load(chunk_val + e);
-                if (ROWIDS) my_row = __builtin_nontemporal_load(chunk_row + e);
-                if (MASKED) eid = __builtin_nontemporal_load(drop.chunk_eid + e);
-            }
-            if (MASKED) {
-                bool kept;
-                if (drop.mode == 1) {
-                    kept = drop.keep[eid] != 0;
-                } else {
-                    const float u01 = (float)(philox_first(eid, drop.seed_lo, drop.seed_hi) >> 8) * 5.9604644775390625e-8f;
-                    kept = (u01 + drop.keep_prob) >= 1.0f;
-                }
-                my_val = kept ? my_val / drop.keep_prob : 0.0f;   // values[random_index] / keep_prob, model.py:53
-                own_off = my_off;
-                if (!kept) my_off = 0xFFFFFFFFu;
-            }
-        }
-        if (MASKED) {
-            // a dropped entry re-reads the source row of the first KEPT entry of this super-chunk (fetched anyway, so
-            // it adds +0 and no traffic); if every entry was dropped each keeps its own row (value 0)
-            const bool dropped = my_off == 0xFFFFFFFFu;      // (lanes past the super-chunk hold 0: neither kept nor dropped)
-            drop_bits = __ballot(dropped);
-            const unsigned long long kept_lanes = __ballot(!dropped && lane < nc * kChunk);
-            const int src = kept_lanes ? (int)__builtin_ctzll(kept_lanes) : 0;
-            const uint32_t stand_in = (uint32_t)__builtin_amdgcn_readlane((int)my_off, src);   // wave-uniform
-            if (dropped) my_off = kept_lanes ? stand_in : own_off;
-        }
-        if (first) my_mask = pre_mask;                       // (lane c < 4 holds chunk c's word; words beyond nc are not read)
-        else if (lane < nc) my_mask = __builtin_nontemporal_load(chunk_mask + t.x + sc + lane);
-        float ep[kChunk];
-#pragma unroll
-        for (int u = 0; u < kChunk; ++u) ep[u] = 0.0f;
-        for (int c = 0; c < nc; ++c) {
-            const uint32_t mask = (uint32_t)__builtin_amdgcn_readlane((int)my_mask, c);
-            const uint32_t dbits = MASKED ? (uint32_t)(drop_bits >> (c * kChunk)) & 0xFFFFu : 0u;
-            float x[kChunk];
-#pragma unroll
-            for (int u = 0; u < kChunk; ++u)
-                x[u] = Xl[(size_t)(uint32_t)__builtin_amdgcn_readlane((int)my_off, c * kChunk + u) * 64];
-            // (ep[] lives ACROSS the chunks — declared in front of the loop — and is written only where a row ends: an entry that ends
-            //  no row keeps whatever the register held, which nothing reads.  Defined per chunk, every such entry cost a v_mov to
-            //  zero it, and a chunk without any row end sixteen of them plus the register shuffles of the join: ~0.6 M of the
-            //  1.0 M vector instructions the epilogue forms issue beyond the plain form's 2.1 M on Epinion2)
-            if (EPI != 0 && mask != 0u) {
-                int r = row;
-#pragma unroll
-                for (int u = 0; u < kChunk; ++u) {
-                    if (mask & (1u << u)) {
-                        const int rr = ROWIDS ? __builtin_amdgcn_readlane(my_row, c * kChunk + u) : r;
-                        ep[u] = SPEX_EPI_LOAD(El + (size_t)rr * 64);
-                        ++r;
-                    }
-                }
-            }
-            // A chunk that ends rows waits for ALL of its loads here, once.  gfx9 counts loads and stores in one vmcnt and the
-            // compiler re-derives its waits at every control-flow join: without this, the wait for a row's epilogue operand
-            // (loaded under the mask's branches) became `s_waitcnt vmcnt(0)` placed AFTER the previous row's stores were
-            // issued, i.e. every emitted row waited out its predecessor's store round trip.
-            if (EPI != 0) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0); expcnt / lgkmcnt unconstrained
-            if (EPI == 0 && mask == 0u) {   // no row ends in this chunk (about every second chunk on Epinion2): sixteen fmafs, no per-entry
-                                           // test (plain form only: in the epilogue forms the second copy of the loop costs the 65th VGPR)
-#pragma unroll
-                for (int u = 0; u < kChunk; ++u) {
-                    const float xv = (MASKED && (dbits & (1u << u))) ? 0.0f : x[u];
-                    acc = fmaf(lane_bcast(my_val, c * kChunk + u), xv, acc);
-                }
-                continue;
-            }
-#pragma unroll
-            for (int u = 0; u < kChunk; ++u) {
-                const float xv = (MASKED && (dbits & (1u << u))) ? 0.0f : x[u];     // a dropped entry contributes nothing
-                acc = fmaf(lane_bcast(my_val, c * kChunk + u), xv, acc);
-                if (mask & (1u << u)) {  // only packs of whole rows carry mask bits
-                    emit(ROWIDS ? __builtin_amdgcn_readlane(my_row, c * kChunk + u) : row, acc, ep[u]);
-                    acc = 0.0f;
-                    ++row;
-                }
-            }
-        }
-    };
-    if (ROWIDS) {
-        if (n_ch > 0) {
-            const int nc0 = n_ch < 4 ? n_ch : 4;
-            if (!implied && lane < nc0 * kChunk) {      // the dense layout: the same values, requested behind the record
-                const size_t e = (size_t)t.x * kChunk + lane;
-                pre_off = __builtin_nontemporal_load(chunk_off + e);
-                pre_val = __builtin_nontemporal_load(chunk_val + e);
-                pre_row = __builtin_nontemporal_load(chunk_row + e);
-                if (MASKED) pre_eid = __builtin_nontemporal_load(drop.chunk_eid + e);
-                if (lane < nc0) pre_mask = __builtin_nontemporal_load(chunk_mask + t.x + lane);   // (the table ends with its last chunk)
-            }
-            super_chunk(0, true);
-        }
-        for (int sc = 4; sc < n_ch; sc += 4) super_chunk(sc, false);
-    } else {
-        for (int sc = 0; sc < n_ch; sc += 4) super_chunk(sc, false);
-    }
-    if (kind == 0 && t.y == 0 && t.z >= 0) {  // a row without stored entries: y = 0, the epilogue still applies
-        float e = 0.0f;
-        if (EPI != 0) e = El[(size_t)t.z * 64];
-        emit(t.z, 0.0f, e);
-    }
-    const bool hub = FOLD && kind == 2 && hf_args.tag != 0u;
-    if (kind == 2 && !hub) partial[(size_t)(t.w >> 4) * 64 + lane] = acc;  // hub segment: summed by the fix-up launch
-    if (t.w & 4) {  // this workgroup combines the segments of rows with 65..1024 entries (and of hub groups) through LDS
-        const bool leader = kind == 1 && (t.w & 8);
-        const int slot = (t.w >> 4) & 15, nseg = (t.w >> 8) & 31;
-        int4 hg = make_int4(0, 0, 0, 0);
-        if (hub) hg = hf_args.grp[tid];
-        const bool hub_leader = hub && hg.x != 0;
-        float e = 0.0f;
-        if ((leader || hub_leader) && EPI != 0) e = El[(size_t)t.z * 64];
-        if (kind == 1 && !leader) s_part[slot][lane] = acc;
-        if (hub && !hub_leader) s_part[wave][lane] = acc;
-        __syncthreads();
-        if (leader) {
-            float y = acc;
-            for (int sgi = 1; sgi < nseg; ++sgi) y = y + s_part[slot + sgi][lane];  // segment order: deterministic
-            emit(t.z, y, e);
-        }
-        if (hub_leader) {
-            // A hub's segments are adjacent in the table: this wave and the hg.y - 1 behind it hold consecutive segments of row t.z.
-            // Their sum is ONE partial row of the hub; the hub's groups meet through memory: agent-scope store (write-through: the
-            // groups may run on different XCDs), the wave's own stores acknowledged (explicit vmcnt(0)), a ticket on the hub (an arrival
-            // counter, see below) and the LAST group to arrive adds the partial rows in group
-            // order (whoever is last: the same order, the same bits) and runs the row's epilogue.  No fence (an agent-scope fence on
-            // gfx950 writes back / invalidates the XCD's whole L2), no waiting, no second launch.
-            float y = acc;
-            for (int i = 1; i < hg.y; ++i) y = y + s_part[wave + i][lane];
-            const int2 hf = hf_args.fold[hg.w];
-            bool last = true;
-            if (hf.y > 1) {
-                __hip_atomic_store(partial + (size_t)hg.z * 64 + lane, y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                // the wave's partial-row store is ACKNOWLEDGED (sc1 write-through: visible to every XCD) before lane 0 touches the
-                // ticket: an explicit s_waitcnt vmcnt(0) — a workgroup-scope release fence emits no vmcnt wait on gfx950.  One wave =
-                // one instruction stream, so the wait covers all 64 lanes' stores.  tests/test_isa_folds.py asserts it in the ISA.
-                __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0); expcnt / lgkmcnt unconstrained
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // (compiler ordering only)
-                // The ticket is a COUNTER that is never reset: the handle zeroes it at creation and every launch that folds adds
-                // exactly hf.y arrivals to it (launches on one handle are ordered: they share its scratch), so the group whose
-                // increment lands on a multiple of hf.y is the launch's last — ONE read-modify-write round trip through memory on the
-                // hub's tail.  (Round 3 carried a per-launch tag in the word: a load, a compare-exchange and often an add — three
-                // dependent agent-scope round trips, ~2 us of the hub rows' 5.)  A replay from a captured graph adds hf.y again.
-                unsigned long long arrived = 0ull;
-                if (lane == 0) arrived = __hip_atomic_fetch_add(hf_args.ticket + hg.w, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull;
-                const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(arrived % (unsigned long long)hf.y));
-                last = lo == 0u;
-                if (last) {
-                    y = 0.0f;
-                    const float *pr = partial + (size_t)hf.x * 64 + lane;
-                    int q = 0;
-                    for (; q + 8 <= hf.y; q += 8) {          // eight partial rows in flight (the kernel lives in 64 VGPRs)
-                        float v[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) v[u] = __hip_atomic_load(pr + (size_t)(q + u) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) y = y + v[u];
-                    }
-                    for (; q < hf.y; ++q) y = y + __hip_atomic_load(pr + (size_t)q * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            if (last) emit(t.z, y, e);
-        }
-    }
+    chunk_body<float, EPI, MASKED, ROWIDS, FOLD>(chunk_off, chunk_val, chunk_row, chunk_mask, task, n_tasks, xcd_contiguous, chunk_stride,
+                                                 table_wgs, X, Y, ChunkSide<float>{out_div, 1.0f / out_div},
+                                                 epi_in, epi_div, acc_out, partial, drop, hf_args, snap);
 }
 
 // The same kernel for wider embeddings.
@@ -664,12 +237,7 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_wide_kernel(
     __shared__ float s_part[kWgWaves][kRow];  // segment sums of the rows this workgroup combines
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // Workgroups are sorted heaviest-first and dealt round-robin over the 8 XCDs by the dispatcher, which gives every
-    // XCD the same mix of weights: right for a graph that streams from HBM (+14 % on Epinion2x538 over handing XCD 0
-    // all the heavy workgroups).  A graph whose whole source table sits in cache instead prefers each XCD to walk a
-    // contiguous range of workgroups (user rows and item rows of the bipartite graph then gather from different
-    // halves of the table in different L2s: 76 % vs 71 % L2 hits on Epinion2).  Placement is a speed matter only.
-    const int wg = xcd_contiguous ? xcd_contiguous_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int wg = xcd_contiguous ? xcd_contiguous_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;     // (placement: see chunk_body)
     const int tid = wg * kWgWaves + wave;
     if (tid >= n_tasks) return;  // whole workgroups only (n_tasks is a multiple of kWgWaves)
     const int4 t = task[tid];
@@ -697,9 +265,7 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_wide_kernel(
         }
     };
 
-    // Metadata of up to 4 chunks (64 entries) per vector load — lane k holds entry k — handed to the scalar side with
-    // v_readlane.  (Feeding it through s_load instead starves on scalar-cache misses once the matrix streams from
-    // HBM: 29 ms vs 13 ms per launch on a 2^23-node graph.)
+    // (metadata of up to 4 chunks per vector load, handed to the scalar side with v_readlane: see chunk_body)
     const int n_ch = kind == 3 ? 0 : t.y;              // (kind 3: a list of rows without stored entries, handled after the loop)
     for (int sc = 0; sc < n_ch; sc += 4) {
         const int nc = (n_ch - sc < 4) ? n_ch - sc : 4;  // chunks in this super-chunk (wave-uniform)
@@ -712,30 +278,9 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_wide_kernel(
             my_off = __builtin_nontemporal_load(chunk_off + e);   // metadata is read once per launch
             my_val = __builtin_nontemporal_load(chunk_val + e);
             if (ROWIDS) my_row = __builtin_nontemporal_load(chunk_row + e);
-            if (MASKED) {
-                const uint32_t eid = __builtin_nontemporal_load(drop.chunk_eid + e);
-                bool kept;
-                if (drop.mode == 1) {
-                    kept = drop.keep[eid] != 0;
-                } else {
-                    const float u01 = (float)(philox_first(eid, drop.seed_lo, drop.seed_hi) >> 8) * 5.9604644775390625e-8f;
-                    kept = (u01 + drop.keep_prob) >= 1.0f;
-                }
-                my_val = kept ? my_val / drop.keep_prob : 0.0f;   // values[random_index] / keep_prob, model.py:53
-                own_off = my_off;
-                if (!kept) my_off = 0xFFFFFFFFu;
-            }
+            if (MASKED) own_off = drop_lane(drop, __builtin_nontemporal_load(drop.chunk_eid + e), my_val, my_off);
         }
-        if (MASKED) {
-            // a dropped entry re-reads the source row of the first KEPT entry of this super-chunk (fetched anyway, so
-            // it adds +0 and no traffic); if every entry was dropped each keeps its own row (value 0)
-            const bool dropped = my_off == 0xFFFFFFFFu;      // (lanes past the super-chunk hold 0: neither kept nor dropped)
-            drop_bits = __ballot(dropped);
-            const unsigned long long kept_lanes = __ballot(!dropped && lane < nc * kChunk);
-            const int src = kept_lanes ? (int)__builtin_ctzll(kept_lanes) : 0;
-            const uint32_t stand_in = (uint32_t)__builtin_amdgcn_readlane((int)my_off, src);   // wave-uniform
-            if (dropped) my_off = kept_lanes ? stand_in : own_off;
-        }
+        if (MASKED) drop_bits = drop_stand_in(lane < nc * kChunk, own_off, my_off);
         if (lane < nc) my_mask = __builtin_nontemporal_load(chunk_mask + t.x + sc + lane);
         for (int c = 0; c < nc; ++c) {
             const uint32_t mask = (uint32_t)__builtin_amdgcn_readlane((int)my_mask, c);
@@ -990,37 +535,28 @@ void launch_chunk_v(bool masked, bool row_ids, dim3 grid, dim3 block, hipStream_
                     float *Y, const float *epi_in, float epi_div, float out_div, float *acc_out, const DropArgs &da,
                     int xcd_contig, const HubFold &hub, const SnapArgs &snap)
 {
+#define SPEX_D64(M, R, F)                                                                                              \
+    hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, F>), grid, block, 0, stream, g->chunk_off, g->chunk_val, g->chunk_row,   \
+                       g->chunk_mask, g->task, g->n_tasks, xcd_contig, g->chunk_stride, snap.table_wgs, X, Y, epi_in, epi_div, \
+                       out_div, acc_out, g->partial, da, hub, snap)
 #define SPEX_GO(M, R)                                                                                                  \
     do {                                                                                                               \
-        if (V == 1 && (!M || hub.tag != 0u))                                                                           \
-            hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, true>), grid, block, 0, stream, g->chunk_off,             \
-                               g->chunk_val, g->chunk_row, g->chunk_mask, g->task, g->n_tasks, xcd_contig,             \
-                               g->chunk_stride, snap.table_wgs, X, Y, epi_in, epi_div, out_div, acc_out, g->partial,   \
-                               da, hub, snap);                                                                         \
-        else if (V == 1)                                                                                               \
-            hipLaunchKernelGGL((spmm_chunk_kernel<EPI, M, R, !M>), grid, block, 0, stream, g->chunk_off,               \
-                               g->chunk_val, g->chunk_row, g->chunk_mask, g->task, g->n_tasks, xcd_contig,             \
-                               g->chunk_stride, snap.table_wgs, X, Y, epi_in, epi_div, out_div, acc_out, g->partial,   \
-                               da, hub, snap);                                                                         \
+        if (V == 1 && (!M || hub.tag != 0u)) SPEX_D64(M, R, true);                                                     \
+        else if (V == 1) SPEX_D64(M, R, !M);                                                                           \
         else                                                                                                           \
             hipLaunchKernelGGL((spmm_chunk_wide_kernel<EPI, M, R, (V == 1 ? 2 : V)>), grid, block, 0, stream, X,       \
                                g->chunk_off, g->chunk_val, g->chunk_mask, g->chunk_row, g->task, g->n_tasks, Y, epi_in, \
                                epi_div, out_div, acc_out, g->partial, da, xcd_contig);                                 \
     } while (0)
     if (masked) {
-        if (row_ids) {
-            SPEX_GO(true, true);
-        } else {
-            SPEX_GO(true, false);
-        }
+        if (row_ids) SPEX_GO(true, true);
+        else SPEX_GO(true, false);
     } else {
-        if (row_ids) {
-            SPEX_GO(false, true);
-        } else {
-            SPEX_GO(false, false);
-        }
+        if (row_ids) SPEX_GO(false, true);
+        else SPEX_GO(false, false);
     }
 #undef SPEX_GO
+#undef SPEX_D64
 }
 
 template <int EPI>
@@ -1060,12 +596,6 @@ struct TimerBracket {
     }
 };
 
-// Workgroups of the chunked task table's launch: whole 16-wave workgroups, a multiple of the XCD count so the remap is a bijection.
-inline int64_t chunk_table_wgs(const spex_graph *g)
-{
-    return (((int64_t)g->n_tasks + kWgWaves - 1) / kWgWaves + 7) / 8 * 8;
-}
-
 // snap: the plain d == 64 unmasked launch also copies the triples' rows of X into snap->out (SnapArgs; table_wgs is filled in here).
 int launch_spmm(const spex_graph *g, const float *X, float *Y, const float *add_in, float add_div, const float *acc_in,
                 float *acc_out, float acc_div, int32_t d, hipStream_t stream, float out_div = 1.0f, const SnapArgs *snap = nullptr)
@@ -1101,15 +631,8 @@ int launch_spmm(const spex_graph *g, const float *X, float *Y, const float *add_
     if (tm && tm->open) tm->launches[tm->used]++;
     std::unique_lock<std::mutex> scratch_lock;   // (held until the launches below are queued)
     if ((fast ? g->n_hub > 0 : g->n_long > 0) || snap) {   // this launch writes the handle's scratch (the snapshot buffer is scratch too): order it behind its last user
-        spex_graph *gm = const_cast<spex_graph *>(g);
-        scratch_lock = std::unique_lock<std::mutex>(gm->scratch_mu);
-        if (gm->scratch_used && gm->scratch_stream != stream) {
-            if (!gm->scratch_ev) SPEX_HIP(hipEventCreateWithFlags(&gm->scratch_ev, hipEventDisableTiming));
-            SPEX_HIP(hipEventRecord(gm->scratch_ev, gm->scratch_stream));
-            SPEX_HIP(hipStreamWaitEvent(stream, gm->scratch_ev, 0));
-        }
-        gm->scratch_stream = stream;
-        gm->scratch_used = true;
+        const int rc = order_scratch(g, stream, scratch_lock);
+        if (rc) return rc;
     }
     if (fast) {
         // (rows are moved as float4 where a wave handles several rows per instruction: every table 16-byte aligned — any row of a
@@ -1117,9 +640,7 @@ int launch_spmm(const spex_graph *g, const float *X, float *Y, const float *add_
         SPEX_CHECK_ARG(((((uintptr_t)X) | ((uintptr_t)Y) | ((uintptr_t)add_in) | ((uintptr_t)acc_in) | ((uintptr_t)acc_out)) & 15) == 0,
                        "spex_spmm_f32: X / Y / add_in / acc_in / acc_out must be 16-byte aligned");
         const int xcd_contig = ((int64_t)g->n_cols * d * 4 <= (int64_t)16 << 20) ? 1 : 0;  // source table <= 16 MiB
-        DropArgs da;
-        da.chunk_eid = g->chunk_eid; da.keep = g->keep; da.mode = g->mask_mode; da.keep_prob = g->keep_prob;
-        da.seed_lo = (uint32_t)g->seed; da.seed_hi = (uint32_t)(g->seed >> 32);
+        const DropArgs da = drop_args(g);
         // rows beyond kWgRowMax entries: folded inside the d == 64 launch (SPEX_HUB_FOLD=0: by the fix-up launch, as for the wide kernels)
         const char *fold_sw = g->n_hub > 0 ? getenv("SPEX_HUB_FOLD") : nullptr;      // (read per launch: the tests run both forms in one process)
         const bool fold_env = !(fold_sw && fold_sw[0] == '0');
@@ -1148,12 +669,28 @@ int launch_spmm(const spex_graph *g, const float *X, float *Y, const float *add_
     return SPEX_OK;
 }
 
-int ensure_partial(spex_graph *g, int32_t d)
+}  // namespace
+
+int spex::order_scratch(const spex_graph_t *g, hipStream_t stream, std::unique_lock<std::mutex> &lock)
+{
+    spex_graph *gm = const_cast<spex_graph *>(g);
+    lock = std::unique_lock<std::mutex>(gm->scratch_mu);
+    if (gm->scratch_used && gm->scratch_stream != stream) {
+        if (!gm->scratch_ev) SPEX_HIP(hipEventCreateWithFlags(&gm->scratch_ev, hipEventDisableTiming));
+        SPEX_HIP(hipEventRecord(gm->scratch_ev, gm->scratch_stream));
+        SPEX_HIP(hipStreamWaitEvent(stream, gm->scratch_ev, 0));
+    }
+    gm->scratch_stream = stream;
+    gm->scratch_used = true;
+    return SPEX_OK;
+}
+
+int spex::ensure_partial(spex_graph_t *g, int32_t d)
 {
     const int64_t need = (int64_t)g->n_seg * d;
     if (need <= g->partial_cap) return SPEX_OK;
     // Only reached for d > 64 on a graph with long rows, on the first call at that d (allocates: do it once outside
-    // any stream capture).
+    // any stream capture): the handle is created with its scratch sized for d == 64.
     SPEX_HIP(hipDeviceSynchronize());
     if (g->partial) SPEX_HIP(hipFree(g->partial));
     g->partial = nullptr;
@@ -1161,8 +698,6 @@ int ensure_partial(spex_graph *g, int32_t d)
     g->partial_cap = need;
     return SPEX_OK;
 }
-
-}  // namespace
 
 extern "C" int spex_spmm_f32(const spex_graph_t *g, const float *X, float *Y, const float *add_in, float add_div,
                              const float *acc_in, float *acc_out, float acc_div, int32_t d, void *stream)

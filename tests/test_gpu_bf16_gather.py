@@ -113,19 +113,19 @@ def test_cast_equals_torch_bit_for_bit():
 FORMS = [("plain", {}), ("acc1", {"acc_div": 1.0}), ("acc4", {"acc_div": 4.0}), ("add4", {"add_div": 4.0}), ("add3", {"add_div": 3.0})]
 
 
-def run_form(c, form, kw, bf16, with_y16=True):
+def run_form(c, form, kw, bf16, with_y16=True, n=N):
     """One launch of `form` -> dict of its outputs.  The running-sum forms also ask for Y (and Y16): every output at once."""
     out = {}
-    Y = torch.full((N, D), float("nan"), device=DEV)
+    Y = torch.full((n, D), float("nan"), device=DEV)
     args = {"Y": Y}
     if form.startswith("acc"):
-        out["acc_out"] = args["acc_out"] = torch.full((N, D), float("nan"), device=DEV)
+        out["acc_out"] = args["acc_out"] = torch.full((n, D), float("nan"), device=DEV)
         args.update(acc_in=c.E, acc_div=kw["acc_div"])
     elif form.startswith("add"):
         args.update(add_in=c.E, add_div=kw["add_div"])
     if bf16:
         if with_y16:
-            out["Y16"] = args["Y16"] = torch.zeros((N, D), dtype=BF16, device=DEV)
+            out["Y16"] = args["Y16"] = torch.zeros((n, D), dtype=BF16, device=DEV)
         c.graph.spmm_bf16(c.X16, **args)
     else:
         c.graph.spmm(c.Xw, **args)
@@ -159,6 +159,45 @@ def test_product_is_the_fp32_launch_on_the_widened_table_bit_for_bit(ctx, form, 
         assert torch.equal(got["acc_out"][empty], c.E[empty] / kw["acc_div"])       # (/1 and /4: exact)
     elif form == "add4":
         assert torch.equal(got["Y"][empty], c.E[empty] / 4.0)
+
+
+def test_adjacent_row_tasks_of_a_table_beyond_the_caches_bit_for_bit():
+    """The ROWIDS = false instantiations (a task's rows adjacent from task.z: tables whose fp32 source exceeds 16 MiB, n_cols > 65 536),
+    which the square graph above — bin-packed, 1 600 columns — never launches: 400 x 70 000, degrees 0..63 with rows of 0, 1, 64, 65,
+    700, 1 024 and 1 025 entries planted, every form under every mask mode."""
+    from spex_amd.graph import SpexGraph, cast_bf16
+    n_rows, n_cols = 400, 70000
+    rng = np.random.default_rng(70000)
+    deg = rng.integers(0, 64, n_rows)
+    deg[:7] = [0, 1, 64, 65, 700, 1024, 1025]
+    rowptr = np.zeros(n_rows + 1, np.int64)
+    np.cumsum(deg, out=rowptr[1:])
+    col = np.concatenate([np.sort(rng.choice(n_cols, int(k), replace=False)) for k in deg]).astype(np.int32)
+    val = (rng.uniform(1e-3, 0.2, len(col)) * rng.choice([-1.0, 1.0], len(col))).astype(np.float32)
+    c = Ctx()
+    c.graph = SpexGraph(rowptr.astype(np.int32), col, val, n_cols=n_cols)
+    try:
+        gen = torch.Generator().manual_seed(17)
+        c.X16 = cast_bf16((torch.randn(n_cols, D, generator=gen) * 0.05).to(DEV))
+        c.Xw = c.X16.float()
+        c.E = (torch.randn(n_rows, D, generator=gen) * 0.05).to(DEV)
+        c.keep = (torch.rand(len(col), generator=torch.Generator().manual_seed(11)) < 0.3).to(torch.uint8).to(DEV)
+        short = torch.from_numpy(deg <= 1024).to(DEV)
+        assert int((~short).sum()) == 1
+        for mode in (0, 1, 2):
+            set_mask(c, mode)
+            for form, kw in FORMS:
+                ref = run_form(c, form, kw, bf16=False, n=n_rows)
+                got = run_form(c, form, kw, bf16=True, n=n_rows)
+                again = run_form(c, form, kw, bf16=True, n=n_rows)
+                for k in ref:
+                    assert not torch.isnan(got[k]).any(), f"{form} mode {mode}: rows of {k} were not written"
+                    assert torch.equal(bits(got[k])[short], bits(ref[k])[short]), f"{form} mode {mode}: {k} differs from spex_spmm_f32 on Xw"
+                assert same_bits(got["Y16"], got["Y"].to(BF16)), f"{form} mode {mode}: Y16 is not bf16(Y)"
+                for k in got:
+                    assert same_bits(got[k], again[k]), f"{form} mode {mode}: two runs differ in {k}"
+    finally:
+        c.graph.close()
 
 
 def test_single_outputs_match_the_all_outputs_launch(ctx):
