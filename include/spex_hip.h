@@ -73,6 +73,12 @@ int spex_graph_pack_digest(const int32_t *h_rowptr, const int32_t *h_col, const 
  * (the last one shorter, the workgroup topped up with ordinary tasks); a hub's scratch rows are consecutive. */
 int spex_graph_pack_hub_table(const int32_t *h_rowptr, const int32_t *h_col, const float *h_val, int32_t n_rows, int32_t n_cols,
                               int64_t nnz, int32_t *out, int64_t cap, int64_t *n_out);
+/* HOST ONLY: the row-head table the handle would carry — a fixed-stride copy of every row's first min(entries, *stride) stored
+ * entries in CSR order, padded with column 0 / value 0, row r at slot r * *stride (what lets the one-call BPR step's fused launch ask
+ * for a row's first entries by the row id alone).  *n_out = slots needed (n_rows * *stride), 0 where none is built: source tables
+ * above 16 MiB, rows beyond 1 024 entries, SPEX_ROW_HEADS=0 (read at creation).  Call with cap = 0 to size. */
+int spex_graph_pack_row_heads(const int32_t *h_rowptr, const int32_t *h_col, const float *h_val, int32_t n_rows, int32_t n_cols,
+                              int64_t nnz, int32_t *out_col, float *out_val, int64_t cap, int64_t *n_out, int32_t *stride);
 /* n_rows, n_cols, nnz, number of long rows, number of long-row segments (any pointer may be NULL) */
 int spex_graph_info(const spex_graph_t *g, int32_t *n_rows, int32_t *n_cols, int64_t *nnz, int32_t *n_long_rows,
                     int32_t *n_segments);

@@ -10,6 +10,7 @@
 // rows are cache hits: consecutive entries share their row; algorithmic bytes nnz (4d + 12) + n_rows 4d).  The softmax
 // streams 8-12 B per entry but is issue-bound (measured, see its kernel).  Per-edge arrays are addressed by edge id so
 // that a graph and its transposed copy (built with the permutation as h_edge_id) read and write the same array.
+#include <algorithm>
 #include <mutex>
 
 #include "spex_common.h"
@@ -35,10 +36,12 @@ __device__ __forceinline__ float group_max(float v)
 }
 
 // ---- values: CSR copy (generic SpMM path) and chunked copy (d = 64 / 128 / 256 path); padding entries keep value 0
-// one launch refreshes both copies
+// one launch refreshes both copies, and the row heads (head_val: row r's first entries at r * kRowHead, the tail 0) where the handle
+// has them — the fused BPR launch reads a row's first segment from there, so they follow the values in the same call
 __global__ void set_values_kernel(float *__restrict__ val, const int32_t *__restrict__ edge_id, int64_t nnz,
                                   float *__restrict__ chunk_val, const uint32_t *__restrict__ chunk_eid,
-                                  const uint8_t *__restrict__ chunk_pad, int64_t n_entries, const float *__restrict__ src)
+                                  const uint8_t *__restrict__ chunk_pad, int64_t n_entries, const float *__restrict__ src,
+                                  float *__restrict__ head_val, const int32_t *__restrict__ rowptr, int64_t n_head)
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     for (int64_t e = first; e < nnz; e += stride) val[e] = src[edge_id ? edge_id[e] : e];
@@ -46,6 +49,11 @@ __global__ void set_values_kernel(float *__restrict__ val, const int32_t *__rest
         const uint32_t n_pad = chunk_pad[k / kChunk];
         const bool pad = (uint32_t)(k % kChunk) >= (uint32_t)kChunk - n_pad;
         chunk_val[k] = pad ? 0.0f : src[chunk_eid[k]];
+    }
+    for (int64_t k = first; k < n_head; k += stride) {
+        const int64_t r = k / kRowHead;
+        const int32_t e = rowptr[r] + (int32_t)(k % kRowHead);
+        head_val[k] = e < rowptr[r + 1] ? src[edge_id ? edge_id[e] : e] : 0.0f;
     }
 }
 
@@ -256,8 +264,10 @@ extern "C" int spex_graph_set_values(spex_graph_t *g, const float *d_val, int64_
     if (g->nnz == 0) return SPEX_OK;
     const int threads = kWave * kWavesPerBlock;
     const int64_t n_entries = g->n_chunks * kChunk;
-    hipLaunchKernelGGL(set_values_kernel, dim3(stream_grid(n_entries > g->nnz ? n_entries : g->nnz, threads)), dim3(threads), 0,
-                       (hipStream_t)stream, g->val, g->edge_id, g->nnz, g->chunk_val, g->chunk_eid, g->chunk_pad, n_entries, d_val);
+    const int64_t n_head = g->head_val ? (int64_t)g->n_rows * kRowHead : 0;
+    hipLaunchKernelGGL(set_values_kernel, dim3(stream_grid(std::max(std::max(n_entries, g->nnz), n_head), threads)), dim3(threads), 0,
+                       (hipStream_t)stream, g->val, g->edge_id, g->nnz, g->chunk_val, g->chunk_eid, g->chunk_pad, n_entries, d_val,
+                       g->head_val, g->rowptr, n_head);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

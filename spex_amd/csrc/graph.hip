@@ -68,7 +68,7 @@ extern "C" int spex_graph_destroy(spex_graph_t *g)
     if (!g) return SPEX_OK;
     void *ptrs[] = {g->rowptr, g->col, g->val, g->edge_id, g->seg_beg, g->seg_end, g->long_row, g->long_seg0, g->partial,
                     g->task, g->chunk_off, g->chunk_val, g->chunk_mask, g->chunk_eid, g->chunk_row, g->hub_row, g->hub_seg0, g->row_of, g->tile_row, g->chunk_pad, g->wg_rows,
-                    g->hub_grp, g->hub_fold, g->hub_ticket, g->snap, g->loss_cell};
+                    g->hub_grp, g->hub_fold, g->hub_ticket, g->snap, g->loss_cell, g->head_col, g->head_val};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (g->scratch_ev) (void)hipEventDestroy(g->scratch_ev);
@@ -78,7 +78,8 @@ extern "C" int spex_graph_destroy(spex_graph_t *g)
 
 static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, const float *h_val, const int32_t *h_edge_id, int32_t n_rows,
                              int32_t n_cols, int64_t nnz, int32_t flags, spex_graph_t **out, uint64_t *digest = nullptr,
-                             std::vector<int32_t> *hub_dump = nullptr);
+                             std::vector<int32_t> *hub_dump = nullptr, std::vector<int32_t> *head_col_dump = nullptr,
+                             std::vector<float> *head_val_dump = nullptr);
 
 // Host only (no device call): the fingerprint of everything spex_graph_create would upload for this matrix — FNV-1a hashes of the
 // task table, the chunk arrays, the segment / hub tables — so that a binding, or the CPU test-suite, can check that the threaded
@@ -108,6 +109,27 @@ extern "C" int spex_graph_pack_hub_table(const int32_t *h_rowptr, const int32_t 
     return SPEX_OK;
 }
 
+// Host only: the row-head table spex_graph_create would upload (spex_common.h: head_col) — n_rows * *stride (column, value) slots,
+// row r's first entries at r * *stride; *n_out = slots needed, 0 where the handle builds none (a table that streams from HBM, hub
+// rows, SPEX_ROW_HEADS=0).  Call with cap = 0 to size.
+extern "C" int spex_graph_pack_row_heads(const int32_t *h_rowptr, const int32_t *h_col, const float *h_val, int32_t n_rows, int32_t n_cols,
+                                         int64_t nnz, int32_t *out_col, float *out_val, int64_t cap, int64_t *n_out, int32_t *stride)
+{
+    SPEX_CHECK_ARG(n_out && stride && ((out_col && out_val) || cap == 0), "spex_graph_pack_row_heads: NULL output");
+    spex_graph_t *unused = nullptr;
+    uint64_t digest[8];
+    std::vector<int32_t> hc;
+    std::vector<float> hv;
+    if (int rc = graph_create_impl(h_rowptr, h_col, h_val, nullptr, n_rows, n_cols, nnz, 0, &unused, digest, nullptr, &hc, &hv)) return rc;
+    *n_out = (int64_t)hc.size();
+    *stride = spex::kRowHead;
+    if (cap >= (int64_t)hc.size() && !hc.empty()) {
+        std::copy(hc.begin(), hc.end(), out_col);
+        std::copy(hv.begin(), hv.end(), out_val);
+    }
+    return SPEX_OK;
+}
+
 extern "C" int spex_graph_create(const int32_t *h_rowptr, const int32_t *h_col, const float *h_val,
                                  const int32_t *h_edge_id, int32_t n_rows, int32_t n_cols, int64_t nnz,
                                  spex_graph_t **out)
@@ -124,7 +146,8 @@ static uint64_t fnv1a(const std::vector<T> &v, uint64_t h = 1469598103934665603u
 }
 
 static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, const float *h_val, const int32_t *h_edge_id, int32_t n_rows,
-                             int32_t n_cols, int64_t nnz, int32_t flags, spex_graph_t **out, uint64_t *digest, std::vector<int32_t> *hub_dump)
+                             int32_t n_cols, int64_t nnz, int32_t flags, spex_graph_t **out, uint64_t *digest, std::vector<int32_t> *hub_dump,
+                             std::vector<int32_t> *head_col_dump, std::vector<float> *head_val_dump)
 {
     SPEX_CHECK_ARG(out, "spex_graph_create: out is NULL");
     *out = nullptr;
@@ -564,11 +587,32 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
     g->n_tasks = (int32_t)task.size();
     g->tile_rows = tile_rows;
     g->n_wgs = (int32_t)wg_rows.size();
+    // Row heads (spex_common.h: head_col) for the handles that can take the fused BPR step: a bin-packed table without hub rows.
+    // SPEX_ROW_HEADS=0, read here at creation like SPEX_PACK_IMPLIED: none (the tests and the A/B timings build both).
+    std::vector<int32_t> head_col;
+    std::vector<float> head_val;
+    {
+        const char *heads_sw = getenv("SPEX_ROW_HEADS");
+        const bool wanted = !digest || head_col_dump;      // (the digest and hub-table exports upload nothing and hash none of it)
+        if (wanted && g->row_ids && hub_row.empty() && nnz > 0 && !(heads_sw && heads_sw[0] == '0')) {
+            head_col.assign((size_t)n_rows * spex::kRowHead, 0);
+            head_val.assign((size_t)n_rows * spex::kRowHead, 0.0f);
+            parallel_parts(n_thr, [&](int p) {
+                const int32_t r_lo = (int32_t)((int64_t)n_rows * p / n_thr), r_hi = (int32_t)((int64_t)n_rows * (p + 1) / n_thr);
+                for (int32_t r = r_lo; r < r_hi; ++r) {
+                    const int32_t b = h_rowptr[r], n = std::min(h_rowptr[r + 1] - b, (int32_t)spex::kRowHead);
+                    std::copy(h_col + b, h_col + b + n, head_col.begin() + (size_t)r * spex::kRowHead);
+                    std::copy(h_val + b, h_val + b + n, head_val.begin() + (size_t)r * spex::kRowHead);
+                }
+            });
+        }
+    }
     if (getenv("SPEX_DEBUG_PACK"))
-        fprintf(stderr, "[spex] graph %d x %d nnz %lld: %d tasks = %d workgroups, %lld chunks (%.1f %% padding), tile mode %d (%d workgroups), chunk stride %d, chunk table %lld bytes\n",
+        fprintf(stderr, "[spex] graph %d x %d nnz %lld: %d tasks = %d workgroups, %lld chunks (%.1f %% padding), tile mode %d (%d workgroups), chunk stride %d, chunk table %lld bytes, row heads %lld bytes\n",
                 n_rows, n_cols, (long long)nnz, (int)task.size(), (int)task.size() / spex::kWgWaves, (long long)c_mask.size(),
                 nnz ? 100.0 * ((double)c_mask.size() * spex::kChunk - (double)nnz) / (double)nnz : 0.0, tile_rows, g->n_wgs, g->chunk_stride,
-                (long long)(c_off.size() * 4 + c_val.size() * 4 + c_eid.size() * 4 + c_row.size() * 4 + c_mask.size() * 4 + c_pad.size()));
+                (long long)(c_off.size() * 4 + c_val.size() * 4 + c_eid.size() * 4 + c_row.size() * 4 + c_mask.size() * 4 + c_pad.size()),
+                (long long)(head_col.size() * 4 + head_val.size() * 4));
     g->n_chunks = (int64_t)c_mask.size();
     g->n_hub = (int32_t)hub_row.size();
     g->n_hub_tasks = (int32_t)hub_grp.size();
@@ -600,6 +644,8 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
                 hub_dump->push_back(f.y);
             }
         }
+        if (head_col_dump) head_col_dump->swap(head_col);
+        if (head_val_dump) head_val_dump->swap(head_val);
         digest[0] = fnv1a(task);
         digest[1] = fnv1a(c_off);
         digest[2] = fnv1a(c_val);
@@ -630,7 +676,9 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
         (rc = upload(&g->hub_row, hub_row.data(), hub_row.size())) ||
         (rc = upload(&g->hub_seg0, hub_seg0.data(), hub_seg0.size())) ||
         (rc = upload(&g->hub_grp, hub_grp.data(), hub_grp.size())) ||
-        (rc = upload(&g->hub_fold, hub_fold.data(), hub_fold.size()))) {
+        (rc = upload(&g->hub_fold, hub_fold.data(), hub_fold.size())) ||
+        (rc = upload(&g->head_col, head_col.data(), head_col.size())) ||
+        (rc = upload(&g->head_val, head_val.data(), head_val.size()))) {
         spex_graph_destroy(g);
         return rc;
     }

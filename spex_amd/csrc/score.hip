@@ -160,6 +160,11 @@ __global__ __launch_bounds__(kWave *kScoreWaves) void bpr_layers_kernel(
 //            indices of a triple are loaded together, and the (col, val) of a wave's NEXT item is requested before the current
 //            item's gathers, so only the first item pays that trip.  (32 gathers in flight were built and measured: faster
 //            while one workgroup runs per CU, slower at two — its 62 VGPRs cost more than the depth saves)
+//            With ROW HEADS on the handle (spex_common.h: head_col; the form above is the one without) the first item does not pay
+//            it either: wave j < 12 owns segment 0 of slot row j whatever the degrees are, and asks for the row's first kRowHead
+//            entries at row * kRowHead in the same trip as rowptr — indices -> (rowptr, head) -> gathers.  Only the later segments
+//            (rows beyond 64 entries) are numbered; they go to waves 12 .. 15, then 0, 1, ... round robin, one item ahead as before.
+//            The segment sum of (row j, segment s) goes to LDS slot 16 j + s on both forms.
 //   Phase B  behind ONE barrier that every wave reaches, wave k < kFuseTriples owns triple k: each of its rows is y = seg_0;
 //            y = y + seg_1; ... in segment order (no segment: 0) — the association of spmm_chunk_kernel / spmm_rowlist_kernel for
 //            every row of up to kWgRowMax entries, so y is the whole-graph launch's row bit for bit (graphs with longer rows keep
@@ -212,10 +217,11 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
     const int64_t *__restrict__ u_idx, const int64_t *__restrict__ p_idx, const int64_t *__restrict__ n_idx, const int32_t *__restrict__ rowptr,
     int64_t T, int64_t n_user_rows, int64_t n_item_rows,
     const int32_t *__restrict__ col, const float *__restrict__ val, const float *__restrict__ Xg,
-    const float *__restrict__ ts, const float *__restrict__ t0, const float *__restrict__ t1, float div, float *table_w,
+    const float *__restrict__ ts, const float *__restrict__ t0, const float *__restrict__ t1,
+    const int32_t *__restrict__ head_col, const float *__restrict__ head_val, float div, float *table_w,
     float a_coef, float b_coef, float *loss_sum, unsigned long long *loss_cells)
 {
-    __shared__ float s_seg[kFuseSegs][kWave];
+    __shared__ float s_seg[kFuseSegs][kWave];          // segment s of slot row j: slot j * kWgWaves + s
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t t_first = (int64_t)blockIdx.x * kFuseTriples;
@@ -225,23 +231,41 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
         const int64_t t = t_first + k;
         if (t < T) {
             // the three indices in ONE round trip: a short-circuit chain makes the compiler load each index behind the test of the one before
-            const int64_t u = u_idx[t], ip = p_idx[t], in = n_idx[t];
-            if ((int)(u >= 0) & (int)(u < n_user_rows) & (int)(ip >= 0) & (int)(ip < n_item_rows) & (int)(in >= 0) & (int)(in < n_item_rows)) {
+            int64_t u = u_idx[t], ip = p_idx[t], in = n_idx[t];
+            asm volatile("" : "+v"(u), "+v"(ip), "+v"(in));        // (all three issued before the first is tested: the scheduler had moved a test between them)
+            if ((int)(u >= 0) & (int)(u < n_user_rows) & (int)(ip >= 0) & (int)(ip < n_item_rows) & (int)(in >= 0) & (int)(in < n_item_rows))
                 my_row = role == 0 ? (int)u : (int)(n_user_rows + (role == 1 ? ip : in));
-                my_beg = rowptr[my_row];
-                my_deg = rowptr[my_row + 1] - my_beg;
-            }
         }
     }
     // (the arguments that are not preloaded, in ONE scalar trip instead of where each is first used — asked for at the top of the
-    // kernel, waited for here, behind the two vector round trips above)
-    asm volatile("" ::"s"(col), "s"(val), "s"(Xg), "s"(ts), "s"(t0), "s"(t1));
+    // kernel, waited for here, behind the vector round trip above)
+    asm volatile("" ::"s"(col), "s"(val), "s"(Xg), "s"(ts), "s"(t0), "s"(t1), "s"(head_col), "s"(head_val));
+    // Row heads: wave j < kFuseRows owns segment 0 of slot row j whatever the degrees are, and the row's first kRowHead entries sit at
+    // the position the row id implies — requested HERE, in the same round trip as the lanes' rowptr loads, not one trip behind them
+    // (lanes past the row's end read the head's padding and are redirected when the item is taken up).  Without heads (NULL) every item's (col, val) come from
+    // the CSR arrays, behind rowptr.
+    const bool heads = head_col != nullptr;            // uniform over the launch
+    const int head_row = heads && wave < kFuseRows ? __builtin_amdgcn_readlane(my_row, wave) : -1;
+    int cnt_n = 0, col_n = 0, slot_n = 0;
+    float val_n = 0.0f;
+    if (head_row >= 0 && lane < kRowHead) {
+        col_n = head_col[(size_t)head_row * kRowHead + lane];
+        val_n = head_val[(size_t)head_row * kRowHead + lane];
+    }
+    if (my_row >= 0) {
+        my_beg = rowptr[my_row];
+        my_deg = rowptr[my_row + 1] - my_beg;
+    }
     int my_nseg = (my_deg + kTaskEntries - 1) / kTaskEntries;
     if (my_nseg > kWgWaves) my_nseg = kWgWaves;        // (never on a graph the step sends here; keeps s_seg's bound local)
-    int my_pre = 0;                                    // lane j: segments of the rows in front of row j; lane 12: all of them
+    // The items the waves share out by number: without heads every segment of the 12 rows, wave w taking items w, w + 16, ...; with
+    // heads the LATER segments only (sgi >= 1 of the rows beyond 64 entries), which go to waves 12 .. 15, then 0, 1, ... round robin.
+    const int sg0 = heads ? 1 : 0;                     // first segment of a row that is numbered
+    const int my_items = my_nseg > sg0 ? my_nseg - sg0 : 0;
+    int my_pre = 0;                                    // lane j: numbered items of the rows in front of row j; lane 12: all of them
 #pragma unroll
     for (int j = 0; j < kFuseRows; ++j) {
-        const int n = __builtin_amdgcn_readlane(my_nseg, j);
+        const int n = __builtin_amdgcn_readlane(my_items, j);
         if (lane > j) my_pre += n;
     }
     const int S = __builtin_amdgcn_readlane(my_pre, kFuseRows);
@@ -261,18 +285,18 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
     }
 
     const float *__restrict__ Xl = Xg + lane;
-    // Item w's (col, val) are REQUESTED one item ahead (a pipeline of depth two: the request of item w + 16 is issued in front of item
-    // w's gathers), so a wave's second and later items cost no metadata round trip; the entries past a segment's end are redirected
-    // when the item is taken up, not when it is requested (that would wait for the request).
-    int cnt_n = 0, col_n = 0;
-    float val_n = 0.0f;
+    // A numbered item's (col, val) are REQUESTED one item ahead (a pipeline of depth two: the request of a wave's next item is issued in
+    // front of the current item's gathers), so a wave's second and later items cost no metadata round trip — with heads that includes
+    // the first numbered item of a wave that owns a head; the entries past a segment's end are redirected when the item is taken up,
+    // not when it is requested (that would wait for the request).
     auto request = [&](int wi) {
-        // item wi belongs to row j = the number of rows 1..11 whose first item is <= wi (rows without segments share their successor's)
+        // item wi belongs to row j = the number of rows 1..11 whose first item is <= wi (rows without items share their successor's)
         const int j = __popcll(__ballot(lane >= 1 && lane < kFuseRows && my_pre <= wi));
-        const int sgi = wi - __builtin_amdgcn_readlane(my_pre, j);
+        const int sgi = wi - __builtin_amdgcn_readlane(my_pre, j) + sg0;
         const int left = __builtin_amdgcn_readlane(my_deg, j) - sgi * kTaskEntries;
         const int e0 = __builtin_amdgcn_readlane(my_beg, j) + sgi * kTaskEntries;
         cnt_n = left < kTaskEntries ? left : kTaskEntries;
+        slot_n = j * kWgWaves + sgi;
         col_n = 0;
         val_n = 0.0f;
         if (lane < cnt_n) {
@@ -280,47 +304,81 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
             val_n = val[e0 + lane];
         }
     };
-    if (wave < S) request(wave);
-    for (int w = wave; w < S; w += kScoreWaves) {
-        const int cnt = cnt_n;
+    int next = heads ? ((wave - kFuseRows) & (kScoreWaves - 1)) : wave;     // the wave's next numbered item
+    bool have = false, from_head = false;
+    if (head_row >= 0 && __builtin_amdgcn_readlane(my_deg, wave) > 0) {     // the head, already requested
+        const int deg = __builtin_amdgcn_readlane(my_deg, wave);
+        cnt_n = deg < kTaskEntries ? deg : kTaskEntries;
+        slot_n = wave * kWgWaves;
+        have = from_head = true;
+    } else if (next < S) {                             // (a wave without a head item goes straight to the numbered ones)
+        request(next);
+        next += kScoreWaves;
+        have = true;
+    }
+    while (have) {
+        const int cnt = cnt_n, slot = slot_n;
         int my_col = col_n;
         const float my_val = val_n;
-        if (w + kScoreWaves < S) request(w + kScoreWaves);
-        // entries past the segment's end: value 0 on the segment's last real source row (a line already being fetched)
-        const int last_col = __builtin_amdgcn_readlane(my_col, (cnt - 1) & 63);
-        if (lane >= cnt) my_col = last_col;
+        // A head holds the item's first chunk; its entries 16 .. 63 come from the CSR arrays, requested now that rowptr is in, and
+        // arrive under the first chunk's gathers (tail_*: what chunks 1 .. 3 read)
+        int tail_col = 0;
+        float tail_val = 0.0f;
+        const bool tail_late = from_head && cnt > kRowHead;
+        if (tail_late) {
+            const int e0 = __builtin_amdgcn_readlane(my_beg, wave);
+            if (lane >= kRowHead && lane < cnt) {
+                tail_col = col[e0 + lane];
+                tail_val = val[e0 + lane];
+            }
+        }
+        from_head = false;
+        have = next < S;
+        if (have) {
+            request(next);
+            next += kScoreWaves;
+        }
+        // entries past the segment's end: value 0 on the segment's last real source row (a line already being fetched, and a row the
+        // sum reads anyway: a stand-in on any other row would bring 0 * Inf = NaN into a row that never referenced it) — a head's
+        // padding (column 0) included.  Behind a head with a tail the first chunk is all real; the tail's lanes are redirected
+        // behind that chunk's gathers, which is where the tail is first waited for.
+        if (!tail_late) {
+            const int last_col = __builtin_amdgcn_readlane(my_col, (cnt - 1) & 63);
+            if (lane >= cnt) my_col = last_col;
+            tail_col = my_col;
+            tail_val = my_val;
+        }
         float acc = 0.0f;
-#if SPEX_FUSED_QUADS
-        // a chunk gathers its real entries only, four at a time (cnt is wave-uniform: scalar branches) — the segment's last chunk is
+        // A chunk gathers its real entries only, four at a time (cnt is wave-uniform: scalar branches) — the segment's last chunk is
         // the one that is partly filled.  The terms left out were fmaf(0, x, acc) = acc; the chain over the real entries is the same.
         // (One straight-line body per quad count: guarded quads inside one body cost the kernel 7 VGPRs.)
-        auto gather = [&](auto n_, int c) {
+        auto gather = [&](auto n_, int c, int cc, float vv) {
             constexpr int N = decltype(n_)::value;
             float x[N];
 #pragma unroll
             for (int k = 0; k < N; ++k)
-                x[k] = Xl[(size_t)(uint32_t)__builtin_amdgcn_readlane(my_col, c * kChunk + k) * 64];
+                x[k] = Xl[(size_t)(uint32_t)__builtin_amdgcn_readlane(cc, c * kChunk + k) * 64];
 #pragma unroll
-            for (int k = 0; k < N; ++k) acc = fmaf(lane_bcast(my_val, c * kChunk + k), x[k], acc);
+            for (int k = 0; k < N; ++k) acc = fmaf(lane_bcast(vv, c * kChunk + k), x[k], acc);
         };
-        for (int c = 0; c * kChunk < cnt; ++c) {
+        auto chunk = [&](int c, int cc, float vv) {
+#if SPEX_FUSED_QUADS
             const int rem = cnt - c * kChunk;              // >= 1
-            if (rem > 12) gather(std::integral_constant<int, 16>(), c);
-            else if (rem > 8) gather(std::integral_constant<int, 12>(), c);
-            else if (rem > 4) gather(std::integral_constant<int, 8>(), c);
-            else gather(std::integral_constant<int, 4>(), c);
-        }
+            if (rem > 12) gather(std::integral_constant<int, 16>(), c, cc, vv);
+            else if (rem > 8) gather(std::integral_constant<int, 12>(), c, cc, vv);
+            else if (rem > 4) gather(std::integral_constant<int, 8>(), c, cc, vv);
+            else gather(std::integral_constant<int, 4>(), c, cc, vv);
 #else
-        for (int c = 0; c * kChunk < cnt; ++c) {
-            float x[kChunk];
-#pragma unroll
-            for (int k = 0; k < kChunk; ++k)
-                x[k] = Xl[(size_t)(uint32_t)__builtin_amdgcn_readlane(my_col, c * kChunk + k) * 64];
-#pragma unroll
-            for (int k = 0; k < kChunk; ++k) acc = fmaf(lane_bcast(my_val, c * kChunk + k), x[k], acc);
-        }
+            gather(std::integral_constant<int, kChunk>(), c, cc, vv);
 #endif
-        s_seg[w][lane] = acc;
+        };
+        chunk(0, my_col, my_val);                          // the first chunk apart: it does not wait for a head's tail
+        if (tail_late) {
+            const int last_col = __builtin_amdgcn_readlane(tail_col, (cnt - 1) & 63);
+            if (lane >= cnt) tail_col = last_col;
+        }
+        for (int c = 1; c * kChunk < cnt; ++c) chunk(c, tail_col, tail_val);
+        s_seg[slot][lane] = acc;
     }
     __syncthreads();
 
@@ -330,7 +388,7 @@ __global__ __launch_bounds__(kWave *kScoreWaves, 8) void bpr_fused_last_kernel(
 #pragma unroll
         for (int role = 0; role < 3; ++role) {
             const int j = 3 * wave + role;
-            const int n = __builtin_amdgcn_readlane(my_nseg, j), first = __builtin_amdgcn_readlane(my_pre, j);
+            const int n = __builtin_amdgcn_readlane(my_nseg, j), first = j * kWgWaves;
             float v = 0.0f;
             if (n > 0) v = s_seg[first][lane];
             for (int i = 1; i < n; ++i) v = v + s_seg[first + i][lane];    // segment order
@@ -875,11 +933,11 @@ int spex::bpr_sgd_fused_last(const spex_graph_t *g, const float *Xg, const float
     }
     if (snap)
         hipLaunchKernelGGL(bpr_fused_last_kernel<true>, dim3((unsigned)blocks), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, u, i_pos, i_neg,
-                           g->rowptr, T, n_user_rows, n_item_rows, g->col, g->val, Xg, snap, t0, t1, div, table_w, -lr / (float)T,
+                           g->rowptr, T, n_user_rows, n_item_rows, g->col, g->val, Xg, snap, t0, t1, g->head_col, g->head_val, div, table_w, -lr / (float)T,
                            -lr * reg / (float)T, loss_sum, g->loss_cell);
     else
         hipLaunchKernelGGL(bpr_fused_last_kernel<false>, dim3((unsigned)blocks), dim3(kWave * kScoreWaves), 0, (hipStream_t)stream, u, i_pos, i_neg,
-                           g->rowptr, T, n_user_rows, n_item_rows, g->col, g->val, Xg, snap, t0, t1, div, table_w, -lr / (float)T,
+                           g->rowptr, T, n_user_rows, n_item_rows, g->col, g->val, Xg, snap, t0, t1, g->head_col, g->head_val, div, table_w, -lr / (float)T,
                            -lr * reg / (float)T, loss_sum, g->loss_cell);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;

@@ -144,7 +144,7 @@ int sum_parts(const float *parts, int32_t n_parts, int64_t stride, int32_t n, fl
 
 // A/B switch of the one-call BPR step's fused launch (score.hip: bpr_fused_last_kernel), for scratch builds: 0 = the form before.
 #ifndef SPEX_FUSED_QUADS
-#define SPEX_FUSED_QUADS 1         // a segment's last chunk gathers its real entries only, four at a time
+#define SPEX_FUSED_QUADS 1         // a segment's last chunk gathers its real entries only, four at a time (0: 52 VGPRs since the row heads)
 #endif
 
 constexpr int kWave = 64;          // CDNA wavefront
@@ -158,6 +158,8 @@ constexpr int kWgWaves = 16;       // the d == 64 kernel runs 1024-thread workgr
 constexpr int kWgRowMax = kWgWaves * kTaskEntries;  // longest row whose segments are combined inside one workgroup
 constexpr int kOpenTasks = 4;      // first-fit packing of short rows keeps this many tasks open
 constexpr int kChunk = 16;         // entries per chunk = gathers a wave keeps in flight
+constexpr int kRowHead = kChunk;   // entries per row of the row-head table (spex_graph::head_col): one chunk.  (A whole wave task, 64,
+                                   // was built and measured too: slower, four times the bytes — DESIGN 5)
 constexpr int kTileRows = 64;      // rows a workgroup completes in tile mode (4 MFMA tiles of 16)
 constexpr int kSoftmaxTile = 2048; // stored entries per workgroup of the row-softmax kernels (512 on small graphs)
 
@@ -389,6 +391,13 @@ struct spex_graph {
     // first 64 entries of metadata together with its task record; task.x is still stored (= k * chunk_stride) and the slots no task
     // fills are padding (column 0, value 0, edge 0, chunk_pad = kChunk).  0: the dense layout (tables that stream from HBM).
     int32_t chunk_stride = 0;
+    // Row heads (bin-packed tables without hub rows, unless SPEX_ROW_HEADS=0): a second, fixed-stride copy of every row's first
+    // min(deg, kRowHead) entries in CSR order, the tail padded with column 0 / value 0 — row r's first entries sit at r * kRowHead,
+    // a position the row id alone implies, so the fused BPR launch (score.hip) requests them in the same round trip as rowptr[r]
+    // instead of one trip behind it.  Static like the chunk table; spex_graph_set_values rewrites head_val with val.  NULL: no heads
+    // (tables that stream from HBM, graphs with hub rows) — every reader tests for that and walks the CSR arrays.
+    int32_t *head_col = nullptr;    // [n_rows * kRowHead]
+    float *head_val = nullptr;      // [n_rows * kRowHead]
     // Tile mode (spex_graph_create_ex, SPEX_GRAPH_TILE_ROWS): every workgroup of the task table completes at most kTileRows rows,
     // task.w bits 16-23 = the workgroup-local slot of the task's first completed row — what the fused NGCF layer kernel needs
     // to hold a workgroup's rows in LDS.  0 = ordinary table.

@@ -7,6 +7,7 @@ from spex_amd.graph import SpexGraph, lightgcn_norm_adj, ngcf_norm_adj
 from spex_amd.ngcf import NGCF
 from spex_amd.trainer import LightGCNStepper, NGCFStepper
 dev = torch.device("cuda:0")
+torch.manual_seed(0)                         # two builds traced one after the other see the same batches
 tr = load_epinion2()["train"]
 csr = lightgcn_norm_adj(tr[:, 0], tr[:, 1], 3185, 12407)
 rng = np.random.default_rng(0)
