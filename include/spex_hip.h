@@ -407,6 +407,31 @@ int spex_unique_rows_i32(const int64_t *idx_a, int32_t n_a, int64_t off_a, const
 int spex_spmm_push_rows_f32(const spex_graph_t *g, const int32_t *list, const int32_t *count, int32_t max_count,
                             const float *src, int32_t src_indexed, const float *add, int32_t add_indexed, float scale,
                             float *out, int32_t d, void *stream);
+/* spex_spmm_push_rows_f32 with a factor of its own for the add term: out += scale * A^T scatter(src) + add_scale * scatter(add)
+ * (G_(l-1) = g / (L + 1) + A^T G_l over a frontier list: scale = 1, add_scale = 1 / (L + 1)).  Both calls run a grid of
+ * min(max_count, 65 536) workgroups that strides over the list, so max_count may be as loose a bound as n_rows. */
+int spex_spmm_push_rows_scaled_f32(const spex_graph_t *g, const int32_t *list, const int32_t *count, int32_t max_count,
+                                   const float *src, int32_t src_indexed, const float *add, int32_t add_indexed, float scale,
+                                   float add_scale, float *out, int32_t d, void *stream);
+/* The frontier of a batch.  On entry list[0 .. *count_b) is what spex_unique_rows_i32 wrote with the same stamp table and the same
+ * epoch (Bset, the batch's distinct rows; max_b >= *count_b bounds the launch: the batch's slot count).  The call appends, into the
+ * same list, every column of a stored entry of those rows that the stamp table has not seen this epoch, and writes the new length
+ * to *count_f (a cell other than count_b, which is left alone): afterwards the list is [Bset | F1 minus Bset] with
+ * F1 = Bset U { col[e] : e a stored entry of a row in Bset }, *count_b = |Bset| and *count_f = |F1|, both on the device.
+ * Every row enters the list at most once per epoch, so a list of n_rows entries always suffices: there is no overflow path.  The
+ * launch reads its input length from count_b and appends through count_f, so it never walks a row it appended itself (that would
+ * be the two-hop set).  No sort, no host round trip, no clearing of the stamp table between steps (the epoch does that).  The graph
+ * must be square (the list indexes rows and columns alike); one wave per input row, one counter bump per wave and 64-entry run. */
+int spex_frontier_rows_i32(const spex_graph_t *g, int32_t *list, const int32_t *count_b, int32_t max_b, int32_t *stamp, int32_t epoch,
+                           int32_t *count_f, void *stream);
+/* spex_spmm_rowlist_f32 driven by such a device list: rows list[k], k < min(*count, max_count), entries distinct (acc_out may
+ * therefore alias acc_in); rows outside the list are not written; list values outside [0, n_rows) are skipped.  The same per-row
+ * arithmetic and epilogue (Y = y; acc_out = (acc_in + y) / acc_div): bit-identical to spex_spmm_rowlist_f32, and to spex_spmm_f32
+ * on rows of up to 1 024 entries.  The work split is the frontier's: a row of at most 64 entries is one wave's task, longer rows are
+ * cut into one-segment wave tasks whose sums meet in LDS in segment order; a fixed grid (<= 1 024 workgroups of 16 list slots per
+ * pass) strides over the list, the count is read on the device.  d == 64 without edge dropout only: otherwise SPEX_ERR_UNSUPPORTED. */
+int spex_spmm_rowlist_dev_f32(const spex_graph_t *g, const float *X, const int32_t *list, const int32_t *count, int32_t max_count,
+                              float *Y, const float *acc_in, float *acc_out, float acc_div, int32_t d, void *stream);
 /* The same product driven by the batch itself (d = 64, 128 or 256), EVERY slot contributing its own row: for slot k with row
  * r = idx_a[k] + off_a (k < n_a) or idx_b[k - n_a] + off_b:
  *   out[col[e], :] += scale * val[e] * src[k, :]  over the stored entries e of row r;   out[r, :] += scale * add[k, :] (if add)
@@ -927,8 +952,11 @@ enum {
                                          * needs no such flag (it took the three widths from its first version); the BPR entry point promised
                                          * d == 64 ONLY and rejects a descriptor whose d says otherwise — callers rely on that rejection for a
                                          * 64-wide descriptor with a wrong d, which would gather out of bounds — so a wider d is an opt-in */
-    SPEX_STEP_BF16_GATHER = 64          /* the one-call LightGCN steps (BCE, exact BPR) and every epoch over them: bf16 gather tables, d == 64
+    SPEX_STEP_BF16_GATHER = 64,         /* the one-call LightGCN steps (BCE, exact BPR) and every epoch over them: bf16 gather tables, d == 64
                                          * and L = 2 or 3 only; the descriptor's E0_16 / ws16 fields are read (see spex_lightgcn_step_t) */
+    SPEX_STEP_FRONTIER = 128            /* the one-call LightGCN steps (BCE, exact BPR) and every epoch over them: forward layer L - 1 and the
+                                         * backward product behind the batch kernel's push run over the batch's frontier, not the whole
+                                         * graph; d == 64, L >= 2; the descriptor's frontier_* fields are read (see spex_lightgcn_step_t) */
 };
 /* The north-star step — LightGCN L-layer propagation + the fused BPR gather + dot + sigmoid + SGD kernel over T triples — as one
  * call of at most L + 1 launches: EVERY whole-graph layer in the plain form (no epilogue operand, one output stream); the layer-1 launch also sets
@@ -985,7 +1013,7 @@ typedef struct spex_lightgcn_step {
     int32_t slot_capacity, n_user_rows, L, d;
     float lr, beta1, beta2, eps;
     int32_t t;
-    int32_t flags;                           /* SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE / _PUSH, SPEX_STEP_WIDE, SPEX_STEP_BF16_GATHER */
+    int32_t flags;                           /* SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE / _PUSH, SPEX_STEP_WIDE, SPEX_STEP_BF16_GATHER, SPEX_STEP_FRONTIER */
     /* appended for spex_lightgcn_step_bpr_adam_f32 / spex_lightgcn_epoch_bpr_f32 (the BCE entry points never read them): */
     float weight_decay;                      /* >= 0: upstream LightGCN's L2 term on the E0 rows of the batch */
     int32_t *row_counts;                     /* [2, N] int32, all-zero before the first call: per-row occurrence counts, by step parity.
@@ -995,7 +1023,25 @@ typedef struct spex_lightgcn_step {
     uint16_t *E0_16;                         /* [N, 64] bf16: the shadow of E0.  Contract: E0_16 == bf16(E0) (spex_cast_bf16_f32) on entry;
                                               * every call leaves it so */
     uint16_t *ws16;                          /* [2, N, 64] bf16: the later layers' gather tables, then the backward's */
+    /* appended for SPEX_STEP_FRONTIER (without the flag no entry point reads them): */
+    int32_t *frontier_list;                  /* [N] int32: [Bset | F1 minus Bset] of the current step */
+    int32_t *frontier_stamp;                 /* [N] int32, all-zero before the first call; never cleared afterwards */
+    int32_t *frontier_counts;                /* [2] int32: |Bset|, |F1| of the current step */
+    int32_t frontier_epoch;                  /* the last stamp used (0 at first); advanced by every flagged step */
 } spex_lightgcn_step_t;
+/* flags & SPEX_STEP_FRONTIER — the exact steps with one more level taken inward (d == 64, L >= 2, fp32 tables).  With Bset the batch's
+ * distinct rows and F1 = Bset U their stored columns (spex_unique_rows_i32 + spex_frontier_rows_i32 into frontier_list):
+ *   forward:   layers 1 .. L - 2 over the whole graph as without the flag; layer L - 1 at the rows of F1 only
+ *              (spex_spmm_rowlist_dev_f32, the same table and, at L >= 4, the same running sum, valid at F1); the batch kernel is
+ *              unchanged: everything it reads of layer L - 1 lies in F1.
+ *   backward:  the batch kernel's push leaves P = G_(L-1) = (g + A^T g) / (L + 1), whose support lies in F1.  The next product
+ *              A^T P is a PUSH over the F1 list (spex_spmm_push_rows_scaled_f32 over `graph`, float atomics) into a table zeroed by a
+ *              launch of the step: grad_E0 at L == 2 (the Adam pass adds g_out / 3 as without the flag), ws_bwd[1] at L >= 3 (L == 3:
+ *              plain, the Adam pass adds P; L >= 4: with the g_out / (L + 1) term).  The remaining L - 2 products are whole-graph pulls.
+ * L == 2 has no whole-graph launch left.  The exact BPR step takes the push form at any T.  Refused before anything touches the device
+ * (t not advanced): d != 64 or SPEX_STEP_WIDE -> SPEX_ERR_UNSUPPORTED; L < 2, SPEX_STEP_DETERMINISTIC (the second push uses float
+ * atomics), SPEX_STEP_BF16_GATHER, SPEX_STEP_BPR_DENSE, an edge-dropout mask on a handle (also the epochs' keep_prob < 1), a NULL
+ * frontier_* field -> SPEX_ERR_INVALID. */
 /* flags & SPEX_STEP_BF16_GATHER — the mixed-precision mode of spex_propagate_bf16_f32 carried through the one-call steps, d == 64,
  * L = 2 or 3 (spex_lightgcn_step_bce_f32, spex_lightgcn_step_bpr_adam_f32 and, through them, every epoch, sampled-epoch and
  * train_*_sampled call).  Rounding enters only where a table becomes a gather source; every product, sum and the layer mean stay

@@ -104,6 +104,9 @@ SIGNATURES = {
     "spex_adam_step_sum_f32": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_i64, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp]),
     "spex_unique_rows_i32": (ctypes.c_int, [c_vp, c_i32, c_i64, c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "spex_spmm_push_rows_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_vp, c_i32, c_vp]),
+    "spex_spmm_push_rows_scaled_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_i32, c_vp]),
+    "spex_frontier_rows_i32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "spex_spmm_rowlist_dev_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_f32, c_i32, c_vp]),
     "spex_expert_gate_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "spex_expert_gate_bwd_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "spex_expert_gate_bwd_parts": (c_i32, [c_i32]),
@@ -194,7 +197,8 @@ class LightGCNStepDesc(ctypes.Structure):
                 + [(n, c_i32) for n in ("slot_capacity", "n_user_rows", "L", "d")]
                 + [(n, c_f32) for n in ("lr", "beta1", "beta2", "eps")] + [("t", c_i32), ("flags", c_i32)]
                 + [("weight_decay", c_f32), ("row_counts", c_vp)]       # the exact BPR step's (spex_lightgcn_step_bpr_adam_f32)
-                + [("E0_16", c_vp), ("ws16", c_vp)])                    # SPEX_STEP_BF16_GATHER's bf16 tables
+                + [("E0_16", c_vp), ("ws16", c_vp)]                     # SPEX_STEP_BF16_GATHER's bf16 tables
+                + [("frontier_list", c_vp), ("frontier_stamp", c_vp), ("frontier_counts", c_vp), ("frontier_epoch", c_i32)])   # SPEX_STEP_FRONTIER's
 
 
 STEP_DETERMINISTIC = 1          # spex_hip.h: SPEX_STEP_DETERMINISTIC
@@ -204,6 +208,7 @@ STEP_BPR_DENSE = 8              # spex_hip.h: SPEX_STEP_BPR_DENSE
 STEP_BPR_PUSH = 16              # spex_hip.h: SPEX_STEP_BPR_PUSH
 STEP_WIDE = 32                  # spex_hip.h: SPEX_STEP_WIDE (exact BPR step at d = 128 / 256)
 STEP_BF16_GATHER = 64           # spex_hip.h: SPEX_STEP_BF16_GATHER (bf16 gather tables in the one-call LightGCN steps, d = 64, L = 2 / 3)
+STEP_FRONTIER = 128             # spex_hip.h: SPEX_STEP_FRONTIER (layer L - 1 and the second backward product over the batch's frontier, d = 64, L >= 2)
 
 
 class NGCFStepDesc(ctypes.Structure):

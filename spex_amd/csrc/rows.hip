@@ -10,6 +10,8 @@
 //                             deduplication by an epoch-stamp table, no sort, no host round trip
 //   spex_spmm_push_rows_f32   out[col[e], :] += scale * val[e] * src_k  for every stored entry e of every listed row (k-th
 //                             listed row r: src_k = src[r] or src[k]), optionally out[r, :] += scale * add_k — 256-byte float atomics
+//                             (spex_spmm_push_rows_scaled_f32: a factor of its own for the add term)
+//   spex_frontier_rows_i32    behind such a list, the stored columns of its rows not yet stamped this epoch: the batch's frontier
 // Sums arrive in arbitrary order (atomics): results agree with the pull form to fp32 re-association.
 #include "spex_common.h"
 
@@ -29,43 +31,82 @@ __global__ __launch_bounds__(256) void unique_rows_kernel(const int64_t *__restr
     if (atomicExch(stamp + r, epoch) != epoch) list[atomicAdd(count, 1)] = (int32_t)r;   // first visitor of the row this epoch
 }
 
-// One 16-wave workgroup per listed row: wave w takes the row's entries w, w + 16, ... (a hub row of 1 000 entries is 64
-// atomics per wave, not 1 000 in one).
-__global__ __launch_bounds__(kWave *kWgWaves) void spmm_push_rows_kernel(
-    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
-    const int32_t *__restrict__ list, const int32_t *__restrict__ count, int n_rows, const float *__restrict__ src,
-    int src_indexed, const float *__restrict__ add, int add_indexed, float scale, float *out, int d)
+// The frontier of a batch: behind the list spex_unique_rows_i32 wrote, every column of the listed rows that the stamp table has not
+// seen this epoch.  One wave per INPUT row, lanes take entries; the rows found by a wave in one 64-entry run are appended with one
+// counter bump (the first new lane's atomic, the others take their rank among the new lanes).  n_in is read from a cell the launch
+// does not write (count_b), the appends go behind it through count_f: the launch never walks a row it appended itself — that would
+// be the two-hop set.  Every row is stamped at most once per epoch, so n_rows list entries always suffice.
+constexpr int kFrontierWaves = 4;
+
+__global__ void frontier_init_kernel(const int32_t *__restrict__ count_b, int32_t *count_f) { *count_f = *count_b; }
+
+__global__ __launch_bounds__(kWave *kFrontierWaves) void frontier_rows_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, int32_t n_rows, const int32_t *__restrict__ count_b,
+    int32_t max_b, int32_t *stamp, int32_t epoch, int32_t *list, int32_t *count_f)
 {
-    const int k = blockIdx.x;
-    if (k >= *count) return;
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int k = blockIdx.x * kFrontierWaves + (threadIdx.x >> 6);
+    const int n_in = *count_b < max_b ? *count_b : max_b;
+    if (k >= n_in) return;
     const int r = list[k];
     if (r < 0 || r >= n_rows) return;                      // never index the matrix out of range
     const int beg = rowptr[r], end = rowptr[r + 1];
-    for (int c0 = 0; c0 < d; c0 += kWave) {
-        const int c = c0 + lane;
-        const bool col_ok = c < d;                         // (every lane stays in the loop: lanes 0..15 carry the run's metadata)
-        const float g = col_ok ? scale * src[(size_t)(src_indexed ? r : k) * d + c] : 0.0f;
-        for (int base = beg + wave * 16; base < end; base += kWgWaves * 16) {   // 16-entry runs: one coalesced (col, val) load each
-            const int cnt = end - base < 16 ? end - base : 16;
-            int my_col = 0;
-            float my_val = 0.0f;
-            if (lane < cnt) {
-                my_col = col[base + lane];
-                my_val = val[base + lane];
-            }
-            // lane 0 is read before the first atomic and the entry loop is a real loop: see spmm_push_batch_kernel
-            const int cc0 = __builtin_amdgcn_readlane(my_col, 0);
-            const float v0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val), 0));
-            if (col_ok) atomicAdd(out + (size_t)cc0 * d + c, v0 * g);
+    for (int base = beg; base < end; base += kWave) {
+        const int e = base + lane;
+        int c = -1;
+        if (e < end) c = col[e];
+        const bool fresh = c >= 0 && c < n_rows && atomicExch(stamp + c, epoch) != epoch;    // first visitor of the row this epoch
+        const unsigned long long m = __ballot(fresh);
+        if (m == 0) continue;
+        const int leader = (int)__builtin_ctzll(m);
+        int start = 0;
+        if (lane == leader) start = atomicAdd(count_f, (int)__builtin_popcountll(m));
+        start = __builtin_amdgcn_readlane(start, leader);
+        if (fresh) list[start + (int)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = c;
+    }
+}
+
+// One 16-wave workgroup per listed row: wave w takes the row's entries w, w + 16, ... (a hub row of 1 000 entries is 64
+// atomics per wave, not 1 000 in one).
+constexpr int kPushRowsMaxWgs = 1 << 16;
+
+__global__ __launch_bounds__(kWave *kWgWaves) void spmm_push_rows_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+    const int32_t *__restrict__ list, const int32_t *__restrict__ count, int n_rows, const float *__restrict__ src,
+    int src_indexed, const float *__restrict__ add, int add_indexed, float scale, float add_scale, float *out, int d)
+{
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int n = *count;
+    // (a grid of min(max_count, kPushRowsMaxWgs) workgroups strides over the list: a frontier list's host-side bound is n_rows)
+    for (int k = blockIdx.x; k < n; k += gridDim.x) {
+        const int r = list[k];
+        if (r < 0 || r >= n_rows) continue;                    // never index the matrix out of range
+        const int beg = rowptr[r], end = rowptr[r + 1];
+        for (int c0 = 0; c0 < d; c0 += kWave) {
+            const int c = c0 + lane;
+            const bool col_ok = c < d;                         // (every lane stays in the loop: lanes 0..15 carry the run's metadata)
+            const float g = col_ok ? scale * src[(size_t)(src_indexed ? r : k) * d + c] : 0.0f;
+            for (int base = beg + wave * 16; base < end; base += kWgWaves * 16) {   // 16-entry runs: one coalesced (col, val) load each
+                const int cnt = end - base < 16 ? end - base : 16;
+                int my_col = 0;
+                float my_val = 0.0f;
+                if (lane < cnt) {
+                    my_col = col[base + lane];
+                    my_val = val[base + lane];
+                }
+                // lane 0 is read before the first atomic and the entry loop is a real loop: see spmm_push_batch_kernel
+                const int cc0 = __builtin_amdgcn_readlane(my_col, 0);
+                const float v0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val), 0));
+                if (col_ok) atomicAdd(out + (size_t)cc0 * d + c, v0 * g);
 #pragma unroll 1
-            for (int j = 1; j < cnt; ++j) {
-                const int cc = __builtin_amdgcn_readlane(my_col, j);
-                const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val), j));
-                if (col_ok) atomicAdd(out + (size_t)cc * d + c, v * g);
+                for (int j = 1; j < cnt; ++j) {
+                    const int cc = __builtin_amdgcn_readlane(my_col, j);
+                    const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val), j));
+                    if (col_ok) atomicAdd(out + (size_t)cc * d + c, v * g);
+                }
             }
+            if (add && wave == 0 && col_ok) atomicAdd(out + (size_t)r * d + c, add_scale * add[(size_t)(add_indexed ? r : k) * d + c]);
         }
-        if (add && wave == 0 && col_ok) atomicAdd(out + (size_t)r * d + c, scale * add[(size_t)(add_indexed ? r : k) * d + c]);
     }
 }
 
@@ -367,16 +408,60 @@ extern "C" int spex_unique_rows_i32(const int64_t *idx_a, int32_t n_a, int64_t o
     return SPEX_OK;
 }
 
+static int push_rows(const char *who, const spex_graph_t *g, const int32_t *list, const int32_t *count, int32_t max_count, const float *src,
+                     int32_t src_indexed, const float *add, int32_t add_indexed, float scale, float add_scale, float *out, int32_t d,
+                     void *stream)
+{
+    SPEX_CHECK_ARG(g && list && count && src && out, "%s: NULL argument", who);
+    SPEX_CHECK_ARG(max_count >= 0 && d >= 1, "%s: max_count=%d d=%d", who, max_count, d);
+    SPEX_CHECK_ARG(g->mask_mode == 0, "%s: edge dropout is not supported in push form", who);
+    if (max_count == 0 || g->n_rows == 0) return SPEX_OK;
+    hipLaunchKernelGGL(spmm_push_rows_kernel, dim3((unsigned)(max_count < kPushRowsMaxWgs ? max_count : kPushRowsMaxWgs)), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr,
+                       g->col, g->val, list, count, g->n_rows, src, src_indexed, add, add_indexed, scale, add_scale, out, d);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
+
+// spex_unique_rows_i32 without the reset of *count: further index lists of the same epoch appended to the same list.
+int spex::unique_rows_more(const int64_t *idx_a, int32_t n_a, int64_t off_a, const int64_t *idx_b, int32_t n_b, int64_t off_b, int32_t n_rows,
+                           int32_t *stamp, int32_t epoch, int32_t *list, int32_t *count, void *stream)
+{
+    if (n_a + n_b <= 0) return SPEX_OK;
+    hipLaunchKernelGGL(unique_rows_kernel, dim3((unsigned)((n_a + n_b + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx_a, n_a,
+                       off_a, idx_b, n_b, off_b, n_rows, stamp, epoch, list, count);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
+
 extern "C" int spex_spmm_push_rows_f32(const spex_graph_t *g, const int32_t *list, const int32_t *count, int32_t max_count,
                                        const float *src, int32_t src_indexed, const float *add, int32_t add_indexed, float scale,
                                        float *out, int32_t d, void *stream)
 {
-    SPEX_CHECK_ARG(g && list && count && src && out, "spex_spmm_push_rows_f32: NULL argument");
-    SPEX_CHECK_ARG(max_count >= 0 && d >= 1, "spex_spmm_push_rows_f32: max_count=%d d=%d", max_count, d);
-    SPEX_CHECK_ARG(g->mask_mode == 0, "spex_spmm_push_rows_f32: edge dropout is not supported in push form");
-    if (max_count == 0 || g->n_rows == 0) return SPEX_OK;
-    hipLaunchKernelGGL(spmm_push_rows_kernel, dim3((unsigned)max_count), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr,
-                       g->col, g->val, list, count, g->n_rows, src, src_indexed, add, add_indexed, scale, out, d);
+    return push_rows("spex_spmm_push_rows_f32", g, list, count, max_count, src, src_indexed, add, add_indexed, scale, scale, out, d, stream);
+}
+
+// spex_spmm_push_rows_f32 with a factor of its own for the `add` term: out += scale * A^T scatter(src) + add_scale * scatter(add) —
+// G_(l-1) = g / (L + 1) + A^T G_l over a frontier list is scale = 1, add_scale = 1 / (L + 1).
+extern "C" int spex_spmm_push_rows_scaled_f32(const spex_graph_t *g, const int32_t *list, const int32_t *count, int32_t max_count,
+                                              const float *src, int32_t src_indexed, const float *add, int32_t add_indexed, float scale,
+                                              float add_scale, float *out, int32_t d, void *stream)
+{
+    return push_rows("spex_spmm_push_rows_scaled_f32", g, list, count, max_count, src, src_indexed, add, add_indexed, scale, add_scale, out, d,
+                     stream);
+}
+
+extern "C" int spex_frontier_rows_i32(const spex_graph_t *g, int32_t *list, const int32_t *count_b, int32_t max_b, int32_t *stamp,
+                                      int32_t epoch, int32_t *count_f, void *stream)
+{
+    SPEX_CHECK_ARG(g && list && count_b && stamp && count_f && count_f != count_b, "spex_frontier_rows_i32: NULL buffer, or count_f == count_b");
+    SPEX_CHECK_ARG(max_b >= 0 && epoch != 0, "spex_frontier_rows_i32: max_b=%d epoch=%d", max_b, epoch);
+    SPEX_CHECK_ARG(g->n_rows == g->n_cols, "spex_frontier_rows_i32: the list indexes rows and columns alike: a square graph (%d x %d)", g->n_rows,
+                   g->n_cols);
+    hipLaunchKernelGGL(frontier_init_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, count_b, count_f);
+    SPEX_HIP(hipGetLastError());
+    if (max_b == 0 || g->n_rows == 0) return SPEX_OK;
+    hipLaunchKernelGGL(frontier_rows_kernel, dim3((unsigned)((max_b + kFrontierWaves - 1) / kFrontierWaves)), dim3(kWave * kFrontierWaves), 0,
+                       (hipStream_t)stream, g->rowptr, g->col, g->n_rows, count_b, max_b, stamp, epoch, list, count_f);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

@@ -120,6 +120,8 @@ int scale_div(const float *in, float *out, float div, int64_t n, void *stream); 
 // caller's kernels are queued), makes `stream` wait for what the scratch's last user has queued, and records `stream` as that user
 int order_scratch(const spex_graph_t *g, hipStream_t stream, std::unique_lock<std::mutex> &lock);
 int ensure_partial(spex_graph_t *g, int32_t d);                                                        // spmm.hip: the scratch holds n_seg partial rows of d floats
+int unique_rows_more(const int64_t *idx_a, int32_t n_a, int64_t off_a, const int64_t *idx_b, int32_t n_b, int64_t off_b, int32_t n_rows,
+                     int32_t *stamp, int32_t epoch, int32_t *list, int32_t *count, void *stream);             // rows.hip: append to a unique-rows list
 int zero_f32(float *x, int64_t n, void *stream);                                                      // rows.hip: x[0 : n] = 0 (a kernel launch)
 int sum_ordered(const float *x, int32_t n, float scale, float *out, int accumulate, void *stream);     // rows.hip: fixed-order sum
 int sum_parts(const float *parts, int32_t n_parts, int64_t stride, int32_t n, float *out, int accumulate,

@@ -82,6 +82,62 @@ static int bf16_backward_push(const spex_lightgcn_step_t *s, size_t sz, const fl
     return spex_spmm_bf16_f32(s->graph_t, src, s->grad_E0, nullptr, nullptr, 1.0f, nullptr, nullptr, 1.0f, 64, stream);
 }
 
+// ---- SPEX_STEP_FRONTIER (d == 64, L >= 2, fp32 tables; include/spex_hip.h): forward layer L - 1 and the backward product behind the
+//      batch kernel's push run over the batch's frontier F1.  Everything a flagged descriptor must satisfy, checked before anything
+//      touches the device.
+static int frontier_step_check(const spex_lightgcn_step_t *s, const char *who)
+{
+    if (s->d != 64 || (s->flags & SPEX_STEP_WIDE) != 0) {
+        spex::set_error("%s: SPEX_STEP_FRONTIER takes d == 64 only (got d = %d%s): run other widths without the flag", who, s->d,
+                        (s->flags & SPEX_STEP_WIDE) != 0 ? ", SPEX_STEP_WIDE" : "");
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    SPEX_CHECK_ARG(s->L >= 2, "%s: SPEX_STEP_FRONTIER needs L >= 2 (got %d): at L = 1 the step has no whole-graph launch to replace", who, s->L);
+    SPEX_CHECK_ARG((s->flags & SPEX_STEP_DETERMINISTIC) == 0,
+                   "%s: SPEX_STEP_FRONTIER does not combine with SPEX_STEP_DETERMINISTIC (the frontier push uses float atomics)", who);
+    SPEX_CHECK_ARG((s->flags & SPEX_STEP_BF16_GATHER) == 0, "%s: SPEX_STEP_FRONTIER does not combine with SPEX_STEP_BF16_GATHER (fp32 tables only)", who);
+    SPEX_CHECK_ARG((s->flags & SPEX_STEP_BPR_DENSE) == 0,
+                   "%s: SPEX_STEP_FRONTIER does not combine with SPEX_STEP_BPR_DENSE (a frontier step takes the push form at any T)", who);
+    SPEX_CHECK_ARG(s->graph->mask_mode == 0 && s->graph_t->mask_mode == 0, "%s: SPEX_STEP_FRONTIER does not combine with edge dropout", who);
+    SPEX_CHECK_ARG(s->frontier_list && s->frontier_stamp && s->frontier_counts,
+                   "%s: SPEX_STEP_FRONTIER needs frontier_list ([N] int32), frontier_stamp ([N] int32, zeroed once) and frontier_counts ([2] int32)", who);
+    return SPEX_OK;
+}
+
+// Bset, then F1 behind it, of a batch of up to three index lists into frontier_list; frontier_counts = { |Bset|, |F1| }.
+static int frontier_lists(spex_lightgcn_step_t *s, const int64_t *a, int32_t n_a, const int64_t *b, int32_t n_b, const int64_t *c, int32_t n_c,
+                          void *stream)
+{
+    const spex_graph *g = s->graph;
+    const int32_t epoch = s->frontier_epoch % 0x7FFFFFFF + 1;      // never 0
+    const int64_t n_u = s->n_user_rows;
+    SPEX_TRY(spex_unique_rows_i32(a, n_a, 0, b, n_b, n_u, g->n_rows, s->frontier_stamp, epoch, s->frontier_list, s->frontier_counts, stream));
+    if (c) SPEX_TRY(spex::unique_rows_more(c, n_c, n_u, nullptr, 0, 0, g->n_rows, s->frontier_stamp, epoch, s->frontier_list, s->frontier_counts, stream));
+    s->frontier_epoch = epoch;      // (the stamps are on the device from here on, whatever becomes of the step)
+    const int64_t slots = (int64_t)n_a + n_b + (c ? n_c : 0);
+    return spex_frontier_rows_i32(g, s->frontier_list, s->frontier_counts, (int32_t)(slots < g->n_rows ? slots : g->n_rows), s->frontier_stamp, epoch,
+                                  s->frontier_counts + 1, stream);
+}
+
+// Forward layer L - 1 at the rows of F1: the table, and for L >= 4 the running sum, at those rows.
+static int frontier_forward(const spex_lightgcn_step_t *s, const float *cur, float *nxt, bool plain, void *stream)
+{
+    return spex_spmm_rowlist_dev_f32(s->graph, cur, s->frontier_list, s->frontier_counts + 1, s->graph->n_rows, nxt, plain ? nullptr : s->light_out,
+                                     plain ? nullptr : s->light_out, 1.0f, s->d, stream);
+}
+
+// The backward product l = L - 2 from the batch kernel's push target P: W = A^T P (+ g_out / (L + 1) where the whole-graph step's
+// launch carries that term: L >= 4) as a push over the F1 list into W, zeroed here.  W = grad_E0 at L == 2, ws_bwd[1] otherwise.
+static int frontier_backward(const spex_lightgcn_step_t *s, size_t sz, const float *P, float **W_out, void *stream)
+{
+    float *W = s->L == 2 ? s->grad_E0 : s->ws_bwd + sz;
+    SPEX_TRY(spex::zero_f32(W, (int64_t)sz, stream));
+    SPEX_TRY(spex_spmm_push_rows_scaled_f32(s->graph, s->frontier_list, s->frontier_counts + 1, s->graph->n_rows, P, 1, s->L >= 4 ? s->g_out : nullptr,
+                                            1, 1.0f, 1.0f / (float)(s->L + 1), W, s->d, stream));
+    *W_out = W;
+    return SPEX_OK;
+}
+
 extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t *users, const int64_t *items,
                                           const float *labels, int32_t B, float *loss_sum, void *stream)
 {
@@ -104,6 +160,8 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
                    "spex_lightgcn_step_bce_f32: edge dropout needs L >= 2 and graph_t = the transposed handle (with its edge-id permutation)");
     const bool bf16 = (s->flags & SPEX_STEP_BF16_GATHER) != 0;
     if (bf16) SPEX_TRY(bf16_step_check(s, "spex_lightgcn_step_bce_f32"));
+    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0;
+    if (fr) SPEX_TRY(frontier_step_check(s, "spex_lightgcn_step_bce_f32"));
     const size_t sz = (size_t)g->n_rows * d;
     const bool det = (s->flags & SPEX_STEP_DETERMINISTIC) != 0;
     // ---- forward: layers 0 .. L-2 over the whole graph; the last layer is taken at the batch's rows only.  For L <= 3 the whole-graph
@@ -111,13 +169,15 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
     //      ws_fwd, and the batch kernel forms the layer sum (E^0 + E^1 (+ E^2)) + y at the batch's rows — the only rows the loss
     //      reads — in the fused epilogues' order; deeper models keep the running sum fused into the launches.
     const bool plain = L >= 2 && L <= 3;
+    if (fr) SPEX_TRY(frontier_lists(s, users, B, items, B, nullptr, 0, stream));      // (the first launches: every argument check is above)
     const float *cur = s->E0;
     const uint16_t *cur16 = nullptr;             // SPEX_STEP_BF16_GATHER: the batch kernel's gather source, bf16(y_(L-1))
     uint16_t *shadow = bf16 ? s->E0_16 : nullptr;   // ... and the Adam pass's second output
     if (bf16) SPEX_TRY(bf16_forward(s, sz, &cur16, stream));
     for (int32_t l = 0; !bf16 && l + 1 < L; ++l) {
         float *nxt = s->ws_fwd + (size_t)(l & 1) * sz;
-        if (plain) SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
+        if (fr && l + 2 == L) SPEX_TRY(frontier_forward(s, cur, nxt, plain, stream));
+        else if (plain) SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
         else SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, l == 0 ? s->E0 : s->light_out, s->light_out, 1.0f, d, stream));
         cur = nxt;
     }
@@ -166,7 +226,10 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
         //      Adam pass touches anyway (to clear it): it adds P instead of g / 4.  No epilogue operand left in the backward.
         const float *c2 = G;
         if (bf16) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
-        for (int32_t l = L - 2; !bf16 && l >= 0; --l) {
+        float *W = nullptr;
+        if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream));     // product l = L - 2 over the frontier
+        if (fr) c2 = W;
+        for (int32_t l = fr ? L - 3 : L - 2; !bf16 && l >= 0; --l) {
             float *nxt = l == 0 ? s->grad_E0 : s->ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;   // ws_bwd[1], [2], [1] ...: never the source, never G
             if (l == 0 || all_plain) SPEX_TRY(spex_spmm_f32(gt, c2, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
             else SPEX_TRY(spex_spmm_f32(gt, c2, nxt, s->g_out, (float)(L + 1), nullptr, nullptr, 1.0f, d, stream));
@@ -262,6 +325,8 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     SPEX_CHECK_ARG(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_rows, "%s: square graphs of one size", who);
     const bool bf16 = (s->flags & SPEX_STEP_BF16_GATHER) != 0;
     if (bf16) SPEX_TRY(bf16_step_check(s, who));
+    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0;
+    if (fr) SPEX_TRY(frontier_step_check(s, who));
     if ((s->flags & SPEX_STEP_WIDE) != 0) {
         if (d != 128 && d != 256) {
             spex::set_error("%s: SPEX_STEP_WIDE takes d = 128 or 256 (got %d); d == 64 runs without the flag — the widths are 64, 128 and 256", who, d);
@@ -290,6 +355,7 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     l2.scale = wd / (float)T;
     l2.g_store = s->grad_E0;
     l2.shift = d == 64 ? 4 : (d == 128 ? 5 : 6);
+    if (fr) SPEX_TRY(frontier_lists(s, users, T, pos, T, neg, T, stream));             // (the first launches: every argument check is above)
     // ---- forward: layers 0 .. L-2 over the whole graph (plain for L <= 3), the last layer at the batch's rows only
     const bool plain = L >= 2 && L <= 3;
     const float *cur = s->E0;
@@ -298,7 +364,8 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     if (bf16) SPEX_TRY(bf16_forward(s, sz, &cur16, stream));
     for (int32_t l = 0; !bf16 && l + 1 < L; ++l) {
         float *nxt = s->ws_fwd + (size_t)(l & 1) * sz;
-        if (plain) SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
+        if (fr && l + 2 == L) SPEX_TRY(frontier_forward(s, cur, nxt, plain, stream));
+        else if (plain) SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
         else SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, l == 0 ? s->E0 : s->light_out, s->light_out, 1.0f, d, stream));
         cur = nxt;
     }
@@ -335,7 +402,7 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
         return SPEX_OK;
     }
     const int32_t dense_min = d == 64 ? kBprStepDenseMinTriples : (d == 128 ? kBprStepDenseMinTriples128 : kBprStepDenseMinTriples256);
-    const bool dense = (s->flags & SPEX_STEP_BPR_DENSE) != 0 || ((s->flags & SPEX_STEP_BPR_PUSH) == 0 && T >= dense_min);
+    const bool dense = !fr && ((s->flags & SPEX_STEP_BPR_DENSE) != 0 || ((s->flags & SPEX_STEP_BPR_PUSH) == 0 && T >= dense_min));
     if (dense) {
         // ---- large batches: the same launch with the push skipped — the gradient rows go to the dense g_out with atomics — and the
         //      whole backward in pull form (L products: their cost does not grow with T, the push's does)
@@ -355,7 +422,10 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     SPEX_TRY(batch(1.0f / (float)(L + 1), s->grad_slots /* per-triple losses, summed by the Adam pass */, nullptr, no_dense ? nullptr : s->g_out, G));
     const float *c2 = G;
     if (bf16) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
-    for (int32_t l = L - 2; !bf16 && l >= 0; --l) {
+    float *W = nullptr;
+    if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream));     // product l = L - 2 over the frontier
+    if (fr) c2 = W;
+    for (int32_t l = fr ? L - 3 : L - 2; !bf16 && l >= 0; --l) {
         float *nxt = l == 0 ? s->grad_E0 : s->ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;
         if (l == 0 || L == 3) SPEX_TRY(spex_spmm_f32(gt, c2, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
         else SPEX_TRY(spex_spmm_f32(gt, c2, nxt, s->g_out, (float)(L + 1), nullptr, nullptr, 1.0f, d, stream));

@@ -347,6 +347,22 @@ class SpexGraph:
         _bump(Y, acc_out)
         return Y if Y is not None else acc_out
 
+    def spmm_rows_dev(self, X, rows, Y=None, acc_in=None, acc_out=None, acc_div=1.0, frontier=True):
+        """spmm_rows() driven by a device list (an ops.UniqueRows / ops.FrontierRows; frontier=True: the whole expanded list): the
+        listed rows only, other rows of Y / acc_out untouched; entries are distinct, so acc_out may be acc_in.  d == 64, no edge
+        dropout.  See spex_spmm_rowlist_dev_f32."""
+        d = X.shape[1]
+        self._chk(X, self.n_cols, d, "X")
+        for t, nm in ((Y, "Y"), (acc_in, "acc_in"), (acc_out, "acc_out")):
+            self._chk(t, self.n_rows, d, nm)
+        if rows.n_rows > self.n_rows:
+            raise ValueError("spmm_rows_dev: the row list must index rows of the graph")
+        count = rows.count_f if frontier and hasattr(rows, "count_f") else rows.count
+        _launch(self.device, "spex_spmm_rowlist_dev_f32", self._h, _ptr(X), _ptr(rows.list), _ptr(count), rows.capacity, _ptr(Y), _ptr(acc_in),
+                _ptr(acc_out), float(acc_div), d)
+        _bump(Y, acc_out)
+        return Y if Y is not None else acc_out
+
     def propagate(self, E0, n_layers, mean_out=None, layers_out=None, ws=None, gather_dtype=None):
         """LightGCN.computer() (model.py:66-97) on a whole graph: returns mean(E0..EL).
         gather_dtype: None / torch.float32 — every layer gathers fp32 rows; torch.bfloat16 (d == 64) — the layers gather from

@@ -376,9 +376,38 @@ class UniqueRows:
         return self
 
 
-def spmm_push_rows(graph, rows, src, out, src_indexed, add=None, add_indexed=False, scale=1.0):
+class FrontierRows(UniqueRows):
+    """A batch's distinct rows Bset and, behind them in the same list, the rest of its frontier F1 = Bset U the stored columns of
+    Bset's rows (spex_unique_rows_i32 + spex_frontier_rows_i32): update(...) then expand(graph).  `list` int32[n_rows] (always
+    enough: a row enters at most once per epoch), `count` = |Bset| and `count_f` = |F1|, int32[1] device cells; one stamp table,
+    never cleared.  A FrontierRows passes for a UniqueRows (its Bset part); frontier=True selects the whole list in
+    spmm_push_rows / SpexGraph.spmm_rows_dev."""
+
+    def __init__(self, n_rows, device):
+        super().__init__(n_rows, n_rows, device)
+        self.counts = torch.zeros(2, dtype=torch.int32, device=device)
+        self.count, self.count_f = self.counts[0:1], self.counts[1:2]
+        self.max_b = 0
+
+    def update(self, idx_a, idx_b=None, off_a=0, off_b=0):
+        super().update(idx_a, idx_b, off_a, off_b)
+        self.max_b = min(self.n_rows, idx_a.numel() + (0 if idx_b is None else idx_b.numel()))
+        return self
+
+    def expand(self, graph):
+        """Append the columns of the listed rows (call once after update)."""
+        if graph.n_rows != self.n_rows or graph.n_cols != self.n_rows:
+            raise ValueError(f"FrontierRows.expand: needs a square graph of {self.n_rows} rows (got {graph.n_rows} x {graph.n_cols})")
+        _launch(self.list.device, "spex_frontier_rows_i32", graph._h, _ptr(self.list), _ptr(self.count), self.max_b, _ptr(self.stamp),
+                self.epoch, _ptr(self.count_f))
+        return self
+
+
+def spmm_push_rows(graph, rows, src, out, src_indexed, add=None, add_indexed=False, scale=1.0, add_scale=None, frontier=False):
     """out += scale * (A^T scatter(src) + scatter(add)) for the rows of a UniqueRows list, A = the matrix of `graph`
-    (spex_spmm_push_rows_f32).  src / add: the table itself (indexed=True) or compact [capacity, d] arrays."""
+    (spex_spmm_push_rows_f32).  src / add: the table itself (indexed=True) or compact [capacity, d] arrays.
+    add_scale: a factor of its own for the add term (spex_spmm_push_rows_scaled_f32).  frontier=True: over the whole list of an
+    expanded FrontierRows, not only its Bset part."""
     _need(src, "src"); _need(out, "out"); _need(add, "add")
     d = out.shape[1]
     if out.shape[0] != graph.n_cols or rows.n_rows > graph.n_rows:
@@ -386,8 +415,13 @@ def spmm_push_rows(graph, rows, src, out, src_indexed, add=None, add_indexed=Fal
     for t, ind, nm in ((src, src_indexed, "src"), (add, add_indexed, "add")):
         if t is not None and (t.shape[1] != d or t.shape[0] < (rows.n_rows if ind else rows.capacity)):
             raise ValueError(f"spmm_push_rows: {nm} has shape {tuple(t.shape)}")
-    _launch(out.device, "spex_spmm_push_rows_f32", graph._h, _ptr(rows.list), _ptr(rows.count), rows.capacity, _ptr(src),
-            1 if src_indexed else 0, _ptr(add), 1 if add_indexed else 0, float(scale), _ptr(out), d)
+    count = rows.count_f if frontier else rows.count
+    if add_scale is None:
+        _launch(out.device, "spex_spmm_push_rows_f32", graph._h, _ptr(rows.list), _ptr(count), rows.capacity, _ptr(src),
+                1 if src_indexed else 0, _ptr(add), 1 if add_indexed else 0, float(scale), _ptr(out), d)
+    else:
+        _launch(out.device, "spex_spmm_push_rows_scaled_f32", graph._h, _ptr(rows.list), _ptr(count), rows.capacity, _ptr(src),
+                1 if src_indexed else 0, _ptr(add), 1 if add_indexed else 0, float(scale), float(add_scale), _ptr(out), d)
     _bump(out)
     return out
 

@@ -51,8 +51,15 @@ def _drop_desc(stepper):
 
 class LightGCNStepper:
     def __init__(self, graph, E0, n_user_rows, n_layers=3, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph_t=None, deterministic=None,
-                 weight_decay=0.0, gather_dtype=None):
-        """gather_dtype: None / torch.float32, or torch.bfloat16 (width 64 and n_layers 2 or 3 only; ValueError otherwise) — the
+                 weight_decay=0.0, gather_dtype=None, frontier=False):
+        """frontier=True (width 64, n_layers >= 2, fp32 tables, no edge dropout, not deterministic; ValueError otherwise): step_bce,
+        step_bpr_exact, the native epochs and the sampled epochs take one more level inward (SPEX_STEP_FRONTIER) —
+        forward layer L - 1 only at the batch's frontier F1 (its rows and their stored columns), the backward product behind the
+        batch kernel's push as a push over the same list; at n_layers 2 no whole-graph launch is left in the step.  Exact semantics
+        (the second push adds with float atomics).  `light_out` and the layer tables are then valid at F1 only.  Pays on graphs that
+        stream from HBM, where F1 is a few percent of the entries; slower on small graphs, where two hops cover everything.  The
+        exact BPR step takes its push form at any T.
+        gather_dtype: None / torch.float32, or torch.bfloat16 (width 64 and n_layers 2 or 3 only; ValueError otherwise) — the
         whole-graph launches of step_bce / step_bpr_exact, of the native epochs and of the sampled epochs gather from bf16 tables
         (rows of 128 bytes) while every product, sum and the layer mean stay fp32 and E0, m, v stay fp32 (SPEX_STEP_BF16_GATHER,
         DESIGN.md 4.19).  The stepper keeps `E0_16`, a bf16 shadow of E0 that the one-call step's Adam pass writes beside E0; the
@@ -101,7 +108,37 @@ class LightGCNStepper:
             self.E0_16 = torch.empty((n, d), dtype=torch.bfloat16, device=dev)       # bf16(E0): see _shadow_current
             self.ws16 = torch.zeros((2, n, d), dtype=torch.bfloat16, device=dev)     # the later layers' gather tables, then the backward's
         self._shadow_current = False  # E0_16 == bf16(E0) (kept so by the bf16 one-call step's Adam pass; every other writer of E0 clears it)
+        self._frontier = False
+        self._front = None            # the batch's frontier list (ops.FrontierRows): list, counts and stamp table of both step forms
+        if frontier:
+            if self.deterministic:
+                raise ValueError("LightGCNStepper(frontier=True): not with deterministic=True — the frontier push adds with float atomics")
+            if self.gather_dtype is not None:
+                raise ValueError("LightGCNStepper(frontier=True): not with gather_dtype — the frontier form reads fp32 tables only")
+            if d != 64 or self.L < 2:
+                raise ValueError(f"LightGCNStepper(frontier=True): takes an embedding width of 64 and n_layers >= 2 (got width {d}, "
+                                 f"n_layers {self.L})")
+            self._front = ops.FrontierRows(n, dev)
+            self.frontier = True
+            self._refuse_frontier_dropout("LightGCNStepper(frontier=True)")
         self.t = 0
+
+    @property
+    def frontier(self):
+        """Whether the steps take the frontier form.  A stepper built with frontier=True may switch it off and on between steps; one
+        built without has no frontier list, and switching it on is refused."""
+        return self._frontier
+
+    @frontier.setter
+    def frontier(self, on):
+        if on and self._front is None:
+            raise ValueError("LightGCNStepper.frontier = True: only on a stepper built with frontier=True (it owns the frontier list and "
+                             "has passed the form's checks)")
+        self._frontier = bool(on)
+
+    def _refuse_frontier_dropout(self, who, keep_prob=1.0):
+        if self.frontier and (keep_prob < 1.0 or getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0):
+            raise ValueError(f"{who}: frontier=True does not combine with edge dropout")
 
     def refresh_gather_table(self):
         """Re-cast the bf16 gather table from E0 (one streaming launch).  For callers that write `stepper.E0` themselves — loading a
@@ -150,8 +187,11 @@ class LightGCNStepper:
         step is exactly eight launches (3 SpMM, scoring, 3 SpMM, Adam) with nothing between them.  The gradient table
         is cleared by the Adam pass of the previous step.  batch_rows_only: compute the last forward layer at the
         batch's rows only (same arithmetic for those rows; `self.light_out` is then not the whole table)."""
+        self._refuse_frontier_dropout("LightGCNStepper.step_bce")
         if batch_rows_only and loss_acc is not None and self._one_call_ok(users, items, labels):
             return self._step_bce_one_call(users, items, labels, loss_acc)
+        if self.frontier:
+            return self._step_bce_frontier(users, items, labels, loss_acc)
         masked = getattr(self.graph, "mask_mode", 0) != 0        # (the row-list kernel of the launch-by-launch form takes no mask)
         bf16 = self.gather_dtype is not None                     # (... and there is none for a bf16 table: the whole-graph propagation)
         lo = self.propagate_for_batch(users, items) if batch_rows_only and not masked and not bf16 else self.propagate()
@@ -180,6 +220,83 @@ class LightGCNStepper:
         self._shadow_current = False
         return None if loss_acc is not None else loss_sum / B
 
+    # -- frontier=True, launch by launch: the statement the one-call frontier step is checked against
+    def _frontier_forward(self, idx_a, idx_b):
+        """Layers 1 .. L-2 over the whole graph, layer L-1 at the rows of F1 (table and running sum), layer L at the batch's rows
+        (idx_a, idx_b + n_user_rows) into lo_batch.  Returns lo_batch, valid at the batch's rows."""
+        if not all(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() for t in (idx_a, idx_b)):
+            raise ValueError("LightGCNStepper(frontier=True): the batch must be contiguous int64 tensors on the GPU")
+        L, g, lo = self.L, self.graph, self.light_out
+        fr = self._front.update(idx_a, idx_b, 0, self.n_u).expand(g)
+        cur = self.E0
+        for l in range(L - 1):
+            nxt = self.ws_fwd[l & 1]
+            acc_in = self.E0 if l == 0 else lo
+            if l == L - 2:
+                g.spmm_rows_dev(cur, fr, Y=nxt, acc_in=acc_in, acc_out=lo)
+            else:
+                g.spmm(cur, Y=nxt, acc_in=acc_in, acc_out=lo)
+            cur = nxt
+        if self.lo_batch is None:
+            self.lo_batch = torch.zeros_like(lo)
+        g.spmm_rows(cur, idx_a, idx_b, 0, self.n_u, acc_in=lo, acc_out=self.lo_batch, acc_div=float(L + 1))
+        return self.lo_batch
+
+    def _frontier_backward(self):
+        """grad_E0 from G_{L-1} in ws_bwd[0] (support in F1) and the dense g_out: G_{L-2} = g/(L+1) + A^T G_{L-1} as a push over the
+        F1 list into a zeroed table (grad_E0 itself at L == 2), the remaining L - 2 products whole-graph pulls over A^T."""
+        L, gt = self.L, self.graph_t
+        inv = 1.0 / float(L + 1)
+        W = self.grad_E0 if L == 2 else self.ws_bwd[1]
+        W.zero_()
+        ops.spmm_push_rows(self.graph, self._front, self.ws_bwd[0], W, True, add=self.g_out, add_indexed=True, scale=1.0, add_scale=inv,
+                           frontier=True)
+        cur = W
+        for l in range(L - 3, -1, -1):
+            nxt = self.grad_E0 if l == 0 else self.ws_bwd[1 + ((L - 2 - l) & 1)]
+            gt.spmm(cur, Y=nxt, add_in=self.g_out, add_div=float(L + 1))
+            cur = nxt
+
+    def _step_bce_frontier(self, users, items, labels, loss_acc):
+        lo = self._frontier_forward(users, items)
+        B = users.numel()
+        self._slots(B)
+        _, loss_sum = ops.score_bce(lo[:self.n_u], lo[self.n_u:], users, items, labels, self.g_out[:self.n_u], self.g_out[self.n_u:],
+                                    1.0 / B, loss_sum=loss_acc, want_gamma=False, grad_slots=self.grad_slots)
+        self._ws0_clean = False
+        G = self.ws_bwd[0]
+        G.zero_()
+        ops.spmm_push_batch(self.graph, users, items, self.n_u, self.grad_slots, G, add=self.grad_slots, scale=1.0 / float(self.L + 1))
+        self._frontier_backward()
+        self._clear_row_counts()
+        self.t += 1
+        ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps, zero=self.g_out)
+        return None if loss_acc is not None else loss_sum / B
+
+    def _step_bpr_frontier(self, users, pos, neg, loss_acc):
+        T = users.numel()
+        items = torch.cat([pos, neg])
+        lo = self._frontier_forward(users, items)
+        loss_sum = ops.bpr_loss_grad(lo[:self.n_u], lo[self.n_u:], users, pos, neg, self.g_out[:self.n_u], self.g_out[self.n_u:], 1.0 / T)
+        self._ws0_clean = False
+        self._clear_row_counts()
+        G = self.ws_bwd[0]
+        G.zero_()
+        # G_{L-1} = (g + A^T g) / (L + 1), pushed from the dense g_out over the Bset part of the list
+        ops.spmm_push_rows(self.graph, self._front, self.g_out, G, True, add=self.g_out, add_indexed=True, scale=1.0 / float(self.L + 1))
+        self._frontier_backward()
+        if self.weight_decay > 0:
+            rows = torch.cat([users, items + self.n_u])
+            count = torch.bincount(rows, minlength=self.E0.shape[0]).to(torch.float32)
+            self.grad_E0.add_(self.E0 * (count * (self.weight_decay / T)).unsqueeze(1))
+            loss_sum = loss_sum + (0.5 * self.weight_decay) * (self.E0[rows] ** 2).sum()
+        self.t += 1
+        ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps, zero=self.g_out)
+        if loss_acc is not None:
+            loss_acc += loss_sum
+            return None
+        return loss_sum / T
+
     def _slots(self, B, rows_per_sample=2):
         """The batch's per-sample gradient rows (operands of the push-form first backward product): two per BCE sample, three per
         BPR triple."""
@@ -198,6 +315,8 @@ class LightGCNStepper:
 
     def set_edge_dropout(self, mask=None):
         """The next steps' edge-dropout mask on graph and graph_t (an edge_dropout_mask(...) tuple; None: off) — model.py:46-55."""
+        if mask is not None and self.frontier:
+            raise ValueError("LightGCNStepper.set_edge_dropout: frontier=True does not combine with edge dropout")
         if mask is not None and self.graph_t is self.graph:
             raise ValueError("LightGCNStepper.set_edge_dropout: needs graph_t = the transposed handle with the edge-id permutation "
                              "(LightGCN._transposed()): a masked adjacency is not symmetric")
@@ -234,6 +353,9 @@ class LightGCNStepper:
                 slot_capacity=self.grad_slots.shape[0], n_user_rows=self.n_u, L=self.L, d=self.E0.shape[1],
                 lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, t=self.t, flags=0,
                 E0_16=None if self.E0_16 is None else p(self.E0_16), ws16=None if self.ws16 is None else p(self.ws16))
+            if self._front is not None:         # (whatever `frontier` says now: it may be switched on before the next step)
+                fr = self._front
+                self._desc.frontier_list, self._desc.frontier_stamp, self._desc.frontier_counts = p(fr.list), p(fr.stamp), p(fr.counts)
         d = self._desc
         d.t, d.lr = self.t, self.lr
         d.flags = _lib.STEP_DETERMINISTIC if self.deterministic else 0
@@ -242,9 +364,19 @@ class LightGCNStepper:
             d.flags |= _lib.STEP_WIDE       # the exact BPR step's opt-in: every table and slot of this descriptor is d wide
         if self.gather_dtype is not None:
             d.flags |= _lib.STEP_BF16_GATHER
+        if self.frontier:
+            if self.bpr_backward == "dense":
+                raise ValueError("LightGCNStepper(frontier=True): bpr_backward='dense' (SPEX_STEP_BPR_DENSE) is refused — a frontier step "
+                                 "takes the push form at any T")
+            d.flags |= _lib.STEP_FRONTIER
+            d.frontier_epoch = self._front.epoch        # one stamp table for both step forms: one epoch counter
         d.weight_decay = self.weight_decay
         d.row_counts = None if self.row_counts is None else self.row_counts.data_ptr()
         return d
+
+    def _after_desc(self, d):
+        if self.frontier and d is self._desc:
+            self._front.epoch = d.frontier_epoch
 
     def _step_bce_one_call(self, users, items, labels, loss_acc):
         B = users.numel()
@@ -253,6 +385,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_step_bce_f32", ctypes.byref(d), ctypes.c_void_p(users.data_ptr()),
                 ctypes.c_void_p(items.data_ptr()), ctypes.c_void_p(labels.data_ptr()), B, ctypes.c_void_p(loss_acc.data_ptr()))
         self.t = d.t
+        self._after_desc(d)
         _bump(self.E0, self.m, self.v, loss_acc, self.E0_16)
         return None
 
@@ -263,6 +396,7 @@ class LightGCNStepper:
         edge mask, a fresh one per step (seed (drop_seed << 32) | step — trainer.edge_dropout_mask's "philox" stream)."""
         if not self._one_call_ok(users[:1], items[:1], labels[:1]):
             raise ValueError("LightGCNStepper.epoch_bce: needs an embedding width of 64, 128 or 256 and contiguous int64 / fp32 device tensors")
+        self._refuse_frontier_dropout("LightGCNStepper.epoch_bce", keep_prob)
         if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
             raise ValueError("LightGCNStepper.epoch_bce: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
         d = self._prepare_desc(min(int(batch_size), users.numel()))
@@ -271,6 +405,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bce_f32", ctypes.byref(d), vp(users), vp(items), vp(labels), users.numel(), int(batch_size),
                 -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
         self.t = d.t
+        self._after_desc(d)
         _bump(self.E0, self.m, self.v, loss_full, loss_ragged, self.E0_16)
 
     def backward_from_batch_rows(self, users, items):
@@ -335,8 +470,11 @@ class LightGCNStepper:
         launch-by-launch form (ValueError) instead of handing out atomics silently.  At width 64 it is left as it was — the
         launch-by-launch step is what the one-call step is checked against there, in deterministic mode too
         (tests/test_gpu_bpr_exact_step.py) — so at that width pass loss_acc and batch_rows_only=True for a reproducible step."""
+        self._refuse_frontier_dropout("LightGCNStepper.step_bpr_exact")
         if batch_rows_only and loss_acc is not None and self._one_call_bpr_ok(users, pos, neg):
             return self._step_bpr_one_call(users, pos, neg, loss_acc)
+        if self.frontier:
+            return self._step_bpr_frontier(users, pos, neg, loss_acc)
         if self.deterministic and self.E0.shape[1] != 64:
             raise ValueError("LightGCNStepper(deterministic=True).step_bpr_exact: at width 128 / 256 only the one-call form is fixed-order — "
                              "pass loss_acc and batch_rows_only=True with contiguous int64 device indices (the launch-by-launch form "
@@ -377,6 +515,7 @@ class LightGCNStepper:
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         _launch(self.E0.device, "spex_lightgcn_step_bpr_adam_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), T, vp(loss_acc))
         self.t = d.t
+        self._after_desc(d)
         _bump(self.E0, self.m, self.v, self.grad_E0, loss_acc, self.E0_16)
         return None
 
@@ -385,6 +524,7 @@ class LightGCNStepper:
         [k T, (k+1) T) through the one-call exact BPR step.  loss_full / loss_ragged, keep_prob and drop_seed as in epoch_bce."""
         if not self._one_call_bpr_ok(users[:1], pos[:1], neg[:1]):
             raise ValueError("LightGCNStepper.epoch_bpr: needs an embedding width of 64, 128 or 256 and contiguous int64 device tensors")
+        self._refuse_frontier_dropout("LightGCNStepper.epoch_bpr", keep_prob)
         if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
             raise ValueError("LightGCNStepper.epoch_bpr: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
         d = self._prepare_desc(min(int(batch_size), users.numel()), 3)
@@ -392,6 +532,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bpr_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), users.numel(), int(batch_size),
                 -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
         self.t = d.t
+        self._after_desc(d)
         _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged, self.E0_16)
 
     # -- sampled epochs: the triples drawn on the device by the same native call that trains on them
@@ -405,6 +546,7 @@ class LightGCNStepper:
             raise ValueError(f"LightGCNStepper.{who}: the sampler's tables live on {sampler.rowptr.device}, the stepper on {self.E0.device}")
         if not self._one_call_bpr_shape_ok() or sampler.n < 1 or int(batch_size) < 1:
             raise ValueError(f"LightGCNStepper.{who}: needs an embedding width of 64, 128 or 256, a sampler with n >= 1 and batch_size >= 1")
+        self._refuse_frontier_dropout(f"LightGCNStepper.{who}", keep_prob)
         if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
             raise ValueError(f"LightGCNStepper.{who}: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
         d = self._prepare_desc(min(int(batch_size), sampler.n), 3)
@@ -423,6 +565,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bpr_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
                 int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
         self.t = d.t
+        self._after_desc(d)
         _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged, self.E0_16, *sampler.epoch_buffers())
 
     def train_bpr_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
@@ -439,6 +582,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_train_bpr_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
                 *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
         self.t = d.t
+        self._after_desc(d)
         _bump(self.E0, self.m, self.v, self.grad_E0, loss_epochs, self.E0_16, *sampler.epoch_buffers())
 
     # -- sampled BCE epochs: negatives, labels and the shuffle drawn on the device by the same native call that trains on them
@@ -452,6 +596,7 @@ class LightGCNStepper:
             raise ValueError(f"LightGCNStepper.{who}: the sampler's tables live on {sampler.rowptr.device}, the stepper on {self.E0.device}")
         if not self._one_call_bce_shape_ok() or sampler.n < 1 or int(batch_size) < 1:
             raise ValueError(f"LightGCNStepper.{who}: needs an embedding width of 64, 128 or 256, a sampler with n >= 1 and batch_size >= 1")
+        self._refuse_frontier_dropout(f"LightGCNStepper.{who}", keep_prob)
         if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
             raise ValueError(f"LightGCNStepper.{who}: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
         d = self._prepare_desc(min(int(batch_size), sampler.n))
@@ -471,6 +616,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bce_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
                 int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
         self.t = d.t
+        self._after_desc(d)
         _bump(self.E0, self.m, self.v, loss_full, loss_ragged, self.E0_16, *sampler.epoch_buffers())
 
     def train_bce_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
@@ -488,6 +634,7 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_train_bce_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
                 *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
         self.t = d.t
+        self._after_desc(d)
         _bump(self.E0, self.m, self.v, loss_epochs, self.E0_16, *sampler.epoch_buffers())
 
 
