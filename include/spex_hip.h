@@ -82,6 +82,11 @@ int spex_graph_pack_row_heads(const int32_t *h_rowptr, const int32_t *h_col, con
 /* n_rows, n_cols, nnz, number of long rows, number of long-row segments (any pointer may be NULL) */
 int spex_graph_info(const spex_graph_t *g, int32_t *n_rows, int32_t *n_cols, int64_t *nnz, int32_t *n_long_rows,
                     int32_t *n_segments);
+/* How the handle laid out its chunk table (any pointer may be NULL): bin_packed = 1 where tasks pack non-adjacent short rows
+ * (source table within 16 MiB at d = 64); packed_words = 1 where such a table stores (output row << 16) | source row in one word
+ * per entry (at most 65 536 rows and packs of 64 entries; SPEX_PACK_WORDS=0, read at creation, keeps a row array);
+ * chunk_stride = the implied-position stride, or 0. */
+int spex_graph_layout(const spex_graph_t *g, int32_t *bin_packed, int32_t *packed_words, int32_t *chunk_stride);
 
 /* Edge dropout — replaces LightGCN.__dropout_x, utility1/model.py:46-55: keep entry e iff floor(rand_e + keep_prob),
  * kept values divided by keep_prob.  Two modes:

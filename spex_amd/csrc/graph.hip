@@ -243,6 +243,9 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
     const char *implied_sw = getenv("SPEX_PACK_IMPLIED");
     const bool pack_implied = !(implied_sw && implied_sw[0] == '0');
     g->row_ids = (int64_t)n_cols * 256 <= ((int64_t)16 << 20);
+    // SPEX_PACK_WORDS=0, read here like SPEX_PACK_IMPLIED: the three-array layout on every table (spex_common.h: packed_words)
+    const char *words_sw = getenv("SPEX_PACK_WORDS");
+    g->packed_words = g->row_ids && n_rows <= 65536 && n_cols <= 65536 && !(words_sw && words_sw[0] == '0');
     (void)flags;
     const int32_t tile_rows = 0;                 // (round 3's tile mode — at most 64 rows per workgroup, for a fused SpMM + NGCF layer launch
                                                  //  that measured no faster than two launches — is gone; the bookkeeping below stays inert)
@@ -333,10 +336,17 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
             c_off.resize(n_slots);
             c_val.resize(n_slots);
             c_eid.resize(n_slots);
-            if (g->row_ids) c_row.resize(n_slots);
+            // Packs raised above 64 entries (the tables whose tasks run a later super-chunk: the Weibo shape) keep the row array — packed,
+            // that shape's launches measured 0.4 us SLOWER (profiles/packed_words/), cause not found
+            if (pack_cap != spex::kTaskEntries) g->packed_words = false;
+            for (const int4 &t : task)                  // (what chunk_body relies on: a packed handle has no later super-chunk)
+                if ((t.w & 3) != 3 && t.y > g->max_task_chunks) g->max_task_chunks = t.y;
+            if (g->max_task_chunks > 4) g->packed_words = false;
+            const bool packed = g->packed_words;     // (output row << 16) | source row in c_off, no c_row
+            if (g->row_ids && !packed) c_row.resize(n_slots);
             c_mask.resize((size_t)n_planned);
             c_pad.assign((size_t)n_planned, implied ? (uint8_t)spex::kChunk : (uint8_t)0);
-            const bool row_ids = g->row_ids;
+            const bool row_ids = g->row_ids && !packed;
             auto fill_job = [&](const ChunkJob &j) {
                 size_t pos = (size_t)j.first_chunk * spex::kChunk, ci = (size_t)j.first_chunk;
                 int32_t in_chunk = 0, last_col = 0, last_eid = 0, last_row = j.r0;
@@ -345,7 +355,7 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
                     last_col = h_col[en];
                     last_eid = h_edge_id ? h_edge_id[en] : en;
                     last_row = r;
-                    c_off[pos] = (uint32_t)last_col;
+                    c_off[pos] = packed ? ((uint32_t)r << 16) | (uint32_t)last_col : (uint32_t)last_col;
                     c_val[pos] = h_val[en];
                     c_eid[pos] = (uint32_t)last_eid;
                     if (row_ids) c_row[pos] = r;
@@ -361,10 +371,11 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
                 if (j.n_rows < 0) {          // zero-row list: row ids only, all slots padding (value 0 on column 0, never gathered)
                     const int32_t n = -j.n_rows, nch = (n + spex::kChunk - 1) / spex::kChunk;
                     for (int32_t k = 0; k < nch * spex::kChunk; ++k, ++pos) {
-                        c_off[pos] = 0u;
+                        const int32_t r = pack_rows[(size_t)j.rows_off + (k < n ? k : n - 1)];
+                        c_off[pos] = packed ? (uint32_t)r << 16 : 0u;
                         c_val[pos] = 0.0f;
                         c_eid[pos] = 0u;
-                        if (row_ids) c_row[pos] = pack_rows[(size_t)j.rows_off + (k < n ? k : n - 1)];
+                        if (row_ids) c_row[pos] = r;
                     }
                     for (int32_t c = 0; c < nch; ++c) {
                         c_mask[ci + c] = 0u;
@@ -383,7 +394,7 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
                 if (in_chunk) {  // padding: value 0 on the task's last real source row (a line already being fetched)
                     const uint32_t n_pad = (uint32_t)(spex::kChunk - in_chunk);
                     for (; in_chunk < spex::kChunk; ++in_chunk, ++pos) {
-                        c_off[pos] = (uint32_t)last_col;
+                        c_off[pos] = packed ? ((uint32_t)last_row << 16) | (uint32_t)last_col : (uint32_t)last_col;
                         c_val[pos] = 0.0f;
                         c_eid[pos] = (uint32_t)last_eid;
                         if (row_ids) c_row[pos] = last_row;
@@ -608,11 +619,12 @@ static int graph_create_impl(const int32_t *h_rowptr, const int32_t *h_col, cons
         }
     }
     if (getenv("SPEX_DEBUG_PACK"))
-        fprintf(stderr, "[spex] graph %d x %d nnz %lld: %d tasks = %d workgroups, %lld chunks (%.1f %% padding), tile mode %d (%d workgroups), chunk stride %d, chunk table %lld bytes, row heads %lld bytes\n",
+        fprintf(stderr, "[spex] graph %d x %d nnz %lld: %d tasks = %d workgroups, %lld chunks (%.1f %% padding), tile mode %d (%d workgroups), chunk stride %d, chunk table %lld bytes, row heads %lld bytes, %s\n",
                 n_rows, n_cols, (long long)nnz, (int)task.size(), (int)task.size() / spex::kWgWaves, (long long)c_mask.size(),
                 nnz ? 100.0 * ((double)c_mask.size() * spex::kChunk - (double)nnz) / (double)nnz : 0.0, tile_rows, g->n_wgs, g->chunk_stride,
                 (long long)(c_off.size() * 4 + c_val.size() * 4 + c_eid.size() * 4 + c_row.size() * 4 + c_mask.size() * 4 + c_pad.size()),
-                (long long)(head_col.size() * 4 + head_val.size() * 4));
+                (long long)(head_col.size() * 4 + head_val.size() * 4),
+                !g->row_ids ? "adjacent rows" : (g->packed_words ? "packed words" : "row array"));
     g->n_chunks = (int64_t)c_mask.size();
     g->n_hub = (int32_t)hub_row.size();
     g->n_hub_tasks = (int32_t)hub_grp.size();
@@ -713,6 +725,15 @@ extern "C" int spex_graph_info(const spex_graph_t *g, int32_t *n_rows, int32_t *
     if (nnz) *nnz = g->nnz;
     if (n_long_rows) *n_long_rows = g->n_long;
     if (n_segments) *n_segments = g->n_seg;
+    return SPEX_OK;
+}
+
+extern "C" int spex_graph_layout(const spex_graph_t *g, int32_t *bin_packed, int32_t *packed_words, int32_t *chunk_stride)
+{
+    SPEX_CHECK_ARG(g, "spex_graph_layout: NULL handle");
+    if (bin_packed) *bin_packed = g->row_ids ? 1 : 0;
+    if (packed_words) *packed_words = g->packed_words ? 1 : 0;
+    if (chunk_stride) *chunk_stride = g->chunk_stride;
     return SPEX_OK;
 }
 

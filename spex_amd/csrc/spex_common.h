@@ -386,8 +386,16 @@ struct spex_graph {
     uint32_t *chunk_mask = nullptr; // [n_chunks] end-of-row flags (16 bits)
     uint8_t *chunk_pad = nullptr;   // [n_chunks] number of padding entries at the end of the chunk
     uint32_t *chunk_eid = nullptr;  // [n_chunks * 16] edge id of each entry (keep-mask index); read only under dropout
-    bool row_ids = false;           // tasks pack non-adjacent rows (cache-resident graphs): the kernel reads chunk_row
-    int32_t *chunk_row = nullptr;   // [n_chunks * 16] output row of each entry, only when row_ids
+    bool row_ids = false;           // tasks pack non-adjacent rows (cache-resident graphs): every entry carries its output row
+    int32_t *chunk_row = nullptr;   // [n_chunks * 16] output row of each entry, only when row_ids && !packed_words
+    // Packed words (bin-packed tables of at most 65 536 rows — their columns are at most 65 536 anyway — whose packs hold 64
+    // entries, i.e. chunk_stride <= 4, unless SPEX_PACK_WORDS=0, read at creation): chunk_off holds (output row << 16) | source row
+    // and there is NO chunk_row array — 8 bytes of metadata per entry instead of 12, one vector load per task less.  The chunk
+    // kernels tell the layouts apart by the null chunk_row, once per wave, and split the word once per lane; a padding slot's row
+    // half is never read.  chunk_body splits in a task's FIRST super-chunk only: a packed handle has no task beyond four chunks
+    // (max_task_chunks, checked by the packer and again by every d == 64 launch).
+    bool packed_words = false;
+    int32_t max_task_chunks = 0;    // the largest task.y of the table (kind-3 row lists, which run no chunk, not counted)
     // Implied positions (bin-packed tables, unless SPEX_PACK_IMPLIED=0): task k's chunks start at chunk k * chunk_stride
     // (chunk_stride = the pack capacity in chunks: 4, or 5 / 6 where the packer raised it), so the d == 64 kernel requests a wave's
     // first 64 entries of metadata together with its task record; task.x is still stored (= k * chunk_stride) and the slots no task

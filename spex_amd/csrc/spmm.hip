@@ -240,6 +240,7 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_wide_kernel(
     const int wg = xcd_contiguous ? xcd_contiguous_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;     // (placement: see chunk_body)
     const int tid = wg * kWgWaves + wave;
     if (tid >= n_tasks) return;  // whole workgroups only (n_tasks is a multiple of kWgWaves)
+    const bool packed = ROWIDS && chunk_row == nullptr;   // (output row << 16) | source row in chunk_off, no chunk_row: see chunk_body
     const int4 t = task[tid];
     const int kind = t.w & 3;
     const float *__restrict__ Xl = X + lane * V;
@@ -277,11 +278,17 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_wide_kernel(
             const size_t e = (size_t)(t.x + sc) * kChunk + lane;
             my_off = __builtin_nontemporal_load(chunk_off + e);   // metadata is read once per launch
             my_val = __builtin_nontemporal_load(chunk_val + e);
-            if (ROWIDS) my_row = __builtin_nontemporal_load(chunk_row + e);
-            if (MASKED) own_off = drop_lane(drop, __builtin_nontemporal_load(drop.chunk_eid + e), my_val, my_off);
+            if (ROWIDS && !packed) my_row = __builtin_nontemporal_load(chunk_row + e);
+            uint32_t eid = 0u;
+            if (MASKED) eid = __builtin_nontemporal_load(drop.chunk_eid + e);
+            if (lane < nc) my_mask = __builtin_nontemporal_load(chunk_mask + t.x + sc + lane);   // (in front of the split: see chunk_body)
+            if (packed) {
+                my_row = (int)(my_off >> 16);
+                my_off &= 0xFFFFu;
+            }
+            if (MASKED) own_off = drop_lane(drop, eid, my_val, my_off);
         }
         if (MASKED) drop_bits = drop_stand_in(lane < nc * kChunk, own_off, my_off);
-        if (lane < nc) my_mask = __builtin_nontemporal_load(chunk_mask + t.x + sc + lane);
         for (int c = 0; c < nc; ++c) {
             const uint32_t mask = (uint32_t)__builtin_amdgcn_readlane((int)my_mask, c);
             const uint32_t dbits = MASKED ? (uint32_t)(drop_bits >> (c * kChunk)) & 0xFFFFu : 0u;
@@ -330,7 +337,8 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_chunk_wide_kernel(
     }
     if (ROWIDS && kind == 3) {                // a list of such rows (see the d == 64 kernel)
         const int count = t.w >> 4;
-        const int my_r = lane < count ? chunk_row[(size_t)t.x * kChunk + lane] : 0;
+        int my_r = 0;
+        if (lane < count) my_r = packed ? (int)(chunk_off[(size_t)t.x * kChunk + lane] >> 16) : chunk_row[(size_t)t.x * kChunk + lane];
         for (int k0 = 0; k0 < count; k0 += kBatch) {    // the rows' epilogue operands in flight together (see the d == 64 kernel)
             vec e[kBatch];
 #pragma unroll
@@ -744,6 +752,8 @@ int launch_spmm(const spex_graph *g, const float *X, float *Y, const float *add_
         //  contiguous fp32 [*, 64 V] tensor is)
         SPEX_CHECK_ARG(((((uintptr_t)X) | ((uintptr_t)Y) | ((uintptr_t)add_in) | ((uintptr_t)acc_in) | ((uintptr_t)acc_out)) & 15) == 0,
                        "spex_spmm_f32: X / Y / add_in / acc_in / acc_out must be 16-byte aligned");
+        // (chunk_body splits packed words in a task's first super-chunk only and reads chunk_row in the later ones)
+        SPEX_CHECK_ARG(!(g->packed_words && g->max_task_chunks > 4), "spex_spmm_f32: packed words on a table with tasks of %d chunks", g->max_task_chunks);
         const int xcd_contig = ((int64_t)g->n_cols * d * 4 <= (int64_t)16 << 20) ? 1 : 0;  // source table <= 16 MiB
         const DropArgs da = drop_args(g);
         // rows beyond kWgRowMax entries: folded inside the d == 64 launch (SPEX_HUB_FOLD=0: by the fix-up launch, as for the wide kernels)

@@ -132,6 +132,7 @@ int launch_spmm_bf16(const spex_graph *g, const uint16_t *X16, float *Y, uint16_
         const int rc = order_scratch(g, stream, scratch_lock);
         if (rc) return rc;
     }
+    SPEX_CHECK_ARG(!(g->packed_words && g->max_task_chunks > 4), "spex_spmm_bf16_f32: packed words on a table with tasks of %d chunks", g->max_task_chunks);
     const int xcd_contig = ((int64_t)g->n_cols * 64 * 2 <= (int64_t)16 << 20) ? 1 : 0;  // source table <= 16 MiB
     const DropArgs da = drop_args(g);
     if (acc_out) launch_chunk_bf16<1>(masked, g->row_ids, grid, block, stream, X16, g, Y, Y16, acc_in, acc_div, acc_out, da, xcd_contig);

@@ -247,8 +247,9 @@ __device__ __forceinline__ f4 finish(const ChunkSide<uint16_t> &, f4 v) { return
 //     as the matrix streams from HBM (29 ms vs 13 ms per launch on a 2^23-node graph); buffer loads with a scalar
 //     offset are ~25 % slower than global loads when the source table is cache-resident.
 // Hence this shape:
-//   * per 64 entries the wave loads source-row index, value (and, for bin-packed tasks, output row) with ONE coalesced
-//     vector load each — lane k holds entry k — and hands them to the scalar side with v_readlane;
+//   * per 64 entries the wave loads source-row index, value (and, for bin-packed tasks, output row — in the high half of the
+//     source-row word where the handle packs its words, spex_common.h) with ONE coalesced vector load each — lane k holds
+//     entry k — and hands them to the scalar side with v_readlane;
 //   * per 16-entry chunk: 16 independent `global_load_dword` (scalar row base + lane offset; `global_load_ushort` from a bf16
 //     table, whose row is 128 bytes — one L2 line where the fp32 row is two) issued back to back,
 //     then 16 x { v_fmac; s_bitcmp on the chunk's end-of-row mask; branch }.  A row's epilogue operand (running layer
@@ -310,6 +311,18 @@ __device__ __forceinline__ void chunk_body(
     // the same round trip as the record, instead of behind it; the lanes beyond the task's chunks are cut off once the record is in (a
     // null task loads and discards: every position below n_tasks * chunk_stride chunks exists, and chunk_stride >= 4).
     const bool implied = ROWIDS && chunk_stride != 0;
+    // Packed words (spex_common.h: packed_words; bin-packed tables only): the handle has no chunk_row array, an entry's word is
+    // (output row << 16) | source row.  Told apart by the null pointer, a scalar test once per wave; the word is split once per lane
+    // (super_chunk, in front of the dropout decision and the v_readlanes), never per gathered entry.
+    // (the test is re-made from the pointer at every use, behind an empty asm: as one named value the compiler carries it across the
+    //  chunk loop in an SGPR pair of its own, which costs the edge-dropout fold forms — at 100 SGPRs — their eighth wave)
+    auto is_packed = [&]() __attribute__((always_inline)) {
+        if (!ROWIDS) return false;
+        unsigned long long p = (unsigned long long)chunk_row;
+        asm volatile("" : "+s"(p));
+        return p == 0ull;
+    };
+    const bool packed = is_packed();
     uint32_t pre_off = 0u, pre_mask = 0u, pre_eid = 0u;
     int pre_row = 0;
     float pre_val = 0.0f;
@@ -317,7 +330,7 @@ __device__ __forceinline__ void chunk_body(
         const size_t c0 = (size_t)tid * (size_t)chunk_stride, e = c0 * kChunk + lane;
         pre_off = __builtin_nontemporal_load(chunk_off + e);
         pre_val = __builtin_nontemporal_load(chunk_val + e);
-        pre_row = __builtin_nontemporal_load(chunk_row + e);
+        if (!packed) pre_row = __builtin_nontemporal_load(chunk_row + e);
         if (MASKED) pre_eid = __builtin_nontemporal_load(drop.chunk_eid + e);
         pre_mask = __builtin_nontemporal_load(chunk_mask + c0 + (lane & 3));
     }
@@ -353,7 +366,10 @@ __device__ __forceinline__ void chunk_body(
     if (ROWIDS && kind == 3) {
         const int count = t.w >> 4;
         int my_r = -1;
-        if (lane < count) my_r = implied ? pre_row : chunk_row[(size_t)t.x * kChunk + lane];
+        if (lane < count) {
+            if (packed) my_r = (int)((implied ? pre_off : chunk_off[(size_t)t.x * kChunk + lane]) >> 16);
+            else my_r = implied ? pre_row : chunk_row[(size_t)t.x * kChunk + lane];
+        }
         const int sub = lane & 15, grp = lane >> 4;
         const f4 zero = (f4)(0.0f);
         for (int k0 = 0; k0 < count; k0 += 16) {
@@ -408,8 +424,16 @@ __device__ __forceinline__ void chunk_body(
                 const size_t e = (size_t)(t.x + sc) * kChunk + lane;
                 my_off = __builtin_nontemporal_load(chunk_off + e);   // metadata is read once per launch
                 my_val = __builtin_nontemporal_load(chunk_val + e);
-                if (ROWIDS) my_row = __builtin_nontemporal_load(chunk_row + e);
+                if (ROWIDS) my_row = __builtin_nontemporal_load(chunk_row + e);   // (a later super-chunk: never on a packed handle, below)
                 if (MASKED) eid = __builtin_nontemporal_load(drop.chunk_eid + e);
+            }
+            // Packed words are split in the FIRST super-chunk only: the packer packs words only where no task has more than four
+            // chunks (graph.hip: max_task_chunks, checked again at launch), so a packed handle never runs a later one, and that path
+            // stays the statement it was — with the test and the split in it, the Weibo shape (tasks of 5 chunks) ran 0.4-0.9 us per
+            // launch slower, packed (profiles/packed_words/any_stride_*) or not (gated_later_test_*).
+            if (first && is_packed()) {      // (in front of drop_lane: 0xFFFFFFFF is a legal packed word, and its mark on a 16-bit source row)
+                my_row = (int)(my_off >> 16);
+                my_off &= 0xFFFFu;
             }
             if (MASKED) own_off = drop_lane(drop, eid, my_val, my_off);
         }
@@ -474,7 +498,7 @@ __device__ __forceinline__ void chunk_body(
                 const size_t e = (size_t)t.x * kChunk + lane;
                 pre_off = __builtin_nontemporal_load(chunk_off + e);
                 pre_val = __builtin_nontemporal_load(chunk_val + e);
-                pre_row = __builtin_nontemporal_load(chunk_row + e);
+                if (!packed) pre_row = __builtin_nontemporal_load(chunk_row + e);
                 if (MASKED) pre_eid = __builtin_nontemporal_load(drop.chunk_eid + e);
                 if (lane < nc0) pre_mask = __builtin_nontemporal_load(chunk_mask + t.x + lane);   // (the table ends with its last chunk)
             }

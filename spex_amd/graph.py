@@ -186,6 +186,9 @@ class SpexGraph:
         nl, ns = ctypes.c_int32(), ctypes.c_int32()
         _lib.call("spex_graph_info", self._h, None, None, None, ctypes.byref(nl), ctypes.byref(ns))
         self.n_long_rows, self.n_segments = nl.value, ns.value
+        bp, pw, cs = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _lib.call("spex_graph_layout", self._h, ctypes.byref(bp), ctypes.byref(pw), ctypes.byref(cs))
+        self.bin_packed, self.packed_words, self.chunk_stride = bool(bp.value), bool(pw.value), cs.value
         self._mask_ref = None
         self.mask_mode = 0
 
