@@ -306,6 +306,17 @@ int spex_scatter_add_owned_rows_f32(float *upd, const int64_t *pos, int64_t K, i
 int spex_adam_step_f32(float *p, const float *g, float *m, float *v, int64_t n, int32_t t, float lr, float beta1,
                        float beta2, float eps, float *zero_buf, void *stream);
 
+/* Row-sparse ("lazy") Adam over [n_rows, 64] tables: the update above, by the same code and therefore with the same roundings, at the
+ * rows list[k], k < min(*count, max_count), and nowhere else — p, m, v of every other row are neither read nor written; t is the
+ * global step count.  list, count: device memory (a spex_unique_rows_i32 / spex_frontier_rows_i32 list); entries must be distinct;
+ * values outside [0, n_rows) are skipped.  The count is read on the device; a fixed grid strides over the list (max_count may be as
+ * loose a bound as n_rows).  The masking law of torch.optim.SparseAdam with torch.optim.Adam's placement of eps (SparseAdam itself
+ * puts eps elsewhere: no bit-level oracle).  d != 64: SPEX_ERR_UNSUPPORTED.  Pointers 16-byte aligned; p, g, m, v four buffers.
+ * spex_zero_rows_f32: x[list[k], 0 .. d) = 0 for the same k (d a multiple of 4, x 16-byte aligned); other rows are not written. */
+int spex_adam_rows_f32(float *p, const float *g, float *m, float *v, const int32_t *list, const int32_t *count, int32_t max_count,
+                       int32_t n_rows, int32_t d, int32_t t, float lr, float beta1, float beta2, float eps, void *stream);
+int spex_zero_rows_f32(float *x, const int32_t *list, const int32_t *count, int32_t max_count, int32_t n_rows, int32_t d, void *stream);
+
 /* The same update for a small parameter block whose gradient arrives as n_parts partial blocks (block j at g_parts +
  * j * part_stride): g = the blocks added up in order, then Adam.  Used for NGCF's layer weights, whose gradient leaves
  * spex_ngcf_layer_bwd_rows_f32 as one block per workgroup.
@@ -959,9 +970,15 @@ enum {
                                          * 64-wide descriptor with a wrong d, which would gather out of bounds — so a wider d is an opt-in */
     SPEX_STEP_BF16_GATHER = 64,         /* the one-call LightGCN steps (BCE, exact BPR) and every epoch over them: bf16 gather tables, d == 64
                                          * and L = 2 or 3 only; the descriptor's E0_16 / ws16 fields are read (see spex_lightgcn_step_t) */
-    SPEX_STEP_FRONTIER = 128            /* the one-call LightGCN steps (BCE, exact BPR) and every epoch over them: forward layer L - 1 and the
+    SPEX_STEP_FRONTIER = 128,           /* the one-call LightGCN steps (BCE, exact BPR) and every epoch over them: forward layer L - 1 and the
                                          * backward product behind the batch kernel's push run over the batch's frontier, not the whole
                                          * graph; d == 64, L >= 2; the descriptor's frontier_* fields are read (see spex_lightgcn_step_t) */
+    SPEX_STEP_SPARSE_ADAM = 256,        /* with SPEX_STEP_FRONTIER at L == 2 only: row-sparse ("lazy") Adam — p, m, v change at the rows of the
+                                         * batch's two-hop set F2 and nowhere else, the step count is global; no launch of the step but the
+                                         * first flagged one passes over a whole fp32 table.  Its own semantics: see spex_lightgcn_step_t */
+    SPEX_STEP_GRAD_ROWS_LISTED = 512    /* state, not a mode: "grad_E0 is zero outside frontier_list[0 .. frontier_counts[2])".  Set in the
+                                         * descriptor by a SPEX_STEP_SPARSE_ADAM step once its launches are queued, cleared by every other
+                                         * step of these entry points; a caller that writes grad_E0 or frontier_list itself clears it */
 };
 /* The north-star step — LightGCN L-layer propagation + the fused BPR gather + dot + sigmoid + SGD kernel over T triples — as one
  * call of at most L + 1 launches: EVERY whole-graph layer in the plain form (no epilogue operand, one output stream); the layer-1 launch also sets
@@ -1018,7 +1035,8 @@ typedef struct spex_lightgcn_step {
     int32_t slot_capacity, n_user_rows, L, d;
     float lr, beta1, beta2, eps;
     int32_t t;
-    int32_t flags;                           /* SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE / _PUSH, SPEX_STEP_WIDE, SPEX_STEP_BF16_GATHER, SPEX_STEP_FRONTIER */
+    int32_t flags;                           /* SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE / _PUSH, SPEX_STEP_WIDE, SPEX_STEP_BF16_GATHER, SPEX_STEP_FRONTIER,
+                                              * SPEX_STEP_SPARSE_ADAM; SPEX_STEP_GRAD_ROWS_LISTED is written back by the steps */
     /* appended for spex_lightgcn_step_bpr_adam_f32 / spex_lightgcn_epoch_bpr_f32 (the BCE entry points never read them): */
     float weight_decay;                      /* >= 0: upstream LightGCN's L2 term on the E0 rows of the batch */
     int32_t *row_counts;                     /* [2, N] int32, all-zero before the first call: per-row occurrence counts, by step parity.
@@ -1029,11 +1047,34 @@ typedef struct spex_lightgcn_step {
                                               * every call leaves it so */
     uint16_t *ws16;                          /* [2, N, 64] bf16: the later layers' gather tables, then the backward's */
     /* appended for SPEX_STEP_FRONTIER (without the flag no entry point reads them): */
-    int32_t *frontier_list;                  /* [N] int32: [Bset | F1 minus Bset] of the current step */
+    int32_t *frontier_list;                  /* [N] int32: [Bset | F1 minus Bset] of the current step (SPEX_STEP_SPARSE_ADAM: [.. | F2 minus F1]) */
     int32_t *frontier_stamp;                 /* [N] int32, all-zero before the first call; never cleared afterwards */
-    int32_t *frontier_counts;                /* [2] int32: |Bset|, |F1| of the current step */
+    int32_t *frontier_counts;                /* [2] int32: |Bset|, |F1| of the current step; with SPEX_STEP_SPARSE_ADAM [4] int32: |Bset|, |F1|,
+                                              * |F2|, one spare */
     int32_t frontier_epoch;                  /* the last stamp used (0 at first); advanced by every flagged step */
 } spex_lightgcn_step_t;
+/* flags & SPEX_STEP_SPARSE_ADAM — row-sparse Adam for the L == 2 frontier steps (with SPEX_STEP_FRONTIER, d == 64; BCE and exact BPR,
+ * weight_decay > 0 too, and every epoch, sampled-epoch and train_*_sampled call over them).  The step computes the forward, the loss
+ * and the gradient of the SPEX_STEP_FRONTIER step.  At L == 2 that gradient's support is structural: it lies in
+ *   F2 = F1 U { col[e] : e a stored entry of a row in F1 },
+ * the rows the frontier push can write (a second spex_frontier_rows_i32 over the same list, stamp table and epoch: frontier_list =
+ * [Bset | F1 minus Bset | F2 minus F1], frontier_counts[2] = |F2|).  Then
+ *   rows in F2:       p, m, v are updated by the dense pass's own expression (spex_adam_step_f32's, shared code: the same roundings)
+ *                     with the global step count t in both bias corrections; the BPR step's L2 term is included.  F2 is the structural
+ *                     set whatever the values: a listed row whose gradient happens to be zero is still updated.
+ *   rows outside F2:  p, m, v are neither read nor written: they stand still bit for bit and do NOT coast on their momentum, as they
+ *                     do under dense Adam.  This is a different optimiser, not a faster route to the same numbers.
+ * That is the masking law of torch.optim.SparseAdam with the eps placement of torch.optim.Adam (denom = sqrt(v) / sqrt(1 - beta2^t)
+ * + eps); SparseAdam itself places eps elsewhere, so it is no bit-level oracle for this mode.
+ * Work: the Adam pass (spex_adam_rows_f32's kernel), the clears of g_out (at Bset) and of the push target ws_bwd[0] (at F1) and the
+ * loss sum (one addend in the dense pass's fixed order: the step's loss sum is the SPEX_STEP_FRONTIER step's bit for bit from the
+ * same state) are proportional to |F2|.  grad_E0 holds the step's gradient afterwards (zero outside F2), so the pass cannot clear
+ * it: the NEXT flagged step clears it as its first launch through the list this step left, if the descriptor still carries
+ * SPEX_STEP_GRAD_ROWS_LISTED (see the flag); without the bit it clears the whole table once.  The exact BPR step clears the other
+ * parity's row_counts table whole (4 N bytes) instead of in the Adam pass; the tables satisfy the same contract afterwards.
+ * g_out and ws_bwd[0] are all-zero after every step, as without the flag.
+ * Refused before anything touches the device (t not advanced): SPEX_STEP_SPARSE_ADAM without SPEX_STEP_FRONTIER, or with L != 2 ->
+ * SPEX_ERR_INVALID; everything SPEX_STEP_FRONTIER refuses stays refused. */
 /* flags & SPEX_STEP_FRONTIER — the exact steps with one more level taken inward (d == 64, L >= 2, fp32 tables).  With Bset the batch's
  * distinct rows and F1 = Bset U their stored columns (spex_unique_rows_i32 + spex_frontier_rows_i32 into frontier_list):
  *   forward:   layers 1 .. L - 2 over the whole graph as without the flag; layer L - 1 at the rows of F1 only

@@ -107,6 +107,8 @@ SIGNATURES = {
     "spex_spmm_push_rows_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_vp, c_i32, c_vp]),
     "spex_spmm_push_rows_scaled_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_i32, c_vp]),
     "spex_frontier_rows_i32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "spex_adam_rows_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp]),
+    "spex_zero_rows_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "spex_spmm_rowlist_dev_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_f32, c_i32, c_vp]),
     "spex_expert_gate_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "spex_expert_gate_bwd_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
@@ -210,6 +212,8 @@ STEP_BPR_PUSH = 16              # spex_hip.h: SPEX_STEP_BPR_PUSH
 STEP_WIDE = 32                  # spex_hip.h: SPEX_STEP_WIDE (exact BPR step at d = 128 / 256)
 STEP_BF16_GATHER = 64           # spex_hip.h: SPEX_STEP_BF16_GATHER (bf16 gather tables in the one-call LightGCN steps, d = 64, L = 2 / 3)
 STEP_FRONTIER = 128             # spex_hip.h: SPEX_STEP_FRONTIER (layer L - 1 and the second backward product over the batch's frontier, d = 64, L >= 2)
+STEP_SPARSE_ADAM = 256          # spex_hip.h: SPEX_STEP_SPARSE_ADAM (row-sparse Adam over the batch's two-hop set, with STEP_FRONTIER at L = 2)
+STEP_GRAD_ROWS_LISTED = 512     # spex_hip.h: SPEX_STEP_GRAD_ROWS_LISTED (state written back by the steps: grad_E0 is zero outside the frontier list)
 
 
 class NGCFStepDesc(ctypes.Structure):

@@ -22,6 +22,27 @@ __device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, flo
     p = p - step_size * (m / denom);
 }
 
+// The pieces of a float4 of parameters that adam_body (the dense pass) and adam_rows_kernel (the row-sparse pass) share, so that
+// both round alike: the add_g share, the L2 term, the update.
+__device__ __forceinline__ void add_share(float4 &G, const float4 A, float add_div)
+{
+    G.x = G.x + A.x / add_div; G.y = G.y + A.y / add_div; G.z = G.z + A.z / add_div; G.w = G.w + A.w / add_div;
+}
+
+__device__ __forceinline__ void add_l2(float4 &G, const float4 P, float c)
+{
+    G.x = G.x + c * P.x; G.y = G.y + c * P.y; G.z = G.z + c * P.z; G.w = G.w + c * P.w;
+}
+
+__device__ __forceinline__ void adam4(float4 &P, const float4 G, float4 &M, float4 &V, float w1, float beta2, float w2, float bc2_sqrt,
+                                      float eps, float step_size)
+{
+    adam1(P.x, G.x, M.x, V.x, w1, beta2, w2, bc2_sqrt, eps, step_size);
+    adam1(P.y, G.y, M.y, V.y, w1, beta2, w2, bc2_sqrt, eps, step_size);
+    adam1(P.z, G.z, M.z, V.z, w1, beta2, w2, bc2_sqrt, eps, step_size);
+    adam1(P.w, G.w, M.w, V.w, w1, beta2, w2, bc2_sqrt, eps, step_size);
+}
+
 // (g and zero_buf carry no __restrict__: the caller may pass the gradient buffer itself to be cleared — every element is
 // read before the same thread clears it)
 // L2: the exact BPR step's pass — gradient += l2.scale * l2.count[row] * p[row] (rows of 64 / 128 / 256 parameters: 1 << l2.shift
@@ -73,26 +94,18 @@ __device__ __forceinline__ void adam_body(float *__restrict__ p, const float *g,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         float4 P = reinterpret_cast<float4 *>(p)[i];
         float4 G = reinterpret_cast<const float4 *>(g)[i];
-        if (add_g) {      // gradient = g + add_g / add_div: the mean's own share g/(L+1) of the LAST backward product, added here (this
-                          // pass reads add_g anyway, to clear it) so that that product runs in the plain form
-            const float4 A = reinterpret_cast<const float4 *>(add_g)[i];
-            G.x = G.x + A.x / add_div; G.y = G.y + A.y / add_div; G.z = G.z + A.z / add_div; G.w = G.w + A.w / add_div;
-        }
+        // gradient = g + add_g / add_div: the mean's own share g/(L+1) of the LAST backward product, added here (this pass reads
+        // add_g anyway, to clear it) so that that product runs in the plain form
+        if (add_g) add_share(G, reinterpret_cast<const float4 *>(add_g)[i], add_div);
         if constexpr (L2) {
             const int64_t row = i >> l2.shift;
-            if (l2.count) {
-                const float c = l2.scale * (float)l2.count[row];
-                G.x = G.x + c * P.x; G.y = G.y + c * P.y; G.z = G.z + c * P.z; G.w = G.w + c * P.w;
-            }
+            if (l2.count) add_l2(G, P, l2.scale * (float)l2.count[row]);
             if (l2.clear && (i & (((int64_t)1 << l2.shift) - 1)) == 0) l2.clear[row] = 0;
             if (l2.g_store) reinterpret_cast<float4 *>(l2.g_store)[i] = G;
         }
         float4 M = reinterpret_cast<float4 *>(m)[i];
         float4 V = reinterpret_cast<float4 *>(v)[i];
-        adam1(P.x, G.x, M.x, V.x, w1, beta2, w2, bc2_sqrt, eps, step_size);
-        adam1(P.y, G.y, M.y, V.y, w1, beta2, w2, bc2_sqrt, eps, step_size);
-        adam1(P.z, G.z, M.z, V.z, w1, beta2, w2, bc2_sqrt, eps, step_size);
-        adam1(P.w, G.w, M.w, V.w, w1, beta2, w2, bc2_sqrt, eps, step_size);
+        adam4(P, G, M, V, w1, beta2, w2, bc2_sqrt, eps, step_size);
         reinterpret_cast<float4 *>(p)[i] = P;
         if constexpr (SHADOW) {
             typedef unsigned short h4 __attribute__((ext_vector_type(4)));
@@ -142,7 +155,163 @@ __global__ __launch_bounds__(256) void adam_shadow_kernel(float *__restrict__ p,
                         main_blocks, add_g, add_div, l2, p16);
 }
 
+// Row-sparse ("lazy") Adam: the update of adam_body at the rows list[k], k < min(*count, max_count), of [n_rows, 64] tables and
+// nowhere else — p, m, v of every other row are neither read nor written.  A row is 16 float4s: 16 lanes per row, four list slots
+// per wave and pass, kRowsFly such groups loaded before the first is updated (eight random 256-byte rows of each of p, g, m, v in
+// flight per wave).  A fixed grid strides over the list; the count is read on the device; list values outside [0, n_rows) are
+// skipped; entries are distinct, so no two lanes meet on a row.  The one-call steps' side jobs, by list position (a frontier list is
+// [Bset | F1 minus Bset | F2 minus F1]): below *count_b the add_g share is read, added and cleared and (L2) the row's occurrence
+// count enters the gradient — rows behind it have an all-zero add_g row and a zero count, for which the dense pass adds exact
+// zeros; below *count_z the row of zero_buf is cleared; L2 stores the whole gradient of a listed row to l2.g_store (l2.clear is
+// not served: the caller clears that table).  The per-sample losses are summed by the first wave in adam_body's order.
+constexpr int kRowsFly = 2;
+
+template <bool L2>
+__global__ __launch_bounds__(256) void adam_rows_kernel(float *__restrict__ p, const float *g, float *__restrict__ m,
+                                                        float *__restrict__ v, const spex::AdamRowList rl, float w1, float beta2,
+                                                        float w2, float bc2_sqrt, float eps, float step_size,
+                                                        const float *__restrict__ loss_rows, int n_loss, float *loss_sum,
+                                                        const spex::L2Rows l2)
+{
+    if (loss_rows && blockIdx.x == 0 && threadIdx.x < spex::kWave) {
+        float t = 0.0f;
+        for (int i = threadIdx.x; i < n_loss; i += spex::kWave) t += loss_rows[i];
+        t = spex::wave_sum_f32(t);
+        if (threadIdx.x == 0) *loss_sum += t;
+    }
+    const int cnt = *rl.count;
+    const int n = cnt < rl.max_count ? cnt : rl.max_count;
+    const int nb = rl.count_b ? *rl.count_b : 0, nz = rl.count_z ? *rl.count_z : 0;
+    const int lane = threadIdx.x & (spex::kWave - 1), sub = lane >> 4, c4 = lane & 15;
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t base = wave * (4 * kRowsFly); base < n; base += n_waves * (4 * kRowsFly)) {
+        int64_t k[kRowsFly];
+        size_t at[kRowsFly];
+        bool ok[kRowsFly], head[kRowsFly];
+        float4 P[kRowsFly], G[kRowsFly], M[kRowsFly], V[kRowsFly], A[kRowsFly];
+        float c[kRowsFly];
+#pragma unroll
+        for (int u = 0; u < kRowsFly; ++u) {
+            k[u] = base + u * 4 + sub;
+            const int r = k[u] < n ? rl.list[k[u]] : -1;
+            ok[u] = r >= 0 && r < rl.n_rows;                 // never index the tables out of range
+            at[u] = (size_t)(ok[u] ? r : 0) * 16 + c4;
+            head[u] = ok[u] && k[u] < nb;
+            c[u] = 0.0f;
+            if constexpr (L2)
+                if (head[u] && l2.count) c[u] = l2.scale * (float)l2.count[r];
+        }
+#pragma unroll
+        for (int u = 0; u < kRowsFly; ++u) {
+            if (!ok[u]) continue;
+            P[u] = reinterpret_cast<float4 *>(p)[at[u]];
+            G[u] = reinterpret_cast<const float4 *>(g)[at[u]];
+            M[u] = reinterpret_cast<float4 *>(m)[at[u]];
+            V[u] = reinterpret_cast<float4 *>(v)[at[u]];
+            if (head[u] && rl.add_g) A[u] = reinterpret_cast<const float4 *>(rl.add_g)[at[u]];
+        }
+#pragma unroll
+        for (int u = 0; u < kRowsFly; ++u) {
+            if (!ok[u]) continue;
+            if (head[u] && rl.add_g) {
+                add_share(G[u], A[u], rl.add_div);
+                reinterpret_cast<float4 *>(rl.add_g)[at[u]] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+            if constexpr (L2) {
+                if (head[u] && l2.count) add_l2(G[u], P[u], c[u]);
+                if (l2.g_store) reinterpret_cast<float4 *>(l2.g_store)[at[u]] = G[u];
+            }
+            adam4(P[u], G[u], M[u], V[u], w1, beta2, w2, bc2_sqrt, eps, step_size);
+            reinterpret_cast<float4 *>(p)[at[u]] = P[u];
+            reinterpret_cast<float4 *>(m)[at[u]] = M[u];
+            reinterpret_cast<float4 *>(v)[at[u]] = V[u];
+            if (rl.zero_buf && k[u] < nz) reinterpret_cast<float4 *>(rl.zero_buf)[at[u]] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+}
+
+// x[list[k], :] = 0 for k < min(*count, max_count): one float4 per thread and pass, a fixed grid striding over the listed rows.
+__global__ __launch_bounds__(256) void zero_rows_kernel(float *__restrict__ x, const int32_t *__restrict__ list,
+                                                        const int32_t *__restrict__ count, int32_t max_count, int32_t n_rows, int32_t d4)
+{
+    const int cnt = *count;
+    const int64_t n = (int64_t)(cnt < max_count ? cnt : max_count) * d4;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int r = list[i / d4];
+        if (r < 0 || r >= n_rows) continue;                    // never index the table out of range
+        reinterpret_cast<float4 *>(x)[(size_t)r * d4 + (size_t)(i % d4)] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
 }  // namespace
+
+// The row-sparse pass (adam_rows_kernel) with the one-call steps' side jobs.
+int spex::adam_rows(float *p, const float *g, float *m, float *v, const spex::AdamRowList &rl, int32_t t, float lr, float beta1, float beta2,
+                    float eps, void *stream, const float *loss_rows, int32_t n_loss, float *loss_sum, const spex::L2Rows *l2_in)
+{
+    SPEX_CHECK_ARG(p && g && m && v && rl.list && rl.count, "spex_adam_rows_f32: NULL pointer");
+    SPEX_CHECK_ARG(rl.max_count >= 0 && rl.n_rows >= 0 && t >= 1, "spex_adam_rows_f32: max_count=%d n_rows=%d t=%d (t counts from 1)", rl.max_count,
+                   rl.n_rows, t);
+    SPEX_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)rl.add_g | (uintptr_t)rl.zero_buf) & 15) == 0,
+                   "spex_adam_rows_f32: pointers must be 16-byte aligned");
+    SPEX_CHECK_ARG(p != m && p != v && m != v && (const float *)p != g && (const float *)m != g && (const float *)v != g,
+                   "spex_adam_rows_f32: p, g, m, v must be four buffers");
+    SPEX_CHECK_ARG(!rl.add_g || (rl.count_b && rl.add_div != 0.0f && rl.add_g != p && rl.add_g != m && rl.add_g != v),
+                   "spex_adam_rows_f32: add_g without its count cell, add_div == 0, or add_g aliases p, m or v");
+    SPEX_CHECK_ARG(!rl.zero_buf || (rl.count_z && rl.zero_buf != p && rl.zero_buf != m && rl.zero_buf != v && (const float *)rl.zero_buf != g),
+                   "spex_adam_rows_f32: zero_buf without its count cell, or zero_buf aliases p, g, m or v");
+    SPEX_CHECK_ARG(!loss_rows || (loss_sum && n_loss >= 0), "spex_adam_rows_f32: loss rows without an accumulator");
+    spex::L2Rows l2{};
+    if (l2_in) l2 = *l2_in;
+    SPEX_CHECK_ARG(!l2_in || (l2.shift == 4 && (!l2.count || rl.count_b) && (((uintptr_t)l2.g_store) & 15) == 0 && l2.g_store != p && l2.g_store != m
+                              && l2.g_store != v),
+                   "spex_adam_rows_f32: the L2 form takes rows of 64, the Bset count cell and a 16-byte aligned gradient store");
+    if (rl.n_rows == 0 || (rl.max_count == 0 && !loss_rows)) return SPEX_OK;
+    const double bc1 = 1.0 - pow((double)beta1, (double)t);
+    const double bc2 = 1.0 - pow((double)beta2, (double)t);
+    const float step_size = (float)((double)lr / bc1);
+    const float bc2_sqrt = (float)sqrt(bc2);
+    constexpr int kSlotsPerBlock = 4 * 4 * kRowsFly;          // four waves of four-row groups
+    int64_t blocks = ((int64_t)rl.max_count + kSlotsPerBlock - 1) / kSlotsPerBlock;
+    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+#define SPEX_ROWS_GO(KERNEL)                                                                                                                 \
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rl, 1.0f - beta1, beta2, 1.0f - beta2, \
+                       bc2_sqrt, eps, step_size, loss_rows, (int)n_loss, loss_sum, l2)
+    if (l2_in) SPEX_ROWS_GO(adam_rows_kernel<true>);
+    else SPEX_ROWS_GO(adam_rows_kernel<false>);
+#undef SPEX_ROWS_GO
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
+
+extern "C" int spex_adam_rows_f32(float *p, const float *g, float *m, float *v, const int32_t *list, const int32_t *count, int32_t max_count,
+                                  int32_t n_rows, int32_t d, int32_t t, float lr, float beta1, float beta2, float eps, void *stream)
+{
+    if (d != spex::kWave) {
+        spex::set_error("spex_adam_rows_f32: d == 64 only (got %d)", d);
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    spex::AdamRowList rl{};
+    rl.list = list;
+    rl.count = count;
+    rl.max_count = max_count;
+    rl.n_rows = n_rows;
+    return spex::adam_rows(p, g, m, v, rl, t, lr, beta1, beta2, eps, stream);
+}
+
+extern "C" int spex_zero_rows_f32(float *x, const int32_t *list, const int32_t *count, int32_t max_count, int32_t n_rows, int32_t d, void *stream)
+{
+    SPEX_CHECK_ARG(x && list && count, "spex_zero_rows_f32: NULL pointer");
+    SPEX_CHECK_ARG(max_count >= 0 && n_rows >= 0 && d >= 4 && d % 4 == 0 && (((uintptr_t)x) & 15) == 0,
+                   "spex_zero_rows_f32: max_count=%d n_rows=%d d=%d (whole float4s of a 16-byte aligned table)", max_count, n_rows, d);
+    if (max_count == 0 || n_rows == 0) return SPEX_OK;
+    int64_t blocks = ((int64_t)max_count * (d / 4) + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+    hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, list, count, max_count, n_rows, d / 4);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
 
 // Internal form with a second buffer to clear (the one-call training step keeps its push target all-zero this way).
 int spex::adam_step_z2(float *p, const float *g, float *m, float *v, int64_t n, int32_t t, float lr, float beta1, float beta2,

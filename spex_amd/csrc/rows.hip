@@ -35,8 +35,10 @@ __global__ __launch_bounds__(256) void unique_rows_kernel(const int64_t *__restr
 // seen this epoch.  One wave per INPUT row, lanes take entries; the rows found by a wave in one 64-entry run are appended with one
 // counter bump (the first new lane's atomic, the others take their rank among the new lanes).  n_in is read from a cell the launch
 // does not write (count_b), the appends go behind it through count_f: the launch never walks a row it appended itself — that would
-// be the two-hop set.  Every row is stamped at most once per epoch, so n_rows list entries always suffice.
+// be the two-hop set (SPEX_STEP_SPARSE_ADAM takes that set with a second launch over [0, |F1|), whose host-side bound is n_rows: a
+// bounded grid strides over the input).  Every row is stamped at most once per epoch, so n_rows list entries always suffice.
 constexpr int kFrontierWaves = 4;
+constexpr int kFrontierMaxWgs = 1 << 14;
 
 __global__ void frontier_init_kernel(const int32_t *__restrict__ count_b, int32_t *count_f) { *count_f = *count_b; }
 
@@ -45,24 +47,25 @@ __global__ __launch_bounds__(kWave *kFrontierWaves) void frontier_rows_kernel(
     int32_t max_b, int32_t *stamp, int32_t epoch, int32_t *list, int32_t *count_f)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const int k = blockIdx.x * kFrontierWaves + (threadIdx.x >> 6);
     const int n_in = *count_b < max_b ? *count_b : max_b;
-    if (k >= n_in) return;
-    const int r = list[k];
-    if (r < 0 || r >= n_rows) return;                      // never index the matrix out of range
-    const int beg = rowptr[r], end = rowptr[r + 1];
-    for (int base = beg; base < end; base += kWave) {
-        const int e = base + lane;
-        int c = -1;
-        if (e < end) c = col[e];
-        const bool fresh = c >= 0 && c < n_rows && atomicExch(stamp + c, epoch) != epoch;    // first visitor of the row this epoch
-        const unsigned long long m = __ballot(fresh);
-        if (m == 0) continue;
-        const int leader = (int)__builtin_ctzll(m);
-        int start = 0;
-        if (lane == leader) start = atomicAdd(count_f, (int)__builtin_popcountll(m));
-        start = __builtin_amdgcn_readlane(start, leader);
-        if (fresh) list[start + (int)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = c;
+    // (a grid of at most kFrontierMaxWgs workgroups strides over the input: the second hop's host-side bound is n_rows)
+    for (int64_t k = (int64_t)blockIdx.x * kFrontierWaves + (threadIdx.x >> 6); k < n_in; k += (int64_t)gridDim.x * kFrontierWaves) {
+        const int r = list[k];
+        if (r < 0 || r >= n_rows) continue;                    // never index the matrix out of range
+        const int beg = rowptr[r], end = rowptr[r + 1];
+        for (int base = beg; base < end; base += kWave) {
+            const int e = base + lane;
+            int c = -1;
+            if (e < end) c = col[e];
+            const bool fresh = c >= 0 && c < n_rows && atomicExch(stamp + c, epoch) != epoch;    // first visitor of the row this epoch
+            const unsigned long long m = __ballot(fresh);
+            if (m == 0) continue;
+            const int leader = (int)__builtin_ctzll(m);
+            int start = 0;
+            if (lane == leader) start = atomicAdd(count_f, (int)__builtin_popcountll(m));
+            start = __builtin_amdgcn_readlane(start, leader);
+            if (fresh) list[start + (int)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = c;
+        }
     }
 }
 
@@ -460,7 +463,8 @@ extern "C" int spex_frontier_rows_i32(const spex_graph_t *g, int32_t *list, cons
     hipLaunchKernelGGL(frontier_init_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, count_b, count_f);
     SPEX_HIP(hipGetLastError());
     if (max_b == 0 || g->n_rows == 0) return SPEX_OK;
-    hipLaunchKernelGGL(frontier_rows_kernel, dim3((unsigned)((max_b + kFrontierWaves - 1) / kFrontierWaves)), dim3(kWave * kFrontierWaves), 0,
+    const int64_t wgs = ((int64_t)max_b + kFrontierWaves - 1) / kFrontierWaves;
+    hipLaunchKernelGGL(frontier_rows_kernel, dim3((unsigned)(wgs < kFrontierMaxWgs ? wgs : kFrontierMaxWgs)), dim3(kWave * kFrontierWaves), 0,
                        (hipStream_t)stream, g->rowptr, g->col, g->n_rows, count_b, max_b, stamp, epoch, list, count_f);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;

@@ -34,6 +34,20 @@ int adam_step_z2(float *p, const float *g, float *m, float *v, int64_t n, int32_
                                                // p16: also receives bf16(the updated p), round to nearest even, from the same register —
                                                // the bf16 gather table of the next step; 8-byte aligned, n % 4 == 0
 
+struct AdamRowList {            // the rows of a row-sparse Adam pass and its side jobs by list position (optim.hip: adam_rows_kernel)
+    const int32_t *list = nullptr;    // rows list[k], k < min(*count, max_count), distinct; values outside [0, n_rows) are skipped
+    const int32_t *count = nullptr;   // device cell
+    int32_t max_count = 0, n_rows = 0;
+    const int32_t *count_b = nullptr; // device cell: positions below it read, add and clear add_g's row and carry the L2 count
+    float *add_g = nullptr;           // gradient += add_g / add_div at those positions (NULL: no such term)
+    float add_div = 1.0f;
+    const int32_t *count_z = nullptr; // device cell: positions below it clear zero_buf's row
+    float *zero_buf = nullptr;
+};
+int adam_rows(float *p, const float *g, float *m, float *v, const AdamRowList &rl, int32_t t, float lr, float beta1, float beta2, float eps,
+              void *stream, const float *loss_rows = nullptr, int32_t n_loss = 0, float *loss_sum = nullptr,
+              const L2Rows *l2 = nullptr);    // optim.hip: spex_adam_rows_f32 with the one-call steps' side jobs (d == 64)
+
 int dual_task_adam(float *p, float *m, float *v, const float *g_E0, float *g_raw, float *g_user, float *g_small, float *g_prop,
                    float *push_zero, float *loss, float *loss_acc, float *prec, int64_t n_table, int64_t n_user, int64_t n_trust,
                    int32_t B, int32_t T, int32_t n_rec, int32_t t, float lr, float beta1, float beta2, float eps, int fixed_weights,

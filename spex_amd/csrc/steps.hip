@@ -104,9 +104,48 @@ static int frontier_step_check(const spex_lightgcn_step_t *s, const char *who)
     return SPEX_OK;
 }
 
-// Bset, then F1 behind it, of a batch of up to three index lists into frontier_list; frontier_counts = { |Bset|, |F1| }.
+// ---- SPEX_STEP_SPARSE_ADAM (with SPEX_STEP_FRONTIER, L == 2, d == 64; include/spex_hip.h): Adam, the clears and the loss sum over the
+//      rows of F2 = F1 U the stored columns of F1's rows — the rows the frontier push can write — instead of the whole table.  Checked
+//      in front of frontier_step_check, like it before anything touches the device.
+static int sparse_adam_check(const spex_lightgcn_step_t *s, const char *who)
+{
+    SPEX_CHECK_ARG((s->flags & SPEX_STEP_FRONTIER) != 0, "%s: SPEX_STEP_SPARSE_ADAM needs SPEX_STEP_FRONTIER (the row list is the frontier's)", who);
+    SPEX_CHECK_ARG(s->L == 2, "%s: SPEX_STEP_SPARSE_ADAM needs L == 2 (got %d): behind a whole-graph pull the gradient is dense", who, s->L);
+    return SPEX_OK;
+}
+
+// The first launch of a flagged step: grad_E0, the frontier push's target, all-zero again — through the list the previous flagged step
+// left (SPEX_STEP_GRAD_ROWS_LISTED: nothing else wrote the table since) or, without the bit, over the whole table once.
+static int sparse_adam_begin(spex_lightgcn_step_t *s, size_t sz, void *stream)
+{
+    const bool listed = (s->flags & SPEX_STEP_GRAD_ROWS_LISTED) != 0;
+    s->flags &= ~SPEX_STEP_GRAD_ROWS_LISTED;        // (set again once every launch of the step is queued)
+    if (listed) return spex_zero_rows_f32(s->grad_E0, s->frontier_list, s->frontier_counts + 2, s->graph->n_rows, s->graph->n_rows, s->d, stream);
+    return spex::zero_f32(s->grad_E0, (int64_t)sz, stream);
+}
+
+// The row-sparse Adam pass of a flagged step over frontier_list[0 .. |F2|): g_out / 3 read and cleared below |Bset|, the batch
+// kernel's push target ws_bwd[0] cleared below |F1|, the per-sample losses summed in the dense pass's order.
+static int sparse_adam_pass(spex_lightgcn_step_t *s, int32_t t_next, int32_t n_loss, float *loss_sum, const spex::L2Rows *l2, void *stream)
+{
+    spex::AdamRowList rl;
+    rl.list = s->frontier_list;
+    rl.count = s->frontier_counts + 2;
+    rl.max_count = rl.n_rows = s->graph->n_rows;
+    rl.count_b = s->frontier_counts;
+    rl.add_g = s->g_out;
+    rl.add_div = (float)(s->L + 1);
+    rl.count_z = s->frontier_counts + 1;
+    rl.zero_buf = s->ws_bwd;
+    SPEX_TRY(spex::adam_rows(s->E0, s->grad_E0, s->m, s->v, rl, t_next, s->lr, s->beta1, s->beta2, s->eps, stream, s->grad_slots, n_loss, loss_sum, l2));
+    s->flags |= SPEX_STEP_GRAD_ROWS_LISTED;
+    return SPEX_OK;
+}
+
+// Bset, then F1 behind it, of a batch of up to three index lists into frontier_list; frontier_counts = { |Bset|, |F1| }.  two_hop
+// (SPEX_STEP_SPARSE_ADAM): F2 behind F1 by a second pass of the same kernel over [0, |F1|); frontier_counts[2] = |F2|.
 static int frontier_lists(spex_lightgcn_step_t *s, const int64_t *a, int32_t n_a, const int64_t *b, int32_t n_b, const int64_t *c, int32_t n_c,
-                          void *stream)
+                          void *stream, bool two_hop = false)
 {
     const spex_graph *g = s->graph;
     const int32_t epoch = s->frontier_epoch % 0x7FFFFFFF + 1;      // never 0
@@ -115,8 +154,10 @@ static int frontier_lists(spex_lightgcn_step_t *s, const int64_t *a, int32_t n_a
     if (c) SPEX_TRY(spex::unique_rows_more(c, n_c, n_u, nullptr, 0, 0, g->n_rows, s->frontier_stamp, epoch, s->frontier_list, s->frontier_counts, stream));
     s->frontier_epoch = epoch;      // (the stamps are on the device from here on, whatever becomes of the step)
     const int64_t slots = (int64_t)n_a + n_b + (c ? n_c : 0);
-    return spex_frontier_rows_i32(g, s->frontier_list, s->frontier_counts, (int32_t)(slots < g->n_rows ? slots : g->n_rows), s->frontier_stamp, epoch,
-                                  s->frontier_counts + 1, stream);
+    SPEX_TRY(spex_frontier_rows_i32(g, s->frontier_list, s->frontier_counts, (int32_t)(slots < g->n_rows ? slots : g->n_rows), s->frontier_stamp, epoch,
+                                    s->frontier_counts + 1, stream));
+    if (!two_hop) return SPEX_OK;
+    return spex_frontier_rows_i32(g, s->frontier_list, s->frontier_counts + 1, g->n_rows, s->frontier_stamp, epoch, s->frontier_counts + 2, stream);
 }
 
 // Forward layer L - 1 at the rows of F1: the table, and for L >= 4 the running sum, at those rows.
@@ -128,10 +169,10 @@ static int frontier_forward(const spex_lightgcn_step_t *s, const float *cur, flo
 
 // The backward product l = L - 2 from the batch kernel's push target P: W = A^T P (+ g_out / (L + 1) where the whole-graph step's
 // launch carries that term: L >= 4) as a push over the F1 list into W, zeroed here.  W = grad_E0 at L == 2, ws_bwd[1] otherwise.
-static int frontier_backward(const spex_lightgcn_step_t *s, size_t sz, const float *P, float **W_out, void *stream)
+static int frontier_backward(const spex_lightgcn_step_t *s, size_t sz, const float *P, float **W_out, void *stream, bool zeroed = false)
 {
     float *W = s->L == 2 ? s->grad_E0 : s->ws_bwd + sz;
-    SPEX_TRY(spex::zero_f32(W, (int64_t)sz, stream));
+    if (!zeroed) SPEX_TRY(spex::zero_f32(W, (int64_t)sz, stream));       // (SPEX_STEP_SPARSE_ADAM: the step's first launch has cleared it)
     SPEX_TRY(spex_spmm_push_rows_scaled_f32(s->graph, s->frontier_list, s->frontier_counts + 1, s->graph->n_rows, P, 1, s->L >= 4 ? s->g_out : nullptr,
                                             1, 1.0f, 1.0f / (float)(s->L + 1), W, s->d, stream));
     *W_out = W;
@@ -160,7 +201,8 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
                    "spex_lightgcn_step_bce_f32: edge dropout needs L >= 2 and graph_t = the transposed handle (with its edge-id permutation)");
     const bool bf16 = (s->flags & SPEX_STEP_BF16_GATHER) != 0;
     if (bf16) SPEX_TRY(bf16_step_check(s, "spex_lightgcn_step_bce_f32"));
-    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0;
+    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0, sp = (s->flags & SPEX_STEP_SPARSE_ADAM) != 0;
+    if (sp) SPEX_TRY(sparse_adam_check(s, "spex_lightgcn_step_bce_f32"));
     if (fr) SPEX_TRY(frontier_step_check(s, "spex_lightgcn_step_bce_f32"));
     const size_t sz = (size_t)g->n_rows * d;
     const bool det = (s->flags & SPEX_STEP_DETERMINISTIC) != 0;
@@ -169,7 +211,9 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
     //      ws_fwd, and the batch kernel forms the layer sum (E^0 + E^1 (+ E^2)) + y at the batch's rows — the only rows the loss
     //      reads — in the fused epilogues' order; deeper models keep the running sum fused into the launches.
     const bool plain = L >= 2 && L <= 3;
-    if (fr) SPEX_TRY(frontier_lists(s, users, B, items, B, nullptr, 0, stream));      // (the first launches: every argument check is above)
+    if (sp) SPEX_TRY(sparse_adam_begin(s, sz, stream));                // (in front of the lists: it may read the previous step's)
+    else s->flags &= ~SPEX_STEP_GRAD_ROWS_LISTED;                      // (this step writes grad_E0 wherever it likes)
+    if (fr) SPEX_TRY(frontier_lists(s, users, B, items, B, nullptr, 0, stream, sp));  // (the first launches: every argument check is above)
     const float *cur = s->E0;
     const uint16_t *cur16 = nullptr;             // SPEX_STEP_BF16_GATHER: the batch kernel's gather source, bf16(y_(L-1))
     uint16_t *shadow = bf16 ? s->E0_16 : nullptr;   // ... and the Adam pass's second output
@@ -227,8 +271,13 @@ extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t
         const float *c2 = G;
         if (bf16) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
         float *W = nullptr;
-        if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream));     // product l = L - 2 over the frontier
+        if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream, sp));     // product l = L - 2 over the frontier
         if (fr) c2 = W;
+        if (sp) {                                       // L == 2: the push has left the whole product in grad_E0, non-zero in F2 only
+            SPEX_TRY(sparse_adam_pass(s, s->t + 1, B, loss_sum, nullptr, stream));
+            s->t += 1;
+            return SPEX_OK;
+        }
         for (int32_t l = fr ? L - 3 : L - 2; !bf16 && l >= 0; --l) {
             float *nxt = l == 0 ? s->grad_E0 : s->ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;   // ws_bwd[1], [2], [1] ...: never the source, never G
             if (l == 0 || all_plain) SPEX_TRY(spex_spmm_f32(gt, c2, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
@@ -325,7 +374,8 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     SPEX_CHECK_ARG(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_rows, "%s: square graphs of one size", who);
     const bool bf16 = (s->flags & SPEX_STEP_BF16_GATHER) != 0;
     if (bf16) SPEX_TRY(bf16_step_check(s, who));
-    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0;
+    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0, sp = (s->flags & SPEX_STEP_SPARSE_ADAM) != 0;
+    if (sp) SPEX_TRY(sparse_adam_check(s, who));
     if (fr) SPEX_TRY(frontier_step_check(s, who));
     if ((s->flags & SPEX_STEP_WIDE) != 0) {
         if (d != 128 && d != 256) {
@@ -355,7 +405,16 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     l2.scale = wd / (float)T;
     l2.g_store = s->grad_E0;
     l2.shift = d == 64 ? 4 : (d == 128 ? 5 : 6);
-    if (fr) SPEX_TRY(frontier_lists(s, users, T, pos, T, neg, T, stream));             // (the first launches: every argument check is above)
+    if (sp) {
+        // (in front of the lists: the clear may read the previous step's.  The row-sparse pass does not clear the other parity's count
+        //  table row by row — the rows that hold counts there are an earlier batch's — so the step clears it whole: 4 N bytes)
+        SPEX_TRY(sparse_adam_begin(s, sz, stream));
+        SPEX_TRY(spex::zero_f32(reinterpret_cast<float *>(cnt_other), (int64_t)g->n_rows, stream));
+        l2.clear = nullptr;
+    } else {
+        s->flags &= ~SPEX_STEP_GRAD_ROWS_LISTED;                                       // (this step writes grad_E0 wherever it likes)
+    }
+    if (fr) SPEX_TRY(frontier_lists(s, users, T, pos, T, neg, T, stream, sp));         // (the first launches: every argument check is above)
     // ---- forward: layers 0 .. L-2 over the whole graph (plain for L <= 3), the last layer at the batch's rows only
     const bool plain = L >= 2 && L <= 3;
     const float *cur = s->E0;
@@ -423,8 +482,13 @@ extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const in
     const float *c2 = G;
     if (bf16) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
     float *W = nullptr;
-    if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream));     // product l = L - 2 over the frontier
+    if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream, sp));     // product l = L - 2 over the frontier
     if (fr) c2 = W;
+    if (sp) {                                           // L == 2: the push has left the whole product in grad_E0, non-zero in F2 only
+        SPEX_TRY(sparse_adam_pass(s, t_next, T, loss_sum, &l2, stream));
+        s->t = t_next;
+        return SPEX_OK;
+    }
     for (int32_t l = fr ? L - 3 : L - 2; !bf16 && l >= 0; --l) {
         float *nxt = l == 0 ? s->grad_E0 : s->ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;
         if (l == 0 || L == 3) SPEX_TRY(spex_spmm_f32(gt, c2, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));

@@ -385,8 +385,8 @@ class FrontierRows(UniqueRows):
 
     def __init__(self, n_rows, device):
         super().__init__(n_rows, n_rows, device)
-        self.counts = torch.zeros(2, dtype=torch.int32, device=device)
-        self.count, self.count_f = self.counts[0:1], self.counts[1:2]
+        self.counts = torch.zeros(4, dtype=torch.int32, device=device)       # |Bset|, |F1|, |F2| (after expand2), one spare
+        self.count, self.count_f, self.count_f2 = self.counts[0:1], self.counts[1:2], self.counts[2:3]
         self.max_b = 0
 
     def update(self, idx_a, idx_b=None, off_a=0, off_b=0):
@@ -401,6 +401,52 @@ class FrontierRows(UniqueRows):
         _launch(self.list.device, "spex_frontier_rows_i32", graph._h, _ptr(self.list), _ptr(self.count), self.max_b, _ptr(self.stamp),
                 self.epoch, _ptr(self.count_f))
         return self
+
+    def expand2(self, graph):
+        """The second hop (call once after expand): append the columns of F1's rows that the list does not hold yet.  Afterwards the
+        list is [Bset | F1 minus Bset | F2 minus F1] and `count_f2` = |F2|, F2 = F1 U the stored columns of F1's rows — at two
+        layers the rows a frontier step's gradient can touch (SPEX_STEP_SPARSE_ADAM)."""
+        if graph.n_rows != self.n_rows or graph.n_cols != self.n_rows:
+            raise ValueError(f"FrontierRows.expand2: needs a square graph of {self.n_rows} rows (got {graph.n_rows} x {graph.n_cols})")
+        _launch(self.list.device, "spex_frontier_rows_i32", graph._h, _ptr(self.list), _ptr(self.count_f), self.n_rows, _ptr(self.stamp),
+                self.epoch, _ptr(self.count_f2))
+        return self
+
+
+def _row_list(rows, count, who):
+    """(list, count cell, capacity) of a UniqueRows / FrontierRows; count: None (rows.count), or one of the object's device cells."""
+    count = rows.count if count is None else count
+    if not (count.is_cuda and count.dtype == torch.int32 and count.numel() >= 1):
+        raise ValueError(f"{who}: count must be an int32 device cell")
+    return rows.list, count, rows.capacity
+
+
+def adam_rows(p, g, m, v, rows, t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, count=None):
+    """Row-sparse ("lazy") Adam over [n_rows, 64] tables (spex_adam_rows_f32): adam_step's update, bit for bit, at the rows of the
+    device list `rows` (a UniqueRows / FrontierRows; count: the cell that holds the length, e.g. rows.count_f2) and nowhere else — p,
+    m, v of every other row are neither read nor written; t is the global step count.  torch.optim.SparseAdam's masking law with
+    torch.optim.Adam's placement of eps."""
+    for x, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+        _need(x, n)
+        if x.dim() != 2 or x.shape != p.shape or not x.is_contiguous():
+            raise ValueError(f"adam_rows: {n} must be a contiguous [n_rows, 64] table like p")
+    lst, cnt, cap = _row_list(rows, count, "adam_rows")
+    if rows.n_rows != p.shape[0]:
+        raise ValueError(f"adam_rows: the list indexes {rows.n_rows} rows, the tables have {p.shape[0]}")
+    _launch(p.device, "spex_adam_rows_f32", _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(lst), _ptr(cnt), cap, p.shape[0], p.shape[1], int(t),
+            float(lr), float(beta1), float(beta2), float(eps))
+    _bump(p, m, v)
+
+
+def zero_rows(x, rows, count=None):
+    """x[r, :] = 0 at the rows of the device list `rows` (spex_zero_rows_f32; count as in adam_rows); other rows are not written."""
+    _need(x, "x")
+    if x.dim() != 2 or not x.is_contiguous() or rows.n_rows != x.shape[0]:
+        raise ValueError("zero_rows: x must be a contiguous [n_rows, d] table of the list's height")
+    lst, cnt, cap = _row_list(rows, count, "zero_rows")
+    _launch(x.device, "spex_zero_rows_f32", _ptr(x), _ptr(lst), _ptr(cnt), cap, x.shape[0], x.shape[1])
+    _bump(x)
+    return x
 
 
 def spmm_push_rows(graph, rows, src, out, src_indexed, add=None, add_indexed=False, scale=1.0, add_scale=None, frontier=False):

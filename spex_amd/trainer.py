@@ -51,8 +51,16 @@ def _drop_desc(stepper):
 
 class LightGCNStepper:
     def __init__(self, graph, E0, n_user_rows, n_layers=3, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph_t=None, deterministic=None,
-                 weight_decay=0.0, gather_dtype=None, frontier=False):
-        """frontier=True (width 64, n_layers >= 2, fp32 tables, no edge dropout, not deterministic; ValueError otherwise): step_bce,
+                 weight_decay=0.0, gather_dtype=None, frontier=False, sparse_adam=False):
+        """sparse_adam=True (only with frontier=True and n_layers == 2; ValueError otherwise): row-sparse ("lazy") Adam for the frontier
+        steps (SPEX_STEP_SPARSE_ADAM).  The forward, the loss and the gradient are the frontier step's; E0, m and v then
+        change only at the rows of the batch's two-hop set F2 = F1 U the stored columns of F1's rows — the rows that can receive a
+        gradient at two layers — by dense Adam's own expression with the global step count; every other row stands still bit for bit
+        and does not coast on its momentum.  torch.optim.SparseAdam's masking law with torch.optim.Adam's placement of eps: its own
+        semantics, an opt-in like gather_dtype.  The Adam pass, the clears and the loss sum then cost |F2| rows, not N: pays where F2
+        is a small share of a graph that streams from HBM, loses on small graphs.  `stepper.sparse_adam` may be switched off and on
+        between steps; while `frontier` is switched off it is ignored (the whole-graph steps run dense Adam).
+        frontier=True (width 64, n_layers >= 2, fp32 tables, no edge dropout, not deterministic; ValueError otherwise): step_bce,
         step_bpr_exact, the native epochs and the sampled epochs take one more level inward (SPEX_STEP_FRONTIER) —
         forward layer L - 1 only at the batch's frontier F1 (its rows and their stored columns), the backward product behind the
         batch kernel's push as a push over the same list; at n_layers 2 no whole-graph launch is left in the step.  Exact semantics
@@ -110,6 +118,12 @@ class LightGCNStepper:
         self._shadow_current = False  # E0_16 == bf16(E0) (kept so by the bf16 one-call step's Adam pass; every other writer of E0 clears it)
         self._frontier = False
         self._front = None            # the batch's frontier list (ops.FrontierRows): list, counts and stamp table of both step forms
+        self._sparse_adam = False
+        self._grad_listed = False     # grad_E0 is zero outside the frontier list's F2 (SPEX_STEP_GRAD_ROWS_LISTED) ...
+        self._grad_ver = self._list_ver = -1      # ... as long as nobody has written grad_E0 or the list since (torch's version counters)
+        if sparse_adam and not (frontier and self.L == 2):
+            raise ValueError(f"LightGCNStepper(sparse_adam=True): only with frontier=True and n_layers == 2 (got frontier={bool(frontier)}, "
+                             f"n_layers {self.L}): behind a whole-graph launch the gradient is dense")
         if frontier:
             if self.deterministic:
                 raise ValueError("LightGCNStepper(frontier=True): not with deterministic=True — the frontier push adds with float atomics")
@@ -121,6 +135,7 @@ class LightGCNStepper:
             self._front = ops.FrontierRows(n, dev)
             self.frontier = True
             self._refuse_frontier_dropout("LightGCNStepper(frontier=True)")
+            self.sparse_adam = bool(sparse_adam)
         self.t = 0
 
     @property
@@ -135,6 +150,31 @@ class LightGCNStepper:
             raise ValueError("LightGCNStepper.frontier = True: only on a stepper built with frontier=True (it owns the frontier list and "
                              "has passed the form's checks)")
         self._frontier = bool(on)
+
+    @property
+    def sparse_adam(self):
+        """Whether the frontier steps run row-sparse Adam (see __init__).  May be switched off and on between steps on a stepper built
+        with frontier=True and n_layers == 2; ignored while `frontier` is off."""
+        return self._sparse_adam
+
+    @sparse_adam.setter
+    def sparse_adam(self, on):
+        if on and (self._front is None or self.L != 2):
+            raise ValueError("LightGCNStepper.sparse_adam = True: only on a stepper built with frontier=True and n_layers == 2")
+        self._sparse_adam = bool(on)
+
+    def _sparse(self):
+        return self._sparse_adam and self._frontier
+
+    def _listed_ok(self):
+        """grad_E0 is zero outside frontier_list[0 : |F2|): a sparse-Adam step said so and nothing has written either tensor since."""
+        return (self._grad_listed and self._front is not None and self.grad_E0._version == self._grad_ver
+                and self._front.list._version == self._list_ver)
+
+    def _mark_listed(self, on=True):
+        self._grad_listed = bool(on)
+        if on:
+            self._grad_ver, self._list_ver = self.grad_E0._version, self._front.list._version
 
     def _refuse_frontier_dropout(self, who, keep_prob=1.0):
         if self.frontier and (keep_prob < 1.0 or getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0):
@@ -156,6 +196,7 @@ class LightGCNStepper:
 
     def _propagate_bwd(self):
         """grad_E0 from the dense g_out, all in pull form (with gather_dtype: the straight-through bf16 backward)."""
+        self._grad_listed = False
         if self.gather_dtype is not None:
             return self.graph_t.propagate_bwd(self.g_out, self.L, grad_E0=self.grad_E0, ws=self.ws16, gather_dtype=self.gather_dtype)
         return self.graph_t.propagate_bwd(self.g_out, self.L, grad_E0=self.grad_E0, ws=self.ws_bwd)
@@ -221,13 +262,15 @@ class LightGCNStepper:
         return None if loss_acc is not None else loss_sum / B
 
     # -- frontier=True, launch by launch: the statement the one-call frontier step is checked against
-    def _frontier_forward(self, idx_a, idx_b):
+    def _frontier_forward(self, idx_a, idx_b, two_hop=False):
         """Layers 1 .. L-2 over the whole graph, layer L-1 at the rows of F1 (table and running sum), layer L at the batch's rows
         (idx_a, idx_b + n_user_rows) into lo_batch.  Returns lo_batch, valid at the batch's rows."""
         if not all(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() for t in (idx_a, idx_b)):
             raise ValueError("LightGCNStepper(frontier=True): the batch must be contiguous int64 tensors on the GPU")
         L, g, lo = self.L, self.graph, self.light_out
         fr = self._front.update(idx_a, idx_b, 0, self.n_u).expand(g)
+        if two_hop:                   # (sparse_adam: F2 behind F1, the rows the Adam pass takes)
+            fr.expand2(g)
         cur = self.E0
         for l in range(L - 1):
             nxt = self.ws_fwd[l & 1]
@@ -242,13 +285,16 @@ class LightGCNStepper:
         g.spmm_rows(cur, idx_a, idx_b, 0, self.n_u, acc_in=lo, acc_out=self.lo_batch, acc_div=float(L + 1))
         return self.lo_batch
 
-    def _frontier_backward(self):
+    def _frontier_backward(self, zeroed=False):
         """grad_E0 from G_{L-1} in ws_bwd[0] (support in F1) and the dense g_out: G_{L-2} = g/(L+1) + A^T G_{L-1} as a push over the
-        F1 list into a zeroed table (grad_E0 itself at L == 2), the remaining L - 2 products whole-graph pulls over A^T."""
+        F1 list into a zeroed table (grad_E0 itself at L == 2), the remaining L - 2 products whole-graph pulls over A^T.
+        zeroed (sparse_adam, L == 2): _sparse_begin has cleared the table."""
         L, gt = self.L, self.graph_t
         inv = 1.0 / float(L + 1)
         W = self.grad_E0 if L == 2 else self.ws_bwd[1]
-        W.zero_()
+        if not zeroed:
+            self._grad_listed = False
+            W.zero_()
         ops.spmm_push_rows(self.graph, self._front, self.ws_bwd[0], W, True, add=self.g_out, add_indexed=True, scale=1.0, add_scale=inv,
                            frontier=True)
         cur = W
@@ -257,8 +303,29 @@ class LightGCNStepper:
             gt.spmm(cur, Y=nxt, add_in=self.g_out, add_div=float(L + 1))
             cur = nxt
 
+    def _sparse_begin(self):
+        """sparse_adam, first thing in a step (before the lists are rebuilt): grad_E0 all-zero again — through the list the last
+        sparse-Adam step left where that still describes it, over the whole table otherwise."""
+        if self._listed_ok():
+            ops.zero_rows(self.grad_E0, self._front, self._front.count_f2)
+        else:
+            self.grad_E0.zero_()
+        self._grad_listed = False
+
+    def _sparse_adam_rows(self):
+        """sparse_adam, last thing in a launch-by-launch step: Adam over the F2 list (grad_E0 holds the whole gradient, zero outside
+        F2), g_out cleared at the batch's rows — the only ones written."""
+        ops.adam_rows(self.E0, self.grad_E0, self.m, self.v, self._front, self.t, self.lr, self.betas[0], self.betas[1], self.eps,
+                      count=self._front.count_f2)
+        ops.zero_rows(self.g_out, self._front)
+        self._shadow_current = False
+        self._mark_listed()
+
     def _step_bce_frontier(self, users, items, labels, loss_acc):
-        lo = self._frontier_forward(users, items)
+        sp = self._sparse()
+        if sp:
+            self._sparse_begin()
+        lo = self._frontier_forward(users, items, sp)
         B = users.numel()
         self._slots(B)
         _, loss_sum = ops.score_bce(lo[:self.n_u], lo[self.n_u:], users, items, labels, self.g_out[:self.n_u], self.g_out[self.n_u:],
@@ -267,16 +334,22 @@ class LightGCNStepper:
         G = self.ws_bwd[0]
         G.zero_()
         ops.spmm_push_batch(self.graph, users, items, self.n_u, self.grad_slots, G, add=self.grad_slots, scale=1.0 / float(self.L + 1))
-        self._frontier_backward()
+        self._frontier_backward(sp)
         self._clear_row_counts()
         self.t += 1
-        ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps, zero=self.g_out)
+        if sp:
+            self._sparse_adam_rows()
+        else:
+            ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps, zero=self.g_out)
         return None if loss_acc is not None else loss_sum / B
 
     def _step_bpr_frontier(self, users, pos, neg, loss_acc):
         T = users.numel()
         items = torch.cat([pos, neg])
-        lo = self._frontier_forward(users, items)
+        sp = self._sparse()
+        if sp:
+            self._sparse_begin()
+        lo = self._frontier_forward(users, items, sp)
         loss_sum = ops.bpr_loss_grad(lo[:self.n_u], lo[self.n_u:], users, pos, neg, self.g_out[:self.n_u], self.g_out[self.n_u:], 1.0 / T)
         self._ws0_clean = False
         self._clear_row_counts()
@@ -284,14 +357,17 @@ class LightGCNStepper:
         G.zero_()
         # G_{L-1} = (g + A^T g) / (L + 1), pushed from the dense g_out over the Bset part of the list
         ops.spmm_push_rows(self.graph, self._front, self.g_out, G, True, add=self.g_out, add_indexed=True, scale=1.0 / float(self.L + 1))
-        self._frontier_backward()
+        self._frontier_backward(sp)
         if self.weight_decay > 0:
             rows = torch.cat([users, items + self.n_u])
             count = torch.bincount(rows, minlength=self.E0.shape[0]).to(torch.float32)
             self.grad_E0.add_(self.E0 * (count * (self.weight_decay / T)).unsqueeze(1))
             loss_sum = loss_sum + (0.5 * self.weight_decay) * (self.E0[rows] ** 2).sum()
         self.t += 1
-        ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps, zero=self.g_out)
+        if sp:
+            self._sparse_adam_rows()
+        else:
+            ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps, zero=self.g_out)
         if loss_acc is not None:
             loss_acc += loss_sum
             return None
@@ -370,13 +446,20 @@ class LightGCNStepper:
                                  "takes the push form at any T")
             d.flags |= _lib.STEP_FRONTIER
             d.frontier_epoch = self._front.epoch        # one stamp table for both step forms: one epoch counter
+            if self._sparse():
+                d.flags |= _lib.STEP_SPARSE_ADAM
+                if self._listed_ok():                   # the first launch then clears grad_E0 through the list, not whole
+                    d.flags |= _lib.STEP_GRAD_ROWS_LISTED
         d.weight_decay = self.weight_decay
         d.row_counts = None if self.row_counts is None else self.row_counts.data_ptr()
         return d
 
     def _after_desc(self, d):
+        """After a native call and its _bump: what the call wrote back into the descriptor."""
         if self.frontier and d is self._desc:
             self._front.epoch = d.frontier_epoch
+        # (a sparse-Adam step leaves the bit set, every other step of these entry points clears it)
+        self._mark_listed(self._front is not None and (d.flags & _lib.STEP_GRAD_ROWS_LISTED) != 0)
 
     def _step_bce_one_call(self, users, items, labels, loss_acc):
         B = users.numel()
@@ -385,8 +468,8 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_step_bce_f32", ctypes.byref(d), ctypes.c_void_p(users.data_ptr()),
                 ctypes.c_void_p(items.data_ptr()), ctypes.c_void_p(labels.data_ptr()), B, ctypes.c_void_p(loss_acc.data_ptr()))
         self.t = d.t
-        self._after_desc(d)
         _bump(self.E0, self.m, self.v, loss_acc, self.E0_16)
+        self._after_desc(d)
         return None
 
     def epoch_bce(self, users, items, labels, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
@@ -405,8 +488,8 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bce_f32", ctypes.byref(d), vp(users), vp(items), vp(labels), users.numel(), int(batch_size),
                 -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
         self.t = d.t
-        self._after_desc(d)
         _bump(self.E0, self.m, self.v, loss_full, loss_ragged, self.E0_16)
+        self._after_desc(d)
 
     def backward_from_batch_rows(self, users, items):
         """grad_E0 from g_out (non-zero on the batch's rows only).  The first product of the backward pass, A^T g, touches
@@ -416,6 +499,7 @@ class LightGCNStepper:
         handle, L < 2)."""
         L, gt = self.L, self.graph_t
         self._ws0_clean = False
+        self._grad_listed = False
         if L < 2 or not self._wide_ok or getattr(gt, "mask_mode", 0) != 0 or getattr(self.graph, "mask_mode", 0) != 0:
             gt.propagate_bwd(self.g_out, L, grad_E0=self.grad_E0, ws=self.ws_bwd)
             return
@@ -515,8 +599,8 @@ class LightGCNStepper:
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         _launch(self.E0.device, "spex_lightgcn_step_bpr_adam_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), T, vp(loss_acc))
         self.t = d.t
-        self._after_desc(d)
         _bump(self.E0, self.m, self.v, self.grad_E0, loss_acc, self.E0_16)
+        self._after_desc(d)
         return None
 
     def epoch_bpr(self, users, pos, neg, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
@@ -532,8 +616,8 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bpr_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), users.numel(), int(batch_size),
                 -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
         self.t = d.t
-        self._after_desc(d)
         _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged, self.E0_16)
+        self._after_desc(d)
 
     # -- sampled epochs: the triples drawn on the device by the same native call that trains on them
     def _one_call_bpr_shape_ok(self):
@@ -565,8 +649,8 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bpr_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
                 int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
         self.t = d.t
-        self._after_desc(d)
         _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged, self.E0_16, *sampler.epoch_buffers())
+        self._after_desc(d)
 
     def train_bpr_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
         """n_epochs sampled epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
@@ -582,8 +666,8 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_train_bpr_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
                 *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
         self.t = d.t
-        self._after_desc(d)
         _bump(self.E0, self.m, self.v, self.grad_E0, loss_epochs, self.E0_16, *sampler.epoch_buffers())
+        self._after_desc(d)
 
     # -- sampled BCE epochs: negatives, labels and the shuffle drawn on the device by the same native call that trains on them
     def _one_call_bce_shape_ok(self):
@@ -616,8 +700,8 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_epoch_bce_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
                 int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
         self.t = d.t
-        self._after_desc(d)
         _bump(self.E0, self.m, self.v, loss_full, loss_ragged, self.E0_16, *sampler.epoch_buffers())
+        self._after_desc(d)
 
     def train_bce_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
         """n_epochs sampled BCE epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
@@ -634,8 +718,8 @@ class LightGCNStepper:
         _launch(self.E0.device, "spex_lightgcn_train_bce_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
                 *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
         self.t = d.t
-        self._after_desc(d)
         _bump(self.E0, self.m, self.v, loss_epochs, self.E0_16, *sampler.epoch_buffers())
+        self._after_desc(d)
 
 
 def dataloader_epoch_order(n):
