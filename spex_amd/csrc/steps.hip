@@ -5,6 +5,15 @@
 // became host-bound once the row-sparse backward had shortened the kernels.  These entry points take the step's buffers
 // in a plain-C descriptor and issue the same launches back to back (~1 us each), so the loop is GPU-bound again.
 // Nothing here computes: every launch is one of the library's own entry points.
+//
+// The BCE and the exact BPR LightGCN steps are ONE schedule, lightgcn_step, built from named pieces: step_check, the optional
+// sparse-Adam clear and frontier lists, step_forward, the kind's batch launch (bce_batch / bpr_batch), the backward behind it
+// (bf16_backward_push, frontier_backward, step_backward_pulls) and one closing Adam launch.  What the kinds do NOT share, and the
+// schedule keeps: BCE at L == 1 scores through spex_spmm_rowlist_f32 + spex_score_bce_slots_f32 and one pull product, BPR at L == 1
+// runs the push form with the push target as the gradient; the deterministic BCE step reduces its slots in one call, the BPR step in
+// two; only BPR has the dense form (from kBprStepDenseMinTriples* triples, never under SPEX_STEP_FRONTIER) and the L2 count tables;
+// the dense d loss / d light_out is not formed at L == 3 (both kinds) and at BPR's L == 1.  The dual-task step's rec branch calls
+// forward_layers and step_backward_pulls too.  Every native epoch is epoch_loop around its step.
 #include <mutex>
 
 #include "spex_common.h"
@@ -179,128 +188,202 @@ static int frontier_backward(const spex_lightgcn_step_t *s, size_t sz, const flo
     return SPEX_OK;
 }
 
-extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t *users, const int64_t *items,
-                                          const float *labels, int32_t B, float *loss_sum, void *stream)
+// ---- The one LightGCN step schedule.  spex_lightgcn_step_bce_f32 and spex_lightgcn_step_bpr_adam_f32 are lightgcn_step (below, behind
+//      the BPR step's own notes) on a StepBatch: what differs between a batch of B labelled samples and a batch of T triples.
+struct StepBatch {
+    const char *who;                    // the entry point, for messages
+    const int64_t *a, *b, *c;           // BCE: users, items, NULL; BPR: users, pos, neg
+    const float *labels;                // BCE only
+    int32_t n;                          // B samples / T triples
+    int32_t rows;                       // table rows per sample: 2 (BCE) or 3 (BPR)
+    float *loss_sum;
+};
+
+// Everything a descriptor and a batch must satisfy, checked before anything touches the device.  Shared rules in one place; slot
+// capacity (2 B / 3 T), row_counts, weight_decay and the width rule — the BPR step takes d = 128 / 256 only from a descriptor that says
+// SPEX_STEP_WIDE, the BCE step takes them without the flag — per kind.
+static int step_check(const spex_lightgcn_step_t *s, const StepBatch &k)
 {
+    const char *who = k.who;
+    const bool bpr = k.rows == 3;
     SPEX_CHECK_ARG(s && s->graph && s->graph_t && s->E0 && s->m && s->v && s->light_out && s->ws_fwd && s->lo_batch && s->g_out
-                       && s->ws_bwd && s->grad_E0 && s->grad_slots,
-                   "spex_lightgcn_step_bce_f32: NULL field in the step descriptor");
-    SPEX_CHECK_ARG(users && items && labels && loss_sum && B >= 1, "spex_lightgcn_step_bce_f32: NULL batch pointer or B < 1");
+                       && s->ws_bwd && s->grad_E0 && s->grad_slots && (!bpr || s->row_counts),
+                   "%s: NULL field in the step descriptor%s", who, bpr ? " (row_counts included)" : "");
+    SPEX_CHECK_ARG(k.a && k.b && (bpr ? k.c != nullptr : k.labels != nullptr) && k.loss_sum && k.n >= 1, "%s: NULL batch pointer or %s < 1", who,
+                   bpr ? "T" : "B");
     const spex_graph *g = s->graph, *gt = s->graph_t;
     const int32_t L = s->L, d = s->d, n_u = s->n_user_rows;
-    SPEX_CHECK_ARG(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_rows, "spex_lightgcn_step_bce_f32: square graphs of one size");
-    SPEX_CHECK_ARG(L >= 1 && (d == 64 || d == 128 || d == 256) && n_u >= 0 && n_u <= g->n_rows,
-                   "spex_lightgcn_step_bce_f32: L=%d d=%d n_user_rows=%d (needs L >= 1 and d = 64, 128 or 256)", L, d, n_u);
-    SPEX_CHECK_ARG(s->slot_capacity >= 2 * B, "spex_lightgcn_step_bce_f32: slot capacity %d < 2 B = %d", s->slot_capacity, 2 * B);
+    SPEX_CHECK_ARG(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_rows, "%s: square graphs of one size", who);
+    if ((s->flags & SPEX_STEP_BF16_GATHER) != 0) SPEX_TRY(bf16_step_check(s, who));
+    if ((s->flags & SPEX_STEP_SPARSE_ADAM) != 0) SPEX_TRY(sparse_adam_check(s, who));
+    if ((s->flags & SPEX_STEP_FRONTIER) != 0) SPEX_TRY(frontier_step_check(s, who));
+    if (!bpr) {
+        SPEX_CHECK_ARG(L >= 1 && (d == 64 || d == 128 || d == 256) && n_u >= 0 && n_u <= g->n_rows,
+                       "%s: L=%d d=%d n_user_rows=%d (needs L >= 1 and d = 64, 128 or 256)", who, L, d, n_u);
+    } else {
+        if ((s->flags & SPEX_STEP_WIDE) != 0) {
+            if (d != 128 && d != 256) {
+                spex::set_error("%s: SPEX_STEP_WIDE takes d = 128 or 256 (got %d); d == 64 runs without the flag — the widths are 64, 128 and 256", who, d);
+                return SPEX_ERR_UNSUPPORTED;
+            }
+        } else if (d != 64) {
+            spex::set_error("%s: d == 64 only (got %d); d = 128 / 256 take the launch-by-launch form", who, d);
+            return SPEX_ERR_UNSUPPORTED;
+        }
+        SPEX_CHECK_ARG(L >= 1 && n_u >= 0 && n_u <= g->n_rows, "%s: L=%d n_user_rows=%d (needs L >= 1)", who, L, n_u);
+    }
+    SPEX_CHECK_ARG(k.n <= INT32_MAX / k.rows && s->slot_capacity >= k.rows * k.n, "%s: slot capacity %d < %d %s = %lld", who, s->slot_capacity,
+                   k.rows, bpr ? "T" : "B", (long long)k.rows * k.n);
+    if (bpr) SPEX_CHECK_ARG(s->weight_decay >= 0.0f, "%s: weight_decay %g", who, (double)s->weight_decay);
     // edge dropout (model.py:46-55; set per step on BOTH handles with spex_graph_set_edge_mask — graph_t must then be the transposed
     // handle carrying the edge-id permutation, a masked adjacency is not symmetric): every product of the step uses the handles'
     // mask — the whole-graph launches through spex_spmm_f32, the batch kernel's last layer and push through the same keep rule.
     SPEX_CHECK_ARG(g->mask_mode == gt->mask_mode && (g->mask_mode == 0 || (g->keep_prob == gt->keep_prob && g->seed == gt->seed && g->keep == gt->keep)),
-                   "spex_lightgcn_step_bce_f32: graph and graph_t must carry the same edge-dropout mask");
+                   "%s: graph and graph_t must carry the same edge-dropout mask", who);
     SPEX_CHECK_ARG(g->mask_mode == 0 || (gt != g && L >= 2),
-                   "spex_lightgcn_step_bce_f32: edge dropout needs L >= 2 and graph_t = the transposed handle (with its edge-id permutation)");
-    const bool bf16 = (s->flags & SPEX_STEP_BF16_GATHER) != 0;
-    if (bf16) SPEX_TRY(bf16_step_check(s, "spex_lightgcn_step_bce_f32"));
-    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0, sp = (s->flags & SPEX_STEP_SPARSE_ADAM) != 0;
-    if (sp) SPEX_TRY(sparse_adam_check(s, "spex_lightgcn_step_bce_f32"));
-    if (fr) SPEX_TRY(frontier_step_check(s, "spex_lightgcn_step_bce_f32"));
-    const size_t sz = (size_t)g->n_rows * d;
-    const bool det = (s->flags & SPEX_STEP_DETERMINISTIC) != 0;
-    // ---- forward: layers 0 .. L-2 over the whole graph; the last layer is taken at the batch's rows only.  For L <= 3 the whole-graph
-    //      launches run in the PLAIN form (no epilogue operand, one output stream: 12.3 vs 14.8 us on Epinion2) into the two halves of
-    //      ws_fwd, and the batch kernel forms the layer sum (E^0 + E^1 (+ E^2)) + y at the batch's rows — the only rows the loss
-    //      reads — in the fused epilogues' order; deeper models keep the running sum fused into the launches.
-    const bool plain = L >= 2 && L <= 3;
-    if (sp) SPEX_TRY(sparse_adam_begin(s, sz, stream));                // (in front of the lists: it may read the previous step's)
-    else s->flags &= ~SPEX_STEP_GRAD_ROWS_LISTED;                      // (this step writes grad_E0 wherever it likes)
-    if (fr) SPEX_TRY(frontier_lists(s, users, B, items, B, nullptr, 0, stream, sp));  // (the first launches: every argument check is above)
-    const float *cur = s->E0;
-    const uint16_t *cur16 = nullptr;             // SPEX_STEP_BF16_GATHER: the batch kernel's gather source, bf16(y_(L-1))
-    uint16_t *shadow = bf16 ? s->E0_16 : nullptr;   // ... and the Adam pass's second output
-    if (bf16) SPEX_TRY(bf16_forward(s, sz, &cur16, stream));
-    for (int32_t l = 0; !bf16 && l + 1 < L; ++l) {
-        float *nxt = s->ws_fwd + (size_t)(l & 1) * sz;
-        if (fr && l + 2 == L) SPEX_TRY(frontier_forward(s, cur, nxt, plain, stream));
-        else if (plain) SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
-        else SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, l == 0 ? s->E0 : s->light_out, s->light_out, 1.0f, d, stream));
-        cur = nxt;
-    }
-    // the tables whose rows the batch kernel adds in front of the last layer's product: E^0 (+ E^1 + E^2), or the running sum
-    const float *sum0 = plain || L == 1 ? s->E0 : s->light_out;
-    const float *sum1 = plain ? s->ws_fwd : nullptr, *sum2 = plain && L == 3 ? s->ws_fwd + sz : nullptr;
-    if (det) {
-        // ---- SPEX_STEP_DETERMINISTIC: the same forward (same kernel code for the batch's rows: bit-identical scores), but every sum
-        //      that the fast path leaves to float atomics is taken in a fixed order — the sample's two gradient rows leave as
-        //      per-sample slots, are added per table row in ascending slot order (what the reference's CPU index backward does,
-        //      model.py:115-116), and the whole backward runs in pull form (each output row one chain in ascending column order,
-        //      like the reference's sparse addmm).  Per-sample losses: head of lo_batch, summed in order by the Adam pass.
-        float *loss_rows = s->lo_batch;
-        if (bf16)
-            SPEX_TRY(spex::lightgcn_batch_slots_bf16_layers(g, cur16, sum0, sum1, sum2, (float)(L + 1), users, items, labels, B, n_u,
-                                                            1.0f / (float)B, nullptr, loss_rows, s->grad_slots, d, stream));
-        else
-            SPEX_TRY(spex::lightgcn_batch_slots_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, items, labels, B, n_u,
-                                                       1.0f / (float)B, nullptr, loss_rows, s->grad_slots, d, stream));
-        SPEX_TRY(spex_reduce_slots_f32(users, B, 0, items, B, n_u, g->n_rows, s->grad_slots, d, 1.0f, s->g_out, 0, d, stream));
-        if (bf16) SPEX_TRY(spex_propagate_bwd_bf16_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, s->ws16, L, d, stream));
-        else SPEX_TRY(spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream));
-        SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, s->t + 1, s->lr, s->beta1, s->beta2, s->eps, s->g_out,
-                                    s->ws_bwd /* keeps the fast path's push target all-zero */, stream, loss_rows, B, loss_sum, nullptr,
-                                    nullptr, 1.0f, nullptr, shadow));
-        s->t += 1;
-        return SPEX_OK;
-    }
-    if (L >= 2) {
-        // ---- the batch-sized middle as one launch: last layer + layer mean at the batch's rows, scores + BCE, gradient rows, and the
-        //      first backward product G_{L-1} = (g + A^T g) / (L+1) in push form — over the rows of A itself: (A^T g)[c] = sum_r
-        //      A[r, c] g[r] — (g_out and G are all-zero here: the Adam pass below clears them for the next step; first call: the caller)
-        float *G = s->ws_bwd;
-        const bool all_plain = L == 3;              // (see below: nothing reads the dense d loss / d light_out then — it is not formed)
-        if (bf16)
-            SPEX_TRY(spex::lightgcn_batch_bf16_layers(g, cur16, sum0, sum1, sum2, (float)(L + 1), users, items, labels, B, n_u, 1.0f / (float)B,
-                                                      1.0f / (float)(L + 1), nullptr, s->grad_slots, all_plain ? nullptr : s->g_out, G, d, stream));
-        else
-            SPEX_TRY(spex::lightgcn_batch_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, items, labels, B, n_u, 1.0f / (float)B,
-                                                 1.0f / (float)(L + 1), nullptr, s->grad_slots /* per-sample losses, summed by the Adam pass */,
-                                                 all_plain ? nullptr : s->g_out, G, d, stream));
-        // ---- L-1 pull-form products G_l = g / (L+1) + A^T G_{l+1}.  The last one (l = 0) runs in the PLAIN form: its g / (L+1) term
-        //      is added by the Adam pass, which reads g_out anyway to clear it (one epilogue stream less on a 15 us launch).
-        //      L == 3 (the reference's depth): BOTH run plain.  With P = G_2 = (g + A^T g) / 4 the gradient is
-        //      A^T (A^T P + g/4) + g/4 = A^T (A^T P) + (A^T g / 4 + g / 4) = A^T (A^T P) + P — and P is the push target, which the
-        //      Adam pass touches anyway (to clear it): it adds P instead of g / 4.  No epilogue operand left in the backward.
-        const float *c2 = G;
-        if (bf16) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
-        float *W = nullptr;
-        if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream, sp));     // product l = L - 2 over the frontier
-        if (fr) c2 = W;
-        if (sp) {                                       // L == 2: the push has left the whole product in grad_E0, non-zero in F2 only
-            SPEX_TRY(sparse_adam_pass(s, s->t + 1, B, loss_sum, nullptr, stream));
-            s->t += 1;
-            return SPEX_OK;
-        }
-        for (int32_t l = fr ? L - 3 : L - 2; !bf16 && l >= 0; --l) {
-            float *nxt = l == 0 ? s->grad_E0 : s->ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;   // ws_bwd[1], [2], [1] ...: never the source, never G
-            if (l == 0 || all_plain) SPEX_TRY(spex_spmm_f32(gt, c2, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
-            else SPEX_TRY(spex_spmm_f32(gt, c2, nxt, s->g_out, (float)(L + 1), nullptr, nullptr, 1.0f, d, stream));
-            c2 = nxt;
-        }
-        SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, s->t + 1, s->lr, s->beta1, s->beta2, s->eps,
-                                    all_plain ? nullptr : s->g_out /* untouched (all-zero) in the all-plain step */, s->ws_bwd, stream,
-                                    s->grad_slots, B, loss_sum, nullptr, all_plain ? G : s->g_out, all_plain ? 1.0f : (float)(L + 1), nullptr,
-                                    shadow));
-        s->t += 1;
-        return SPEX_OK;
-    } else {    // L == 1: the last layer at the batch's rows, scoring, then grad = (g + A^T g) / 2 as one pull-form product
-        SPEX_TRY(spex_spmm_rowlist_f32(g, cur, users, B, 0, items, B, n_u, nullptr, s->E0, s->lo_batch, (float)(L + 1), d, stream));
-        SPEX_TRY(spex_score_bce_slots_f32(s->lo_batch, s->lo_batch + (size_t)n_u * d, d, d, n_u, g->n_rows - n_u, users, items, labels, B, d,
-                                          loss_sum, s->g_out, s->g_out + (size_t)n_u * d, 1.0f / (float)B, s->grad_slots, d, stream));
-        SPEX_TRY(spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream));
-    }
-    // ---- Adam over the whole table (also clears g_out for the next step); t is advanced only once every launch is queued
-    SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, s->t + 1, s->lr, s->beta1, s->beta2, s->eps, s->g_out,
-                                L >= 2 ? s->ws_bwd : nullptr, stream, L >= 2 ? s->grad_slots : nullptr, B, loss_sum));
-    s->t += 1;
+                   "%s: edge dropout needs L >= 2 and graph_t = the transposed handle (with its edge-id permutation)", who);
     return SPEX_OK;
+}
+
+// The first `count` whole-graph forward launches y_(l+1) = A y_l of an L-layer model, into ws_fwd[l & 1]; *cur = the last table written
+// (E0 for count == 0).  For L <= 3 the launches run in the PLAIN form (no epilogue operand, one output stream: 12.3 vs 14.8 us on
+// Epinion2) and the batch kernel forms the layer sum (E^0 + E^1 (+ E^2)) + y at the batch's rows — the only rows the loss reads — in
+// the fused epilogues' order; deeper models keep the running sum fused into the launches (`light`).
+static int forward_layers(const spex_graph *g, const float *E0, float *light, float *ws_fwd, int32_t L, int32_t count, int32_t d, void *stream,
+                          const float **cur)
+{
+    const size_t sz = (size_t)g->n_rows * d;
+    const bool plain = L >= 2 && L <= 3;
+    *cur = E0;
+    for (int32_t l = 0; l < count; ++l) {
+        float *nxt = ws_fwd + (size_t)(l & 1) * sz;
+        if (plain) SPEX_TRY(spex_spmm_f32(g, *cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
+        else SPEX_TRY(spex_spmm_f32(g, *cur, nxt, nullptr, 1.0f, l == 0 ? E0 : light, light, 1.0f, d, stream));
+        *cur = nxt;
+    }
+    return SPEX_OK;
+}
+
+struct StepTables {                     // what the forward leaves for the batch launch
+    const float *cur = nullptr;         // y_(L-1), its gather source ...
+    const uint16_t *cur16 = nullptr;    // ... or, SPEX_STEP_BF16_GATHER, bf16(y_(L-1))
+    const float *sum0 = nullptr, *sum1 = nullptr, *sum2 = nullptr;      // the tables whose rows it adds in front of the last layer's
+};                                                                      // product: E^0 (+ E^1 + E^2), or the running sum
+
+// Forward layers 0 .. L-2: from the bf16 shadow, or in fp32 over the whole graph — under SPEX_STEP_FRONTIER the last of them at the rows
+// of F1 only.  The last layer is left to the batch launch, at the batch's rows.
+static int step_forward(const spex_lightgcn_step_t *s, size_t sz, void *stream, StepTables *f)
+{
+    const int32_t L = s->L;
+    const bool plain = L >= 2 && L <= 3, fr = (s->flags & SPEX_STEP_FRONTIER) != 0;
+    f->cur = s->E0;
+    if ((s->flags & SPEX_STEP_BF16_GATHER) != 0) {
+        SPEX_TRY(bf16_forward(s, sz, &f->cur16, stream));
+    } else {
+        SPEX_TRY(forward_layers(s->graph, s->E0, s->light_out, s->ws_fwd, L, fr ? L - 2 : L - 1, s->d, stream, &f->cur));
+        if (fr) {
+            float *nxt = s->ws_fwd + (size_t)(L & 1) * sz;
+            SPEX_TRY(frontier_forward(s, f->cur, nxt, plain, stream));
+            f->cur = nxt;
+        }
+    }
+    f->sum0 = plain || L == 1 ? s->E0 : s->light_out;
+    f->sum1 = plain ? s->ws_fwd : nullptr;
+    f->sum2 = plain && L == 3 ? s->ws_fwd + sz : nullptr;
+    return SPEX_OK;
+}
+
+// The pull-form products G_l = g / (L+1) + A^T G_(l+1), l = l_first .. 0, from src = G_(l_first + 1), through ws_bwd[1], [2], [1] ...
+// (never the source, never the push target ws_bwd[0]) into grad.  The last one (l = 0) runs in the PLAIN form: its g / (L+1) term is
+// added by the Adam pass, which reads g anyway to clear it (one epilogue stream less on a 15 us launch).  L == 3 (the reference's
+// depth): BOTH run plain.  With P = G_2 = (g + A^T g) / 4 the gradient is A^T (A^T P + g/4) + g/4 = A^T (A^T P) + (A^T g / 4 + g / 4)
+// = A^T (A^T P) + P — and P is the push target, which the Adam pass touches anyway (to clear it): it adds P instead of g / 4.  No
+// epilogue operand left in the backward.
+static int step_backward_pulls(const spex_graph *gt, const float *src, int32_t l_first, const float *g_dense, float *ws_bwd, float *grad, int32_t L,
+                               int32_t d, void *stream)
+{
+    const size_t sz = (size_t)gt->n_rows * d;
+    for (int32_t l = l_first; l >= 0; --l) {
+        float *nxt = l == 0 ? grad : ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;
+        if (l == 0 || L == 3) SPEX_TRY(spex_spmm_f32(gt, src, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
+        else SPEX_TRY(spex_spmm_f32(gt, src, nxt, g_dense, (float)(L + 1), nullptr, nullptr, 1.0f, d, stream));
+        src = nxt;
+    }
+    return SPEX_OK;
+}
+
+// The batch launch of either kind in its forms, from the fp32 or the bf16 table: slots given — per-sample gradient rows, nothing added
+// anywhere (SPEX_STEP_DETERMINISTIC); otherwise atomics into `dense` (NULL: not formed) and, G given, the first backward product
+// (g + A^T g) * push_scale in push form into G.
+static int bce_batch(const spex_lightgcn_step_t *s, const StepBatch &k, const StepTables &f, float push_scale, float *loss_rows, float *slots,
+                     float *dense, float *G, void *stream)
+{
+    const spex_graph *g = s->graph;
+    const int32_t n_u = s->n_user_rows, d = s->d;
+    const float n_sum = (float)(s->L + 1), scale = 1.0f / (float)k.n;
+    if (slots)
+        return f.cur16 ? spex::lightgcn_batch_slots_bf16_layers(g, f.cur16, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.labels, k.n, n_u, scale, nullptr,
+                                                                loss_rows, slots, d, stream)
+                       : spex::lightgcn_batch_slots_layers(g, f.cur, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.labels, k.n, n_u, scale, nullptr,
+                                                           loss_rows, slots, d, stream);
+    return f.cur16 ? spex::lightgcn_batch_bf16_layers(g, f.cur16, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.labels, k.n, n_u, scale, push_scale, nullptr,
+                                                      loss_rows, dense, G, d, stream)
+                   : spex::lightgcn_batch_layers(g, f.cur, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.labels, k.n, n_u, scale, push_scale, nullptr,
+                                                 loss_rows, dense, G, d, stream);
+}
+
+static int bpr_batch(const spex_lightgcn_step_t *s, const StepBatch &k, const StepTables &f, int32_t *counts, float push_scale, float *loss_rows,
+                     float *slots, float *dense, float *G, void *stream)
+{
+    const spex_graph *g = s->graph;
+    const int32_t n_u = s->n_user_rows, d = s->d;
+    const float n_sum = (float)(s->L + 1), scale = 1.0f / (float)k.n, wd = s->weight_decay;
+    if (slots)
+        return f.cur16 ? spex::lightgcn_bpr_batch_slots_bf16_layers(g, f.cur16, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.c, k.n, n_u, scale, wd, s->E0,
+                                                                    counts, nullptr, loss_rows, slots, d, stream)
+                       : spex::lightgcn_bpr_batch_slots_layers(g, f.cur, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.c, k.n, n_u, scale, wd, s->E0, counts,
+                                                               nullptr, loss_rows, slots, d, stream);
+    return f.cur16 ? spex::lightgcn_bpr_batch_bf16_layers(g, f.cur16, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.c, k.n, n_u, scale, push_scale, wd, s->E0,
+                                                          counts, nullptr, loss_rows, dense, G, d, stream)
+                   : spex::lightgcn_bpr_batch_layers(g, f.cur, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.c, k.n, n_u, scale, push_scale, wd, s->E0, counts,
+                                                     nullptr, loss_rows, dense, G, d, stream);
+}
+
+static int lightgcn_step(spex_lightgcn_step_t *s, const StepBatch &k, void *stream);
+
+extern "C" int spex_lightgcn_step_bce_f32(spex_lightgcn_step_t *s, const int64_t *users, const int64_t *items,
+                                          const float *labels, int32_t B, float *loss_sum, void *stream)
+{
+    const StepBatch k = {"spex_lightgcn_step_bce_f32", users, items, nullptr, labels, B, 2, loss_sum};
+    return lightgcn_step(s, k, stream);
+}
+
+// The loop of every native epoch: batch k = samples [k B, min((k+1) B, n)) through step(k, b0, nb), at most max_steps (< 0: all) of
+// them, stopping at the first error.  keep_prob < 1: the per-step mask is set on both handles (once where gt == g) in front of the
+// step, and both are unmasked again on every path.
+template <class Step>
+static int epoch_loop(const spex_graph *graph, const spex_graph *graph_t, int64_t n, int32_t B, int64_t max_steps, float keep_prob,
+                      uint32_t drop_seed, Step step)
+{
+    spex_graph *g = const_cast<spex_graph *>(graph), *gt = const_cast<spex_graph *>(graph_t);
+    const bool drop = keep_prob < 1.0f;
+    int rc = SPEX_OK;
+    int64_t k = 0;
+    for (int64_t b0 = 0; b0 < n && rc == SPEX_OK && (max_steps < 0 || k < max_steps); b0 += B, ++k) {
+        const int32_t nb = (int32_t)(n - b0 < B ? n - b0 : B);
+        if (drop) {
+            const uint64_t seed = ((uint64_t)drop_seed << 32) | (uint64_t)(uint32_t)(k + 1);
+            rc = spex_graph_set_edge_mask(g, 2, nullptr, keep_prob, seed);
+            if (rc == SPEX_OK && gt != g) rc = spex_graph_set_edge_mask(gt, 2, nullptr, keep_prob, seed);
+            if (rc != SPEX_OK) break;
+        }
+        rc = step(k, b0, nb);
+    }
+    if (drop) {
+        (void)spex_graph_set_edge_mask(g, 0, nullptr, 1.0f, 0);
+        if (gt != g) (void)spex_graph_set_edge_mask(gt, 0, nullptr, 1.0f, 0);
+    }
+    return rc;
 }
 
 // Train() of main_rec.py:30-37 over a whole (pre-shuffled, device-resident) epoch as ONE call: batch k = samples [k B, min((k+1) B, n))
@@ -316,25 +399,9 @@ extern "C" int spex_lightgcn_epoch_bce_f32(spex_lightgcn_step_t *s, const int64_
     SPEX_CHECK_ARG(s && s->graph && s->graph_t, "spex_lightgcn_epoch_bce_f32: NULL step descriptor or graph");
     SPEX_CHECK_ARG(users && items && labels && loss_full && loss_ragged && n >= 0 && B >= 1, "spex_lightgcn_epoch_bce_f32: NULL pointer, n < 0 or B < 1");
     SPEX_CHECK_ARG(keep_prob > 0.0f && keep_prob <= 1.0f, "spex_lightgcn_epoch_bce_f32: keep_prob %g", keep_prob);
-    spex_graph *g = const_cast<spex_graph *>(s->graph), *gt = const_cast<spex_graph *>(s->graph_t);
-    const bool drop = keep_prob < 1.0f;
-    int rc = SPEX_OK;
-    int64_t k = 0;
-    for (int64_t b0 = 0; b0 < n && rc == SPEX_OK && (max_steps < 0 || k < max_steps); b0 += B, ++k) {
-        const int32_t nb = (int32_t)(n - b0 < B ? n - b0 : B);
-        if (drop) {
-            const uint64_t seed = ((uint64_t)drop_seed << 32) | (uint64_t)(uint32_t)(k + 1);
-            rc = spex_graph_set_edge_mask(g, 2, nullptr, keep_prob, seed);
-            if (rc == SPEX_OK && gt != g) rc = spex_graph_set_edge_mask(gt, 2, nullptr, keep_prob, seed);
-            if (rc != SPEX_OK) break;
-        }
-        rc = spex_lightgcn_step_bce_f32(s, users + b0, items + b0, labels + b0, nb, nb == B ? loss_full : loss_ragged, stream);
-    }
-    if (drop) {
-        (void)spex_graph_set_edge_mask(g, 0, nullptr, 1.0f, 0);
-        if (gt != g) (void)spex_graph_set_edge_mask(gt, 0, nullptr, 1.0f, 0);
-    }
-    return rc;
+    return epoch_loop(s->graph, s->graph_t, n, B, max_steps, keep_prob, drop_seed, [&](int64_t, int64_t b0, int32_t nb) {
+        return spex_lightgcn_step_bce_f32(s, users + b0, items + b0, labels + b0, nb, nb == B ? loss_full : loss_ragged, stream);
+    });
 }
 
 // The exact BPR training step — BPR differentiated through the propagation, an L2 term on the E0 rows of the batch, Adam: upstream
@@ -361,146 +428,124 @@ extern "C" int spex_lightgcn_epoch_bce_f32(spex_lightgcn_step_t *s, const int64_
 // 159.1 / 159.8 (no), 1 024: 176.5 / 165.3; d = 256: 256: 214.9 / 224.6 (no), 512: 247.1 / 234.6 and 246.0 / 232.6.
 constexpr int32_t kBprStepDenseMinTriples = 768, kBprStepDenseMinTriples128 = 1024, kBprStepDenseMinTriples256 = 512;
 
-extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const int64_t *users, const int64_t *pos, const int64_t *neg,
-                                               int32_t T, float *loss_sum, void *stream)
+// The schedule of both kinds: checks -> [sparse-Adam clear] -> [frontier lists] -> L - 1 forward launches -> the batch launch in one of
+// its forms -> the backward behind it -> ONE Adam launch.  s->t advances only once every launch of the step is queued.
+//   SPEX_STEP_DETERMINISTIC: every sum that the fast path leaves to float atomics is taken in a fixed order — same forward (same
+//                   kernel code for the batch's rows: bit-identical scores), the samples' gradient rows leave as per-sample slots and
+//                   are added per table row in ascending slot order (what the reference's CPU index backward does, model.py:115-116),
+//                   and the whole backward runs in pull form (each output row one chain in ascending column order, like the
+//                   reference's sparse addmm).  Per-sample losses: head of lo_batch, summed in order by the Adam pass.
+//   dense (BPR):    the batch launch with the push skipped — the gradient rows go to the dense g_out with atomics — and the whole
+//                   backward in pull form (L products: their cost does not grow with T, the push's does)
+//   BCE at L == 1:  the last layer at the batch's rows, scoring, then grad = (g + A^T g) / 2 as one pull-form product
+//   push:           the batch-sized middle as one launch, the first backward product G_(L-1) = (g + A^T g) / (L+1) in push form over the
+//                   rows of A itself: (A^T g)[c] = sum_r A[r, c] g[r] (g_out and the push target ws_bwd[0] are all-zero here: the Adam
+//                   pass clears them for the next step; first call: the caller); then the pull products (step_backward_pulls)
+static int lightgcn_step(spex_lightgcn_step_t *s, const StepBatch &k, void *stream)
 {
-    const char *who = "spex_lightgcn_step_bpr_adam_f32";
-    SPEX_CHECK_ARG(s && s->graph && s->graph_t && s->E0 && s->m && s->v && s->light_out && s->ws_fwd && s->lo_batch && s->g_out
-                       && s->ws_bwd && s->grad_E0 && s->grad_slots && s->row_counts,
-                   "%s: NULL field in the step descriptor (row_counts included)", who);
-    SPEX_CHECK_ARG(users && pos && neg && loss_sum && T >= 1, "%s: NULL batch pointer or T < 1", who);
+    SPEX_TRY(step_check(s, k));
     const spex_graph *g = s->graph, *gt = s->graph_t;
-    const int32_t L = s->L, d = s->d, n_u = s->n_user_rows;
-    SPEX_CHECK_ARG(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_rows, "%s: square graphs of one size", who);
-    const bool bf16 = (s->flags & SPEX_STEP_BF16_GATHER) != 0;
-    if (bf16) SPEX_TRY(bf16_step_check(s, who));
-    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0, sp = (s->flags & SPEX_STEP_SPARSE_ADAM) != 0;
-    if (sp) SPEX_TRY(sparse_adam_check(s, who));
-    if (fr) SPEX_TRY(frontier_step_check(s, who));
-    if ((s->flags & SPEX_STEP_WIDE) != 0) {
-        if (d != 128 && d != 256) {
-            spex::set_error("%s: SPEX_STEP_WIDE takes d = 128 or 256 (got %d); d == 64 runs without the flag — the widths are 64, 128 and 256", who, d);
-            return SPEX_ERR_UNSUPPORTED;
-        }
-    } else if (d != 64) {
-        spex::set_error("%s: d == 64 only (got %d); d = 128 / 256 take the launch-by-launch form", who, d);
-        return SPEX_ERR_UNSUPPORTED;
-    }
-    SPEX_CHECK_ARG(L >= 1 && n_u >= 0 && n_u <= g->n_rows, "%s: L=%d n_user_rows=%d (needs L >= 1)", who, L, n_u);
-    SPEX_CHECK_ARG(T <= INT32_MAX / 3 && s->slot_capacity >= 3 * T, "%s: slot capacity %d < 3 T = %lld", who, s->slot_capacity, 3LL * T);
-    SPEX_CHECK_ARG(s->weight_decay >= 0.0f, "%s: weight_decay %g", who, (double)s->weight_decay);
-    // edge dropout: the BCE step's rules
-    SPEX_CHECK_ARG(g->mask_mode == gt->mask_mode && (g->mask_mode == 0 || (g->keep_prob == gt->keep_prob && g->seed == gt->seed && g->keep == gt->keep)),
-                   "%s: graph and graph_t must carry the same edge-dropout mask", who);
-    SPEX_CHECK_ARG(g->mask_mode == 0 || (gt != g && L >= 2),
-                   "%s: edge dropout needs L >= 2 and graph_t = the transposed handle (with its edge-id permutation)", who);
+    const int32_t L = s->L, d = s->d, n_u = s->n_user_rows, n = k.n, t_next = s->t + 1;
     const size_t sz = (size_t)g->n_rows * d;
-    const bool det = (s->flags & SPEX_STEP_DETERMINISTIC) != 0;
-    const int32_t t_next = s->t + 1;
-    const float wd = s->weight_decay;
-    int32_t *cnt = s->row_counts + (size_t)(t_next & 1) * g->n_rows, *cnt_other = s->row_counts + (size_t)((t_next + 1) & 1) * g->n_rows;
-    spex::L2Rows l2;
-    l2.count = wd > 0.0f ? cnt : nullptr;
-    l2.clear = cnt_other;
-    l2.scale = wd / (float)T;
-    l2.g_store = s->grad_E0;
-    l2.shift = d == 64 ? 4 : (d == 128 ? 5 : 6);
+    const bool bpr = k.rows == 3, bf16 = (s->flags & SPEX_STEP_BF16_GATHER) != 0, det = (s->flags & SPEX_STEP_DETERMINISTIC) != 0;
+    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0, sp = (s->flags & SPEX_STEP_SPARSE_ADAM) != 0;
+    // BPR: the L2 term's count tables by step parity — the batch launch counts into one, the Adam pass clears the other
+    spex::L2Rows l2_rows;
+    const spex::L2Rows *l2 = nullptr;
+    int32_t *counts = nullptr, *counts_other = nullptr;
+    if (bpr) {
+        counts_other = s->row_counts + (size_t)((t_next + 1) & 1) * g->n_rows;
+        if (s->weight_decay > 0.0f) counts = s->row_counts + (size_t)(t_next & 1) * g->n_rows;
+        l2_rows.count = counts;
+        l2_rows.clear = counts_other;
+        l2_rows.scale = s->weight_decay / (float)n;
+        l2_rows.g_store = s->grad_E0;
+        l2_rows.shift = d == 64 ? 4 : (d == 128 ? 5 : 6);
+        l2 = &l2_rows;
+    }
     if (sp) {
         // (in front of the lists: the clear may read the previous step's.  The row-sparse pass does not clear the other parity's count
         //  table row by row — the rows that hold counts there are an earlier batch's — so the step clears it whole: 4 N bytes)
         SPEX_TRY(sparse_adam_begin(s, sz, stream));
-        SPEX_TRY(spex::zero_f32(reinterpret_cast<float *>(cnt_other), (int64_t)g->n_rows, stream));
-        l2.clear = nullptr;
+        if (bpr) SPEX_TRY(spex::zero_f32(reinterpret_cast<float *>(counts_other), (int64_t)g->n_rows, stream));
+        l2_rows.clear = nullptr;
     } else {
-        s->flags &= ~SPEX_STEP_GRAD_ROWS_LISTED;                                       // (this step writes grad_E0 wherever it likes)
+        s->flags &= ~SPEX_STEP_GRAD_ROWS_LISTED;                       // (this step writes grad_E0 wherever it likes)
     }
-    if (fr) SPEX_TRY(frontier_lists(s, users, T, pos, T, neg, T, stream, sp));         // (the first launches: every argument check is above)
-    // ---- forward: layers 0 .. L-2 over the whole graph (plain for L <= 3), the last layer at the batch's rows only
-    const bool plain = L >= 2 && L <= 3;
-    const float *cur = s->E0;
-    const uint16_t *cur16 = nullptr;             // SPEX_STEP_BF16_GATHER: the batch kernel's gather source, bf16(y_(L-1))
-    uint16_t *shadow = bf16 ? s->E0_16 : nullptr;   // ... and the Adam pass's second output
-    if (bf16) SPEX_TRY(bf16_forward(s, sz, &cur16, stream));
-    for (int32_t l = 0; !bf16 && l + 1 < L; ++l) {
-        float *nxt = s->ws_fwd + (size_t)(l & 1) * sz;
-        if (fr && l + 2 == L) SPEX_TRY(frontier_forward(s, cur, nxt, plain, stream));
-        else if (plain) SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
-        else SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, l == 0 ? s->E0 : s->light_out, s->light_out, 1.0f, d, stream));
-        cur = nxt;
-    }
-    const float *sum0 = plain || L == 1 ? s->E0 : s->light_out;
-    const float *sum1 = plain ? s->ws_fwd : nullptr, *sum2 = plain && L == 3 ? s->ws_fwd + sz : nullptr;
-    // the batch launch in its four forms: slots (G and g_out NULL, slots given) or atomics, from the fp32 or the bf16 table
+    if (fr) SPEX_TRY(frontier_lists(s, k.a, n, k.b, n, k.c, k.c ? n : 0, stream, sp));      // (the first launches: every argument check is above)
+    StepTables f;
+    SPEX_TRY(step_forward(s, sz, stream, &f));
     auto batch = [&](float push_scale, float *loss_rows, float *slots, float *dense, float *G) -> int {
-        int32_t *counts = l2.count ? cnt : nullptr;
-        if (slots)
-            return bf16 ? spex::lightgcn_bpr_batch_slots_bf16_layers(g, cur16, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u,
-                                                                     1.0f / (float)T, wd, s->E0, counts, nullptr, loss_rows, slots, d, stream)
-                        : spex::lightgcn_bpr_batch_slots_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u,
-                                                                1.0f / (float)T, wd, s->E0, counts, nullptr, loss_rows, slots, d, stream);
-        return bf16 ? spex::lightgcn_bpr_batch_bf16_layers(g, cur16, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u, 1.0f / (float)T,
-                                                           push_scale, wd, s->E0, counts, nullptr, loss_rows, dense, G, d, stream)
-                    : spex::lightgcn_bpr_batch_layers(g, cur, sum0, sum1, sum2, (float)(L + 1), users, pos, neg, T, n_u, 1.0f / (float)T,
-                                                      push_scale, wd, s->E0, counts, nullptr, loss_rows, dense, G, d, stream);
+        return bpr ? bpr_batch(s, k, f, counts, push_scale, loss_rows, slots, dense, G, stream)
+                   : bce_batch(s, k, f, push_scale, loss_rows, slots, dense, G, stream);
     };
     // the whole backward in pull form from the dense d loss / d light_out
     auto backward_dense = [&]() -> int {
         return bf16 ? spex_propagate_bwd_bf16_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, s->ws16, L, d, stream)
                     : spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream);
     };
-    if (det) {
-        float *loss_rows = s->lo_batch;
-        SPEX_TRY(batch(0.0f, loss_rows, s->grad_slots, nullptr, nullptr));
-        SPEX_TRY(spex_reduce_slots_f32(users, T, 0, nullptr, 0, 0, g->n_rows, s->grad_slots, d, 1.0f, s->g_out, 0, d, stream));
-        SPEX_TRY(spex_reduce_slots_f32(pos, T, n_u, neg, T, n_u, g->n_rows, s->grad_slots + (size_t)T * d, d, 1.0f, s->g_out, 1, d, stream));
-        SPEX_TRY(backward_dense());
-        SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, t_next, s->lr, s->beta1, s->beta2, s->eps, s->g_out,
-                                    s->ws_bwd /* keeps the fast path's push target all-zero */, stream, loss_rows, T, loss_sum, nullptr,
-                                    nullptr, 1.0f, &l2, shadow));
-        s->t = t_next;
-        return SPEX_OK;
-    }
     const int32_t dense_min = d == 64 ? kBprStepDenseMinTriples : (d == 128 ? kBprStepDenseMinTriples128 : kBprStepDenseMinTriples256);
-    const bool dense = !fr && ((s->flags & SPEX_STEP_BPR_DENSE) != 0 || ((s->flags & SPEX_STEP_BPR_PUSH) == 0 && T >= dense_min));
-    if (dense) {
-        // ---- large batches: the same launch with the push skipped — the gradient rows go to the dense g_out with atomics — and the
-        //      whole backward in pull form (L products: their cost does not grow with T, the push's does)
+    const bool dense = bpr && !fr && ((s->flags & SPEX_STEP_BPR_DENSE) != 0 || ((s->flags & SPEX_STEP_BPR_PUSH) == 0 && n >= dense_min));
+    // what the closing Adam launch reads besides the gradient, as the dense-backward forms leave it; the other forms say otherwise
+    const float *grad = s->grad_E0, *loss_rows = s->grad_slots, *add = nullptr;
+    float *zero1 = s->g_out, *zero2 = s->ws_bwd /* stays the push form's all-zero target */, add_div = 1.0f;
+    if (det) {
+        SPEX_TRY(batch(0.0f, s->lo_batch, s->grad_slots, nullptr, nullptr));
+        if (bpr) {
+            // (users over slots [0, T), then (pos, neg) over [T, 3 T) — user rows and item rows never coincide for valid triples; the
+            //  second call accumulates, so that the all-zero slots of a skipped triple whose negative item index lands among the user
+            //  rows clobber nothing)
+            SPEX_TRY(spex_reduce_slots_f32(k.a, n, 0, nullptr, 0, 0, g->n_rows, s->grad_slots, d, 1.0f, s->g_out, 0, d, stream));
+            SPEX_TRY(spex_reduce_slots_f32(k.b, n, n_u, k.c, n, n_u, g->n_rows, s->grad_slots + (size_t)n * d, d, 1.0f, s->g_out, 1, d, stream));
+        } else {
+            SPEX_TRY(spex_reduce_slots_f32(k.a, n, 0, k.b, n, n_u, g->n_rows, s->grad_slots, d, 1.0f, s->g_out, 0, d, stream));
+        }
+        SPEX_TRY(backward_dense());
+        loss_rows = s->lo_batch;
+    } else if (dense) {
         SPEX_TRY(batch(0.0f, s->grad_slots, nullptr, s->g_out, nullptr));
         SPEX_TRY(backward_dense());
-        SPEX_TRY(spex::adam_step_z2(s->E0, s->grad_E0, s->m, s->v, (int64_t)sz, t_next, s->lr, s->beta1, s->beta2, s->eps, s->g_out,
-                                    s->ws_bwd /* propagate_bwd's scaled gradient: the push target stays all-zero */, stream, s->grad_slots, T,
-                                    loss_sum, nullptr, nullptr, 1.0f, &l2, shadow));
-        s->t = t_next;
-        return SPEX_OK;
+    } else if (!bpr && L == 1) {
+        SPEX_TRY(spex_spmm_rowlist_f32(g, f.cur, k.a, n, 0, k.b, n, n_u, nullptr, s->E0, s->lo_batch, (float)(L + 1), d, stream));
+        SPEX_TRY(spex_score_bce_slots_f32(s->lo_batch, s->lo_batch + (size_t)n_u * d, d, d, n_u, g->n_rows - n_u, k.a, k.b, k.labels, n, d,
+                                          k.loss_sum, s->g_out, s->g_out + (size_t)n_u * d, 1.0f / (float)n, s->grad_slots, d, stream));
+        SPEX_TRY(spex_propagate_bwd_f32(gt, s->g_out, s->grad_E0, s->ws_bwd, L, d, stream));
+        loss_rows = nullptr;            // (the scoring launch has added the loss itself, and nothing pushed)
+        zero2 = nullptr;
+    } else {
+        // (BPR at L == 1 runs this form too: no pull product, the push target IS the gradient — read, stored to grad_E0 and cleared by the
+        //  Adam pass.  Nothing reads the dense d loss / d light_out there or in the all-plain L == 3 step: it is not formed)
+        float *G = s->ws_bwd;
+        const bool no_dense = L == 3 || L == 1;
+        SPEX_TRY(batch(1.0f / (float)(L + 1), s->grad_slots /* per-sample losses, summed by the Adam pass */, nullptr, no_dense ? nullptr : s->g_out, G));
+        const float *src = G;
+        if (bf16) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
+        float *W = nullptr;
+        if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream, sp));     // product l = L - 2 over the frontier
+        if (fr) src = W;
+        // (none under SPEX_STEP_SPARSE_ADAM, L == 2: the frontier push has left the whole product in grad_E0, non-zero in F2 only)
+        if (!bf16) SPEX_TRY(step_backward_pulls(gt, src, fr ? L - 3 : L - 2, s->g_out, s->ws_bwd, s->grad_E0, L, d, stream));
+        if (L == 1) grad = G;
+        if (no_dense) zero1 = nullptr;                                  // (untouched, all-zero)
+        add = L == 1 ? nullptr : (L == 3 ? G : s->g_out);
+        add_div = L == 3 ? 1.0f : (float)(L + 1);
     }
-    // ---- the batch-sized middle as one launch (g_out and G are all-zero here: the Adam pass clears them), then the L - 1 pull-form
-    //      products G_l = g / (L+1) + A^T G_{l+1}: the last one plain (the Adam pass adds its g / (L+1) share), at L == 3 both plain
-    //      with the push target P added instead — A^T (A^T P) + P, the identity derived at spex_lightgcn_step_bce_f32
-    float *G = s->ws_bwd;
-    const bool no_dense = L == 3 || L == 1;        // nothing reads the dense d loss / d light_out then: it is not formed
-    SPEX_TRY(batch(1.0f / (float)(L + 1), s->grad_slots /* per-triple losses, summed by the Adam pass */, nullptr, no_dense ? nullptr : s->g_out, G));
-    const float *c2 = G;
-    if (bf16) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
-    float *W = nullptr;
-    if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream, sp));     // product l = L - 2 over the frontier
-    if (fr) c2 = W;
-    if (sp) {                                           // L == 2: the push has left the whole product in grad_E0, non-zero in F2 only
-        SPEX_TRY(sparse_adam_pass(s, t_next, T, loss_sum, &l2, stream));
-        s->t = t_next;
-        return SPEX_OK;
-    }
-    for (int32_t l = fr ? L - 3 : L - 2; !bf16 && l >= 0; --l) {
-        float *nxt = l == 0 ? s->grad_E0 : s->ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;
-        if (l == 0 || L == 3) SPEX_TRY(spex_spmm_f32(gt, c2, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
-        else SPEX_TRY(spex_spmm_f32(gt, c2, nxt, s->g_out, (float)(L + 1), nullptr, nullptr, 1.0f, d, stream));
-        c2 = nxt;
-    }
-    // (L == 1: the push target IS the gradient — read, stored to grad_E0 and cleared by the same pass)
-    SPEX_TRY(spex::adam_step_z2(s->E0, L == 1 ? G : s->grad_E0, s->m, s->v, (int64_t)sz, t_next, s->lr, s->beta1, s->beta2, s->eps,
-                                no_dense ? nullptr : s->g_out, s->ws_bwd, stream, s->grad_slots, T, loss_sum, nullptr,
-                                L == 1 ? nullptr : (L == 3 ? G : s->g_out), L == 3 ? 1.0f : (float)(L + 1), &l2, shadow));
+    // ---- Adam — over the whole table, or over the listed rows — which also sums the per-sample losses in order, adds the L2 gradient
+    //      and clears g_out and the push target for the next step
+    if (sp)
+        SPEX_TRY(sparse_adam_pass(s, t_next, n, k.loss_sum, l2, stream));      // (sets SPEX_STEP_GRAD_ROWS_LISTED again)
+    else
+        SPEX_TRY(spex::adam_step_z2(s->E0, grad, s->m, s->v, (int64_t)sz, t_next, s->lr, s->beta1, s->beta2, s->eps, zero1, zero2, stream, loss_rows, n,
+                                    k.loss_sum, nullptr, add, add_div, l2, bf16 ? s->E0_16 : nullptr));
     s->t = t_next;
     return SPEX_OK;
+}
+
+extern "C" int spex_lightgcn_step_bpr_adam_f32(spex_lightgcn_step_t *s, const int64_t *users, const int64_t *pos, const int64_t *neg,
+                                               int32_t T, float *loss_sum, void *stream)
+{
+    const StepBatch k = {"spex_lightgcn_step_bpr_adam_f32", users, pos, neg, nullptr, T, 3, loss_sum};
+    return lightgcn_step(s, k, stream);
 }
 
 // An epoch of pre-drawn, device-resident triples as ONE call: batch k = triples [k T, min((k+1) T, n)) through
@@ -512,25 +557,9 @@ extern "C" int spex_lightgcn_epoch_bpr_f32(spex_lightgcn_step_t *s, const int64_
     SPEX_CHECK_ARG(s && s->graph && s->graph_t, "spex_lightgcn_epoch_bpr_f32: NULL step descriptor or graph");
     SPEX_CHECK_ARG(users && pos && neg && loss_full && loss_ragged && n >= 0 && T >= 1, "spex_lightgcn_epoch_bpr_f32: NULL pointer, n < 0 or T < 1");
     SPEX_CHECK_ARG(keep_prob > 0.0f && keep_prob <= 1.0f, "spex_lightgcn_epoch_bpr_f32: keep_prob %g", keep_prob);
-    spex_graph *g = const_cast<spex_graph *>(s->graph), *gt = const_cast<spex_graph *>(s->graph_t);
-    const bool drop = keep_prob < 1.0f;
-    int rc = SPEX_OK;
-    int64_t k = 0;
-    for (int64_t b0 = 0; b0 < n && rc == SPEX_OK && (max_steps < 0 || k < max_steps); b0 += T, ++k) {
-        const int32_t nb = (int32_t)(n - b0 < T ? n - b0 : T);
-        if (drop) {
-            const uint64_t seed = ((uint64_t)drop_seed << 32) | (uint64_t)(uint32_t)(k + 1);
-            rc = spex_graph_set_edge_mask(g, 2, nullptr, keep_prob, seed);
-            if (rc == SPEX_OK && gt != g) rc = spex_graph_set_edge_mask(gt, 2, nullptr, keep_prob, seed);
-            if (rc != SPEX_OK) break;
-        }
-        rc = spex_lightgcn_step_bpr_adam_f32(s, users + b0, pos + b0, neg + b0, nb, nb == T ? loss_full : loss_ragged, stream);
-    }
-    if (drop) {
-        (void)spex_graph_set_edge_mask(g, 0, nullptr, 1.0f, 0);
-        if (gt != g) (void)spex_graph_set_edge_mask(gt, 0, nullptr, 1.0f, 0);
-    }
-    return rc;
+    return epoch_loop(s->graph, s->graph_t, n, T, max_steps, keep_prob, drop_seed, [&](int64_t, int64_t b0, int32_t nb) {
+        return spex_lightgcn_step_bpr_adam_f32(s, users + b0, pos + b0, neg + b0, nb, nb == T ? loss_full : loss_ragged, stream);
+    });
 }
 
 // A sampled epoch: the triples are drawn on the device (sampler.hip: one launch into the caller's index buffers) and consumed by the
@@ -616,13 +645,10 @@ extern "C" int spex_ngcf_epoch_bce_f32(spex_ngcf_step_t *s, const int64_t *users
 {
     SPEX_CHECK_ARG(s && users && items && labels && loss_full && loss_ragged && n >= 0 && B >= 1,
                    "spex_ngcf_epoch_bce_f32: NULL pointer, n < 0 or B < 1");
-    int rc = SPEX_OK;
-    int64_t k = 0;
-    for (int64_t b0 = 0; b0 < n && rc == SPEX_OK && (max_steps < 0 || k < max_steps); b0 += B, ++k) {
-        const int32_t nb = (int32_t)(n - b0 < B ? n - b0 : B);
-        rc = spex_ngcf_step_bce_f32(s, users + b0, items + b0, labels + b0, nb, nb == B ? loss_full : loss_ragged, stream);
-    }
-    return rc;
+    // (no edge dropout in NGCF: keep_prob = 1, the loop touches no handle)
+    return epoch_loop(nullptr, nullptr, n, B, max_steps, 1.0f, 0, [&](int64_t, int64_t b0, int32_t nb) {
+        return spex_ngcf_step_bce_f32(s, users + b0, items + b0, labels + b0, nb, nb == B ? loss_full : loss_ragged, stream);
+    });
 }
 
 // A sampled NGCF epoch: negatives (without replacement, per user), labels and the shuffle drawn on the device (sampler.hip: one launch
@@ -984,13 +1010,8 @@ extern "C" int spex_dual_task_step_f32(spex_dual_task_step_t *s, const int64_t *
         //      the scores only at the batch's rows
         //      (whole-graph launches in the plain form for L <= 3, the layer sum formed at the batch's rows: see the LightGCN step)
         const bool plain = L >= 2 && L <= 3;
-        const float *cur = E0;
-        for (int32_t l = 0; l + 1 < L; ++l) {
-            float *nxt = s->ws_fwd + (size_t)(l & 1) * sz;
-            if (plain) SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
-            else SPEX_TRY(spex_spmm_f32(g, cur, nxt, nullptr, 1.0f, l == 0 ? E0 : s->light, s->light, 1.0f, d, stream));
-            cur = nxt;
-        }
+        const float *cur = nullptr;
+        SPEX_TRY(forward_layers(g, E0, s->light, s->ws_fwd, L, L - 1, d, stream, &cur));
         if (!det && L >= 2) {
             // (fast path: last layer at the batch's rows + layer mean + gate + scores + the gate's backward + the first backward
             //  product in push form — ONE launch, batch.hip: gated_batch_push_kernel; then the L-1 pull-form launches on A^T, the
@@ -1004,14 +1025,8 @@ extern "C" int spex_dual_task_step_f32(spex_dual_task_step_t *s, const int64_t *
                                                    d, stream));
             att_copies_used = att_copies_max;
             fused_middle_used = true;
-            const float *c2 = G;
-            for (int32_t l = L - 2; l >= 0; --l) {
-                float *nxt = l == 0 ? s->g_E0 : s->ws_bwd + (size_t)(1 + ((L - 2 - l) & 1)) * sz;
-                // (L == 3: both products plain, the Adam pass adds the push target P instead of g_prop / 4 — see the LightGCN step)
-                if (l == 0 || L == 3) SPEX_TRY(spex_spmm_f32(gt, c2, nxt, nullptr, 1.0f, nullptr, nullptr, 1.0f, d, stream));
-                else SPEX_TRY(spex_spmm_f32(gt, c2, nxt, s->g_prop, (float)(L + 1), nullptr, nullptr, 1.0f, d, stream));
-                c2 = nxt;
-            }
+            // (L == 3: both products plain, the Adam pass adds the push target P instead of g_prop / 4 — see step_backward_pulls)
+            SPEX_TRY(step_backward_pulls(gt, G, L - 2, s->g_prop, s->ws_bwd, s->g_E0, L, d, stream));
             plain_last = true;
             return SPEX_OK;
         }
@@ -1092,33 +1107,16 @@ extern "C" int spex_dual_task_epoch_f32(spex_dual_task_step_t *s, const int64_t 
     SPEX_CHECK_ARG(s && s->graph && s->graph_t && users && items && labels && path_off && n >= 0 && B >= 1,
                    "spex_dual_task_epoch_f32: NULL pointer, n < 0 or B < 1");
     SPEX_CHECK_ARG(keep_prob > 0.0f && keep_prob <= 1.0f, "spex_dual_task_epoch_f32: keep_prob %g", keep_prob);
-    spex_graph *g = const_cast<spex_graph *>(s->graph), *gt = const_cast<spex_graph *>(s->graph_t);
-    const bool drop = keep_prob < 1.0f;
-    int rc = SPEX_OK;
-    int64_t k = 0;
-    for (int64_t b0 = 0; b0 < n && rc == SPEX_OK && (max_steps < 0 || k < max_steps); b0 += B, ++k) {
-        const int32_t nb = (int32_t)(n - b0 < B ? n - b0 : B);
+    return epoch_loop(s->graph, s->graph_t, n, B, max_steps, keep_prob, drop_seed, [&](int64_t k, int64_t b0, int32_t nb) {
         const int64_t p0 = path_off[k], T = path_off[k + 1] - p0;
-        if (T < 0 || (T > 0 && !(seq && seq_l && targets))) {
+        if (T < 0 || (T > 0 && !(seq && seq_l && targets))) {          // (in front of the batch's first launch)
             spex::set_error("spex_dual_task_epoch_f32: batch %lld has %lld paths (offsets must ascend; path arrays must be given)", (long long)k,
                             (long long)T);
-            rc = SPEX_ERR_INVALID;
-            break;
+            return (int)SPEX_ERR_INVALID;
         }
-        if (drop) {
-            const uint64_t seed = ((uint64_t)drop_seed << 32) | (uint64_t)(uint32_t)(k + 1);
-            rc = spex_graph_set_edge_mask(g, 2, nullptr, keep_prob, seed);
-            if (rc == SPEX_OK && gt != g) rc = spex_graph_set_edge_mask(gt, 2, nullptr, keep_prob, seed);
-            if (rc != SPEX_OK) break;
-        }
-        rc = spex_dual_task_step_f32(s, users + b0, items + b0, labels + b0, nb, T ? seq + p0 * s->path_len : nullptr, T ? seq_l + p0 : nullptr,
-                                     T ? targets + p0 : nullptr, (int32_t)T, stream);
-    }
-    if (drop) {
-        (void)spex_graph_set_edge_mask(g, 0, nullptr, 1.0f, 0);
-        if (gt != g) (void)spex_graph_set_edge_mask(gt, 0, nullptr, 1.0f, 0);
-    }
-    return rc;
+        return spex_dual_task_step_f32(s, users + b0, items + b0, labels + b0, nb, T ? seq + p0 * s->path_len : nullptr, T ? seq_l + p0 : nullptr,
+                                       T ? targets + p0 : nullptr, (int32_t)T, stream);
+    });
 }
 
 // spex_dual_task_epoch_f32 over paths staged with a fixed stride: batch k's paths are the first h_count[k] rows from row
@@ -1141,24 +1139,10 @@ extern "C" int spex_dual_task_epoch_strided_f32(spex_dual_task_step_t *s, const 
                        "spex_dual_task_epoch_strided_f32: batch %lld has %lld paths (stride %lld, capacity %d; path arrays must be given)",
                        (long long)k, (long long)T, (long long)path_stride, s->path_capacity);
     }
-    spex_graph *g = const_cast<spex_graph *>(s->graph), *gt = const_cast<spex_graph *>(s->graph_t);
-    const bool drop = keep_prob < 1.0f;
-    int rc = SPEX_OK;
-    for (int64_t k = 0; k < n_batches && rc == SPEX_OK; ++k) {
-        const int64_t b0 = k * B, p0 = k * path_stride;
-        const int32_t nb = (int32_t)(n - b0 < B ? n - b0 : B), T = h_count[k];
-        if (drop) {
-            const uint64_t seed = ((uint64_t)drop_seed << 32) | (uint64_t)(uint32_t)(k + 1);
-            rc = spex_graph_set_edge_mask(g, 2, nullptr, keep_prob, seed);
-            if (rc == SPEX_OK && gt != g) rc = spex_graph_set_edge_mask(gt, 2, nullptr, keep_prob, seed);
-            if (rc != SPEX_OK) break;
-        }
-        rc = spex_dual_task_step_f32(s, users + b0, items + b0, labels + b0, nb, T ? seq + p0 * s->path_len : nullptr, T ? seq_l + p0 : nullptr,
-                                     T ? targets + p0 : nullptr, T, stream);
-    }
-    if (drop) {
-        (void)spex_graph_set_edge_mask(g, 0, nullptr, 1.0f, 0);
-        if (gt != g) (void)spex_graph_set_edge_mask(gt, 0, nullptr, 1.0f, 0);
-    }
-    return rc;
+    return epoch_loop(s->graph, s->graph_t, n, B, max_steps, keep_prob, drop_seed, [&](int64_t k, int64_t b0, int32_t nb) {
+        const int64_t p0 = k * path_stride;
+        const int32_t T = h_count[k];
+        return spex_dual_task_step_f32(s, users + b0, items + b0, labels + b0, nb, T ? seq + p0 * s->path_len : nullptr, T ? seq_l + p0 : nullptr,
+                                       T ? targets + p0 : nullptr, T, stream);
+    });
 }

@@ -402,10 +402,23 @@ class LightGCNStepper:
             self.graph_t.set_edge_mask(*args)
 
     # -- the whole step as one library call (spex_lightgcn_step_bce_f32): same launches, issued from native code
-    def _one_call_ok(self, users, items, labels):
+    def _one_call_shape_ok(self):
+        """What the stepper itself must be for the one-call steps of either kind (without a batch)."""
         masked = getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
-        return (self.L >= 1 and self._wide_ok and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
-                and _batch_ok(users, items, labels))
+        return self.L >= 1 and self._wide_ok and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
+
+    def _one_call_ok(self, users, items, labels):
+        return self._one_call_shape_ok() and _batch_ok(users, items, labels)
+
+    def _one_call_bpr_ok(self, users, pos, neg):
+        return (self._one_call_shape_ok() and all(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() for t in (users, pos, neg))
+                and users.numel() == pos.numel() == neg.numel() >= 1)
+
+    def _check_epoch_dropout(self, who, keep_prob):
+        """The native epochs' keep_prob < 1: refused on a frontier stepper, and the step's own mask rule ahead of the call."""
+        self._refuse_frontier_dropout(f"LightGCNStepper.{who}", keep_prob)
+        if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
+            raise ValueError(f"LightGCNStepper.{who}: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
 
     def _prepare_desc(self, B, rows_per_sample=2):
         """The one-call step's descriptor for batches of up to B samples (built once, refreshed per call)."""
@@ -454,8 +467,11 @@ class LightGCNStepper:
         d.row_counts = None if self.row_counts is None else self.row_counts.data_ptr()
         return d
 
-    def _after_desc(self, d):
-        """After a native call and its _bump: what the call wrote back into the descriptor."""
+    def _after_call(self, d, *written):
+        """After a native call on descriptor d: the step count, the version bumps of what it wrote (E0, m, v and the bf16 shadow, plus
+        `written`), and what the call wrote back into the descriptor."""
+        self.t = d.t
+        _bump(self.E0, self.m, self.v, self.E0_16, *written)
         if self.frontier and d is self._desc:
             self._front.epoch = d.frontier_epoch
         # (a sparse-Adam step leaves the bit set, every other step of these entry points clears it)
@@ -467,9 +483,7 @@ class LightGCNStepper:
         self._clear_row_counts()
         _launch(self.E0.device, "spex_lightgcn_step_bce_f32", ctypes.byref(d), ctypes.c_void_p(users.data_ptr()),
                 ctypes.c_void_p(items.data_ptr()), ctypes.c_void_p(labels.data_ptr()), B, ctypes.c_void_p(loss_acc.data_ptr()))
-        self.t = d.t
-        _bump(self.E0, self.m, self.v, loss_acc, self.E0_16)
-        self._after_desc(d)
+        self._after_call(d, loss_acc)
         return None
 
     def epoch_bce(self, users, items, labels, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
@@ -479,17 +493,13 @@ class LightGCNStepper:
         edge mask, a fresh one per step (seed (drop_seed << 32) | step — trainer.edge_dropout_mask's "philox" stream)."""
         if not self._one_call_ok(users[:1], items[:1], labels[:1]):
             raise ValueError("LightGCNStepper.epoch_bce: needs an embedding width of 64, 128 or 256 and contiguous int64 / fp32 device tensors")
-        self._refuse_frontier_dropout("LightGCNStepper.epoch_bce", keep_prob)
-        if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
-            raise ValueError("LightGCNStepper.epoch_bce: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
+        self._check_epoch_dropout("epoch_bce", keep_prob)
         d = self._prepare_desc(min(int(batch_size), users.numel()))
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         self._clear_row_counts()
         _launch(self.E0.device, "spex_lightgcn_epoch_bce_f32", ctypes.byref(d), vp(users), vp(items), vp(labels), users.numel(), int(batch_size),
                 -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
-        self.t = d.t
-        _bump(self.E0, self.m, self.v, loss_full, loss_ragged, self.E0_16)
-        self._after_desc(d)
+        self._after_call(d, loss_full, loss_ragged)
 
     def backward_from_batch_rows(self, users, items):
         """grad_E0 from g_out (non-zero on the batch's rows only).  The first product of the backward pass, A^T g, touches
@@ -587,20 +597,12 @@ class LightGCNStepper:
         return loss_sum / T
 
     # -- the exact BPR step as one library call (spex_lightgcn_step_bpr_adam_f32) and the native epoch over it
-    def _one_call_bpr_ok(self, users, pos, neg):
-        masked = getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
-        return (self.L >= 1 and self._wide_ok and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
-                and all(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() for t in (users, pos, neg))
-                and users.numel() == pos.numel() == neg.numel() >= 1)
-
     def _step_bpr_one_call(self, users, pos, neg, loss_acc):
         T = users.numel()
         d = self._prepare_desc(T, 3)
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         _launch(self.E0.device, "spex_lightgcn_step_bpr_adam_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), T, vp(loss_acc))
-        self.t = d.t
-        _bump(self.E0, self.m, self.v, self.grad_E0, loss_acc, self.E0_16)
-        self._after_desc(d)
+        self._after_call(d, self.grad_E0, loss_acc)
         return None
 
     def epoch_bpr(self, users, pos, neg, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
@@ -608,37 +610,24 @@ class LightGCNStepper:
         [k T, (k+1) T) through the one-call exact BPR step.  loss_full / loss_ragged, keep_prob and drop_seed as in epoch_bce."""
         if not self._one_call_bpr_ok(users[:1], pos[:1], neg[:1]):
             raise ValueError("LightGCNStepper.epoch_bpr: needs an embedding width of 64, 128 or 256 and contiguous int64 device tensors")
-        self._refuse_frontier_dropout("LightGCNStepper.epoch_bpr", keep_prob)
-        if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
-            raise ValueError("LightGCNStepper.epoch_bpr: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
+        self._check_epoch_dropout("epoch_bpr", keep_prob)
         d = self._prepare_desc(min(int(batch_size), users.numel()), 3)
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         _launch(self.E0.device, "spex_lightgcn_epoch_bpr_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), users.numel(), int(batch_size),
                 -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
-        self.t = d.t
-        _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged, self.E0_16)
-        self._after_desc(d)
+        self._after_call(d, self.grad_E0, loss_full, loss_ragged)
 
-    # -- sampled epochs: the triples drawn on the device by the same native call that trains on them
-    def _one_call_bpr_shape_ok(self):
-        """_one_call_bpr_ok without a batch: what the stepper itself must be for the one-call exact BPR step."""
-        masked = getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
-        return self.L >= 1 and self._wide_ok and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
-
+    # -- sampled epochs: the epoch drawn on the device by the same native call that trains on it (BprDeviceSampler: triples;
+    #    BceDeviceSampler: negatives, labels and the shuffle)
     def _sampled_args(self, sampler, batch_size, max_steps, keep_prob, who):
         if sampler.rowptr.device != self.E0.device:
             raise ValueError(f"LightGCNStepper.{who}: the sampler's tables live on {sampler.rowptr.device}, the stepper on {self.E0.device}")
-        if not self._one_call_bpr_shape_ok() or sampler.n < 1 or int(batch_size) < 1:
+        if not self._one_call_shape_ok() or sampler.n < 1 or int(batch_size) < 1:
             raise ValueError(f"LightGCNStepper.{who}: needs an embedding width of 64, 128 or 256, a sampler with n >= 1 and batch_size >= 1")
-        self._refuse_frontier_dropout(f"LightGCNStepper.{who}", keep_prob)
-        if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
-            raise ValueError(f"LightGCNStepper.{who}: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
-        d = self._prepare_desc(min(int(batch_size), sampler.n), 3)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        tables = (vp(sampler.rowptr), vp(sampler.items), sampler.rowptr.numel() - 1, vp(sampler.active), sampler.active.numel(), sampler.n_items,
-                  sampler.n, ops.BPR_SAMPLER_MODES[sampler.by], sampler.seed & 0xFFFFFFFFFFFFFFFF)
+        self._check_epoch_dropout(who, keep_prob)
+        d = self._prepare_desc(min(int(batch_size), sampler.n), sampler.rows_per_sample)
         loop = (int(batch_size), -1 if max_steps is None else int(max_steps), float(keep_prob))
-        return d, tables, loop, tuple(vp(t) for t in sampler.epoch_buffers())
+        return d, sampler.native_tables(), loop, tuple(ctypes.c_void_p(t.data_ptr()) for t in sampler.epoch_buffers())
 
     def epoch_bpr_sampled(self, sampler, epoch, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
         """Epoch number `epoch` of a BprDeviceSampler drawn and trained as ONE native call (spex_lightgcn_epoch_bpr_sampled_f32): one
@@ -648,9 +637,7 @@ class LightGCNStepper:
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         _launch(self.E0.device, "spex_lightgcn_epoch_bpr_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
                 int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
-        self.t = d.t
-        _bump(self.E0, self.m, self.v, self.grad_E0, loss_full, loss_ragged, self.E0_16, *sampler.epoch_buffers())
-        self._after_desc(d)
+        self._after_call(d, self.grad_E0, loss_full, loss_ragged, *sampler.epoch_buffers())
 
     def train_bpr_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
         """n_epochs sampled epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
@@ -665,43 +652,18 @@ class LightGCNStepper:
         d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, "train_bpr_sampled")
         _launch(self.E0.device, "spex_lightgcn_train_bpr_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
                 *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
-        self.t = d.t
-        _bump(self.E0, self.m, self.v, self.grad_E0, loss_epochs, self.E0_16, *sampler.epoch_buffers())
-        self._after_desc(d)
-
-    # -- sampled BCE epochs: negatives, labels and the shuffle drawn on the device by the same native call that trains on them
-    def _one_call_bce_shape_ok(self):
-        """_one_call_ok without a batch: what the stepper itself must be for the one-call BCE step."""
-        masked = getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
-        return self.L >= 1 and self._wide_ok and (not masked or (self.L >= 2 and self.graph_t is not self.graph))
-
-    def _sampled_bce_args(self, sampler, batch_size, max_steps, keep_prob, who):
-        if sampler.rowptr.device != self.E0.device:
-            raise ValueError(f"LightGCNStepper.{who}: the sampler's tables live on {sampler.rowptr.device}, the stepper on {self.E0.device}")
-        if not self._one_call_bce_shape_ok() or sampler.n < 1 or int(batch_size) < 1:
-            raise ValueError(f"LightGCNStepper.{who}: needs an embedding width of 64, 128 or 256, a sampler with n >= 1 and batch_size >= 1")
-        self._refuse_frontier_dropout(f"LightGCNStepper.{who}", keep_prob)
-        if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
-            raise ValueError(f"LightGCNStepper.{who}: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")
-        d = self._prepare_desc(min(int(batch_size), sampler.n))
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        tables = (vp(sampler.rowptr), vp(sampler.items), sampler.rowptr.numel() - 1, vp(sampler.pos_user), vp(sampler.pos_item), sampler.n_pos,
-                  sampler.num_ng, sampler.n_items, sampler.seed & 0xFFFFFFFFFFFFFFFF)
-        loop = (int(batch_size), -1 if max_steps is None else int(max_steps), float(keep_prob))
-        return d, tables, loop, tuple(vp(t) for t in sampler.epoch_buffers())
+        self._after_call(d, self.grad_E0, loss_epochs, *sampler.epoch_buffers())
 
     def epoch_bce_sampled(self, sampler, epoch, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
         """Epoch number `epoch` of a BceDeviceSampler drawn and trained as ONE native call (spex_lightgcn_epoch_bce_sampled_f32): one
         sampler launch into the sampler's epoch buffers, then epoch_bce's loop over them — the state after it is that of
         epoch_bce(*sampler.draw(epoch), ...).  loss_full / loss_ragged, max_steps, keep_prob, drop_seed as in epoch_bce."""
-        d, tables, loop, bufs = self._sampled_bce_args(sampler, batch_size, max_steps, keep_prob, "epoch_bce_sampled")
+        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, "epoch_bce_sampled")
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
         self._clear_row_counts()
         _launch(self.E0.device, "spex_lightgcn_epoch_bce_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
                 int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
-        self.t = d.t
-        _bump(self.E0, self.m, self.v, loss_full, loss_ragged, self.E0_16, *sampler.epoch_buffers())
-        self._after_desc(d)
+        self._after_call(d, loss_full, loss_ragged, *sampler.epoch_buffers())
 
     def train_bce_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
         """n_epochs sampled BCE epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
@@ -713,13 +675,11 @@ class LightGCNStepper:
             raise ValueError("LightGCNStepper.train_bce_sampled: loss_epochs needs to be a contiguous fp32 device tensor of 2 n_epochs elements")
         if int(n_epochs) == 0:
             return
-        d, tables, loop, bufs = self._sampled_bce_args(sampler, batch_size, max_steps, keep_prob, "train_bce_sampled")
+        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, "train_bce_sampled")
         self._clear_row_counts()
         _launch(self.E0.device, "spex_lightgcn_train_bce_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
                 *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
-        self.t = d.t
-        _bump(self.E0, self.m, self.v, loss_epochs, self.E0_16, *sampler.epoch_buffers())
-        self._after_desc(d)
+        self._after_call(d, loss_epochs, *sampler.epoch_buffers())
 
 
 def dataloader_epoch_order(n):
@@ -877,7 +837,7 @@ def _train_epochs_bce_sampled(stepper, sampler, n_epochs, batch_size, edge_dropo
     keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
     if stream is not None and stepper.graph_t is stepper.graph:
         raise ValueError("train_epochs(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation")
-    one_call = (after_epoch is None and n_epochs > 0 and sampler.n > 0 and stream in (None, "philox") and stepper._one_call_bce_shape_ok()
+    one_call = (after_epoch is None and n_epochs > 0 and sampler.n > 0 and stream in (None, "philox") and stepper._one_call_shape_ok()
                 and (stream is None or stepper.L >= 2))
     if one_call:
         acc = torch.zeros(n_epochs, 2, 1, dtype=torch.float32, device=stepper.E0.device)
@@ -923,7 +883,7 @@ def train_epoch(stepper, train_data, batch_size=256, resample=True, pause_gc=Tru
     if sampler is not None:
         if sampler.rowptr.device != dev:
             raise ValueError(f"train_epoch: the sampler's tables live on {sampler.rowptr.device}, the stepper on {dev}")
-        if (step_losses is None and stream in (None, "philox") and sampler.n > 0 and stepper._one_call_bce_shape_ok()
+        if (step_losses is None and stream in (None, "philox") and sampler.n > 0 and stepper._one_call_shape_ok()
                 and (stream is None or stepper.L >= 2)):
             acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
             with _gc_paused(pause_gc):
@@ -1046,6 +1006,14 @@ class BprDeviceSampler:
         return ops.sample_bpr_triples(self.rowptr, self.items, self.active, self.n_items, self.n if n is None else n, self.seed, epoch,
                                       by=self.by)
 
+    rows_per_sample = 3           # table rows per sample of the step that consumes the draw (LightGCNStepper._sampled_args)
+
+    def native_tables(self):
+        """The sampler's leading arguments of spex_lightgcn_epoch_bpr_sampled_f32 / spex_lightgcn_train_bpr_sampled_f32."""
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        return (vp(self.rowptr), vp(self.items), self.rowptr.numel() - 1, vp(self.active), self.active.numel(), self.n_items, self.n,
+                ops.BPR_SAMPLER_MODES[self.by], self.seed & 0xFFFFFFFFFFFFFFFF)
+
     def epoch_buffers(self):
         """Three int64 [n] device buffers, allocated once: what the native sampled epochs draw into (stream order keeps one epoch's
         reads ahead of the next epoch's draw)."""
@@ -1092,6 +1060,14 @@ class BceDeviceSampler:
         """Epoch `epoch`'s samples as three fresh device tensors: users int64 [n], items int64 [n], labels fp32 [n]."""
         return ops.sample_bce_epoch(self.rowptr, self.items, self.pos_user, self.pos_item, self.num_ng, self.n_items, self.seed, epoch)
 
+    rows_per_sample = 2
+
+    def native_tables(self):
+        """The sampler's leading arguments of spex_lightgcn_epoch_bce_sampled_f32 / spex_lightgcn_train_bce_sampled_f32."""
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        return (vp(self.rowptr), vp(self.items), self.rowptr.numel() - 1, vp(self.pos_user), vp(self.pos_item), self.n_pos, self.num_ng,
+                self.n_items, self.seed & 0xFFFFFFFFFFFFFFFF)
+
     def epoch_buffers(self):
         """(users int64 [n], items int64 [n], labels fp32 [n]) device buffers, allocated once: what the native sampled epochs draw into
         (stream order keeps one epoch's reads ahead of the next epoch's draw)."""
@@ -1119,7 +1095,7 @@ def train_epoch_bpr(stepper, triples_or_sampler, batch_size=2048, pause_gc=True,
     if stream is not None and stepper.graph_t is stepper.graph:
         raise ValueError("train_epoch_bpr(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation")
     dev = stepper.E0.device
-    native_ok = (step_losses is None and stream in (None, "philox") and stepper._one_call_bpr_shape_ok()
+    native_ok = (step_losses is None and stream in (None, "philox") and stepper._one_call_shape_ok()
                  and (stream is None or stepper.L >= 2))
     if sampler is not None and sampler.n > 0 and native_ok:
         acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
@@ -1180,7 +1156,7 @@ def _train_epochs_bpr_sampled(stepper, sampler, n_epochs, batch_size, edge_dropo
     keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
     if stream is not None and stepper.graph_t is stepper.graph:
         raise ValueError("train_epochs_bpr(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation")
-    one_call = (after_epoch is None and n_epochs > 0 and sampler.n > 0 and stream in (None, "philox") and stepper._one_call_bpr_shape_ok()
+    one_call = (after_epoch is None and n_epochs > 0 and sampler.n > 0 and stream in (None, "philox") and stepper._one_call_shape_ok()
                 and (stream is None or stepper.L >= 2))
     if one_call:
         acc = torch.zeros(n_epochs, 2, 1, dtype=torch.float32, device=stepper.E0.device)

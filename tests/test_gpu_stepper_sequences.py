@@ -459,3 +459,39 @@ def test_deterministic_changing_batch_size_is_bit_reproducible(G, d, L):
         st, full, ragged = run_alternating(G, d, L, True)
         runs.append(end_state(st) + (full, ragged))
     assert all(torch.equal(x, y) for x, y in zip(*runs))
+
+
+# ------------------------------------------------------------------------------------------ 8. five layers: both ping-pongs at length
+@pytest.fixture(scope="module")
+def hub_handles(G):
+    return handles(G)
+
+
+@pytest.mark.parametrize("kind,form", [(kind, form) for kind in ("bce", "bpr") for form in ("fast", "deterministic", "frontier")])
+def test_one_call_steps_at_five_layers_equal_the_launch_by_launch_steps(hub_handles, kind, form):
+    """L = 5, d = 64 on the hub graph: the first depth at which the one-call step's forward visits ws_fwd[0], [1], [0], [1] and its
+    pull products ws_bwd[1], [2], [1].  Three steps (T = 17; BPR: 17, 768 — the dense form, except on the frontier stepper — , 17) from
+    one state through the one-call step and through the launch-by-launch step, fast, deterministic and frontier=True: the loss sum,
+    E0, m and v within the bounds of test_gpu_wide_step.py::test_one_call_step_equals_the_launch_by_launch_step (loss sum, E0 and m
+    2e-5 relative, v 4e-5).  Deterministic: two one-call runs are bit-identical."""
+    from spex_amd.trainer import LightGCNStepper
+    g, gt = hub_handles
+    batch = bce_batch if kind == "bce" else bpr_batch
+    seq = [batch(800 + k, T) for k, T in enumerate((17, 768, 17) if kind == "bpr" else (17, 17, 17))]
+    runs = []
+    for one_call in (True, True, False) if form == "deterministic" else (True, False):
+        st = LightGCNStepper(g, t(table(64)), N_U, n_layers=5, lr=LR, graph_t=gt, deterministic=form == "deterministic", weight_decay=WD,
+                             frontier=form == "frontier")
+        acc = torch.zeros(1, device=DEV)
+        for _, arrs in seq:
+            a, b, c = (t(x) for x in arrs)
+            assert (st._one_call_bpr_ok if kind == "bpr" else st._one_call_ok)(a, b, c)
+            (st.step_bpr_exact if kind == "bpr" else st.step_bce)(a, b, c, loss_acc=acc, batch_rows_only=one_call)
+        assert st.t == 3
+        runs.append((st.E0.cpu().numpy(), st.m.cpu().numpy(), st.v.cpu().numpy(), acc.item()))
+    one, launches = runs[0], runs[-1]
+    if form == "deterministic":
+        assert all(np.array_equal(x, y) for x, y in zip(one[:3], runs[1][:3])) and one[3] == runs[1][3]
+    figs = (abs(one[3] - launches[3]) / abs(launches[3]), rel_err(one[0], launches[0]), rel_err(one[1], launches[1]), rel_err(one[2], launches[2]))
+    print(f"L=5 {kind} {form}: loss {figs[0]:.2e} E0 {figs[1]:.2e} m {figs[2]:.2e} v {figs[3]:.2e}")
+    assert figs[0] <= 2e-5 and figs[1] <= 2e-5 and figs[2] <= 2e-5 and figs[3] <= 4e-5
