@@ -9,8 +9,10 @@ synchronisation and no Python between kernels beyond the ctypes calls (capturabl
     bpr step    (north-star extension): L x SpMM (mean fused)  ->  fused gather + dot + sigmoid + SGD over triples,
                                         scores read from the propagated table, updates applied to E0
 """
+import collections
 import contextlib
 import ctypes
+import functools
 import gc
 import os
 import threading
@@ -33,6 +35,13 @@ def _batch_ok(users, items, labels, min_len=1):
     return (users.is_cuda and items.is_cuda and labels.is_cuda and users.dtype == torch.int64 and items.dtype == torch.int64
             and labels.dtype == torch.float32 and users.is_contiguous() and items.is_contiguous() and labels.is_contiguous()
             and users.numel() == items.numel() == labels.numel() >= min_len)
+
+
+def _check_loss_epochs(who, loss_epochs, n_epochs):
+    """The loss buffer of a multi-epoch native call (`who`: the method the caller used): fp32, contiguous, on the device, 2 per epoch."""
+    if not (loss_epochs.is_cuda and loss_epochs.dtype == torch.float32 and loss_epochs.is_contiguous()
+            and loss_epochs.numel() >= 2 * int(n_epochs) and int(n_epochs) >= 0):
+        raise ValueError(f"{who}: loss_epochs needs to be a contiguous fp32 device tensor of 2 n_epochs elements")
 
 
 def _drop_desc(stepper):
@@ -491,15 +500,48 @@ class LightGCNStepper:
         samples [k B, (k+1) B) through the one-call step, nothing but its launches issued by the host.  loss_full / loss_ragged:
         1-element device accumulators (loss sums of the full batches / of a shorter last one).  keep_prob < 1: the in-kernel sampled
         edge mask, a fresh one per step (seed (drop_seed << 32) | step — trainer.edge_dropout_mask's "philox" stream)."""
-        if not self._one_call_ok(users[:1], items[:1], labels[:1]):
-            raise ValueError("LightGCNStepper.epoch_bce: needs an embedding width of 64, 128 or 256 and contiguous int64 / fp32 device tensors")
-        self._check_epoch_dropout("epoch_bce", keep_prob)
-        d = self._prepare_desc(min(int(batch_size), users.numel()))
+        self._epoch("bce", users, items, labels, batch_size, loss_full, loss_ragged, max_steps, keep_prob, drop_seed)
+
+    # -- the native epochs of both kinds of exact step ("bce" / "bpr"): one implementation each of the epoch over device tensors, the
+    #    sampled epoch and the multi-epoch sampled run; the public methods name the kind
+    def _native_call(self, kind, name, d, args, written):
+        """One native epoch call of `kind` on descriptor d.  The BCE calls clear the BPR row counts first (_clear_row_counts: they advance
+        t without them); the BPR calls write grad_E0."""
+        if kind == "bce":
+            self._clear_row_counts()
+        _launch(self.E0.device, name, ctypes.byref(d), *args)
+        self._after_call(d, *((self.grad_E0,) if kind == "bpr" else ()), *written)
+
+    def _epoch(self, kind, users, b, c, batch_size, loss_full, loss_ragged, max_steps, keep_prob, drop_seed):
+        """epoch_bce / epoch_bpr."""
+        bpr = kind == "bpr"
+        if not (self._one_call_bpr_ok if bpr else self._one_call_ok)(users[:1], b[:1], c[:1]):
+            raise ValueError(f"LightGCNStepper.epoch_{kind}: needs an embedding width of 64, 128 or 256 and contiguous int64 "
+                             f"{'' if bpr else '/ fp32 '}device tensors")
+        self._check_epoch_dropout(f"epoch_{kind}", keep_prob)
+        d = self._prepare_desc(min(int(batch_size), users.numel()), 3 if bpr else 2)
         vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        self._clear_row_counts()
-        _launch(self.E0.device, "spex_lightgcn_epoch_bce_f32", ctypes.byref(d), vp(users), vp(items), vp(labels), users.numel(), int(batch_size),
-                -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
-        self._after_call(d, loss_full, loss_ragged)
+        self._native_call(kind, f"spex_lightgcn_epoch_{kind}_f32", d,
+                          (vp(users), vp(b), vp(c), users.numel(), int(batch_size), -1 if max_steps is None else int(max_steps), float(keep_prob),
+                           int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged)), (loss_full, loss_ragged))
+
+    def _epoch_sampled(self, kind, sampler, epoch, batch_size, loss_full, loss_ragged, max_steps, keep_prob, drop_seed):
+        """epoch_bce_sampled / epoch_bpr_sampled."""
+        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, f"epoch_{kind}_sampled")
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._native_call(kind, f"spex_lightgcn_epoch_{kind}_sampled_f32", d,
+                          (*tables, int(epoch) & 0xFFFFFFFF, *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged)),
+                          (loss_full, loss_ragged, *sampler.epoch_buffers()))
+
+    def _train_sampled(self, kind, sampler, n_epochs, batch_size, loss_epochs, max_steps, keep_prob, drop_seed, first_epoch):
+        """train_bce_sampled / train_bpr_sampled."""
+        _check_loss_epochs(f"LightGCNStepper.train_{kind}_sampled", loss_epochs, n_epochs)
+        if int(n_epochs) == 0:
+            return
+        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, f"train_{kind}_sampled")
+        self._native_call(kind, f"spex_lightgcn_train_{kind}_sampled_f32", d,
+                          (*tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs), *loop, int(drop_seed) & 0xFFFFFFFF, *bufs,
+                           ctypes.c_void_p(loss_epochs.data_ptr())), (loss_epochs, *sampler.epoch_buffers()))
 
     def backward_from_batch_rows(self, users, items):
         """grad_E0 from g_out (non-zero on the batch's rows only).  The first product of the backward pass, A^T g, touches
@@ -608,14 +650,7 @@ class LightGCNStepper:
     def epoch_bpr(self, users, pos, neg, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
         """A whole epoch of pre-drawn, device-resident triples as ONE native call (spex_lightgcn_epoch_bpr_f32): batch k = triples
         [k T, (k+1) T) through the one-call exact BPR step.  loss_full / loss_ragged, keep_prob and drop_seed as in epoch_bce."""
-        if not self._one_call_bpr_ok(users[:1], pos[:1], neg[:1]):
-            raise ValueError("LightGCNStepper.epoch_bpr: needs an embedding width of 64, 128 or 256 and contiguous int64 device tensors")
-        self._check_epoch_dropout("epoch_bpr", keep_prob)
-        d = self._prepare_desc(min(int(batch_size), users.numel()), 3)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        _launch(self.E0.device, "spex_lightgcn_epoch_bpr_f32", ctypes.byref(d), vp(users), vp(pos), vp(neg), users.numel(), int(batch_size),
-                -1 if max_steps is None else int(max_steps), float(keep_prob), int(drop_seed) & 0xFFFFFFFF, vp(loss_full), vp(loss_ragged))
-        self._after_call(d, self.grad_E0, loss_full, loss_ragged)
+        self._epoch("bpr", users, pos, neg, batch_size, loss_full, loss_ragged, max_steps, keep_prob, drop_seed)
 
     # -- sampled epochs: the epoch drawn on the device by the same native call that trains on it (BprDeviceSampler: triples;
     #    BceDeviceSampler: negatives, labels and the shuffle)
@@ -633,53 +668,27 @@ class LightGCNStepper:
         """Epoch number `epoch` of a BprDeviceSampler drawn and trained as ONE native call (spex_lightgcn_epoch_bpr_sampled_f32): one
         sampler launch into the sampler's index buffers, then epoch_bpr's loop over them — the state after it is that of
         epoch_bpr(*sampler.draw(epoch), ...).  loss_full / loss_ragged, max_steps, keep_prob, drop_seed as in epoch_bpr."""
-        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, "epoch_bpr_sampled")
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        _launch(self.E0.device, "spex_lightgcn_epoch_bpr_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
-                int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
-        self._after_call(d, self.grad_E0, loss_full, loss_ragged, *sampler.epoch_buffers())
+        self._epoch_sampled("bpr", sampler, epoch, batch_size, loss_full, loss_ragged, max_steps, keep_prob, drop_seed)
 
     def train_bpr_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
         """n_epochs sampled epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
         (spex_lightgcn_train_bpr_sampled_f32): no host thread, no synchronisation.  loss_epochs: a contiguous fp32 device tensor of
         2 n_epochs elements, zeroed by the caller — epoch e's loss sums of the full batches / of the ragged last one accumulate into
         elements 2 e and 2 e + 1.  Under edge dropout epoch number E runs with the mask seed bpr_epoch_drop_seed(drop_seed, E)."""
-        if not (loss_epochs.is_cuda and loss_epochs.dtype == torch.float32 and loss_epochs.is_contiguous()
-                and loss_epochs.numel() >= 2 * int(n_epochs) and int(n_epochs) >= 0):
-            raise ValueError("LightGCNStepper.train_bpr_sampled: loss_epochs needs to be a contiguous fp32 device tensor of 2 n_epochs elements")
-        if int(n_epochs) == 0:
-            return
-        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, "train_bpr_sampled")
-        _launch(self.E0.device, "spex_lightgcn_train_bpr_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
-                *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
-        self._after_call(d, self.grad_E0, loss_epochs, *sampler.epoch_buffers())
+        self._train_sampled("bpr", sampler, n_epochs, batch_size, loss_epochs, max_steps, keep_prob, drop_seed, first_epoch)
 
     def epoch_bce_sampled(self, sampler, epoch, batch_size, loss_full, loss_ragged, max_steps=None, keep_prob=1.0, drop_seed=0):
         """Epoch number `epoch` of a BceDeviceSampler drawn and trained as ONE native call (spex_lightgcn_epoch_bce_sampled_f32): one
         sampler launch into the sampler's epoch buffers, then epoch_bce's loop over them — the state after it is that of
         epoch_bce(*sampler.draw(epoch), ...).  loss_full / loss_ragged, max_steps, keep_prob, drop_seed as in epoch_bce."""
-        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, "epoch_bce_sampled")
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())
-        self._clear_row_counts()
-        _launch(self.E0.device, "spex_lightgcn_epoch_bce_sampled_f32", ctypes.byref(d), *tables, int(epoch) & 0xFFFFFFFF, *loop,
-                int(drop_seed) & 0xFFFFFFFF, *bufs, vp(loss_full), vp(loss_ragged))
-        self._after_call(d, loss_full, loss_ragged, *sampler.epoch_buffers())
+        self._epoch_sampled("bce", sampler, epoch, batch_size, loss_full, loss_ragged, max_steps, keep_prob, drop_seed)
 
     def train_bce_sampled(self, sampler, n_epochs, batch_size, loss_epochs, max_steps=None, keep_prob=1.0, drop_seed=0, first_epoch=0):
         """n_epochs sampled BCE epochs (numbers first_epoch .. first_epoch + n_epochs - 1) queued back to back by ONE native call
         (spex_lightgcn_train_bce_sampled_f32): no host thread, no synchronisation.  loss_epochs: a contiguous fp32 device tensor of
         2 n_epochs elements, zeroed by the caller — epoch e's loss sums of the full batches / of the ragged last one accumulate into
         elements 2 e and 2 e + 1.  Under edge dropout epoch number E runs with the mask seed bpr_epoch_drop_seed(drop_seed, E)."""
-        if not (loss_epochs.is_cuda and loss_epochs.dtype == torch.float32 and loss_epochs.is_contiguous()
-                and loss_epochs.numel() >= 2 * int(n_epochs) and int(n_epochs) >= 0):
-            raise ValueError("LightGCNStepper.train_bce_sampled: loss_epochs needs to be a contiguous fp32 device tensor of 2 n_epochs elements")
-        if int(n_epochs) == 0:
-            return
-        d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, keep_prob, "train_bce_sampled")
-        self._clear_row_counts()
-        _launch(self.E0.device, "spex_lightgcn_train_bce_sampled_f32", ctypes.byref(d), *tables, int(first_epoch) & 0xFFFFFFFF, int(n_epochs),
-                *loop, int(drop_seed) & 0xFFFFFFFF, *bufs, ctypes.c_void_p(loss_epochs.data_ptr()))
-        self._after_call(d, loss_epochs, *sampler.epoch_buffers())
+        self._train_sampled("bce", sampler, n_epochs, batch_size, loss_epochs, max_steps, keep_prob, drop_seed, first_epoch)
 
 
 def dataloader_epoch_order(n):
@@ -738,7 +747,7 @@ def epoch_arrays(train_data, resample=True):
     return train_data.users_fill[order], train_data.items_fill[order], train_data.labels_fill_np[order]
 
 
-# ---- what the three epoch drivers share
+# ---- what the epoch drivers of the four families (BCE, BPR, NGCF, dual-task) share: DESIGN.md 4.22
 def _edge_dropout_args(edge_dropout):
     """(keep_prob, stream, seed) of an epoch's edge_dropout: None (no dropout: (1.0, None, 0)) or (keep_prob, stream[, seed])."""
     if edge_dropout is None:
@@ -812,6 +821,125 @@ def _run_epochs(n_epochs, prepare, train, after_epoch, overlap):
     return totals
 
 
+def _samples_done(n, batch_size, max_steps):
+    """How many of an epoch's n samples the first max_steps batches (None: all) cover."""
+    return min(n, len(_batch_starts(n, batch_size, max_steps)) * batch_size)
+
+
+def _refuse_symmetric_handle(who, stepper, stream, why=""):
+    """Edge dropout (stream not None) on a stepper whose graph_t is its graph: refused in the name of the function the caller used."""
+    if stream is not None and stepper.graph_t is stepper.graph:
+        raise ValueError(f"{who}(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation{why}")
+
+
+def _is_device_triples(x):
+    return isinstance(x, (tuple, list)) and len(x) == 3 and all(torch.is_tensor(t) for t in x)
+
+
+def _triples_to_device(dev, triples):
+    """train_epoch_bpr's pre-drawn triples on the stepper's device as contiguous int64: device tensors used where they are, host arrays
+    uploaded."""
+    if _is_device_triples(triples):
+        return tuple(t.to(device=dev, dtype=torch.int64).contiguous() for t in triples)
+    return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev) for a in triples)
+
+
+def _lightgcn_native_ok(batch_ok, stepper, stream, tensors):
+    """A native LightGCN epoch applies: no host-drawn ("reference") mask, the one-call step does — for the stepper alone (tensors None:
+    a sampled epoch) or, by its method `batch_ok`, for these tensors —, and two layers under dropout."""
+    return (stream in (None, "philox") and (stepper._one_call_shape_ok() if tensors is None else getattr(stepper, batch_ok)(*(t[:1] for t in tensors)))
+            and (stream is None or stepper.L >= 2))
+
+
+def _ngcf_native_ok(stepper, stream, tensors):
+    """A native NGCF epoch applies: the single-layer model, tensors (if any) the one-call step takes, counter-based message dropout."""
+    return (stepper.L == 1 and (tensors is None or stepper._one_call_ok(*(t[:1] for t in tensors)))
+            and not (stepper._reference_stream and stepper.model.mess_dropout[0] > 0))
+
+
+# What differs between the three single-task families, for _train_epoch and _train_epochs_sampled.  who: the per-epoch front end;
+# tables: the sampler attribute whose device the front end checks itself (None: left to the stepper); to_device(dev, source): host
+# arrays / pre-drawn tensors as three device tensors; native_ok: above; epoch / sampled / train / step: the stepper's methods, by name
+# (looked up on the instance); step_kw: the step's keywords; edge_dropout: whether the native calls take keep_prob and drop_seed.
+_Family = collections.namedtuple("_Family", "who tables to_device native_ok epoch sampled train step step_kw edge_dropout")
+_BCE = _Family("train_epoch", "rowptr", lambda dev, arrays: _upload(dev, *arrays), functools.partial(_lightgcn_native_ok, "_one_call_ok"),
+               "epoch_bce", "epoch_bce_sampled", "train_bce_sampled", "step_bce", {"batch_rows_only": True}, True)
+_BPR = _Family("train_epoch_bpr", None, _triples_to_device, functools.partial(_lightgcn_native_ok, "_one_call_bpr_ok"),
+               "epoch_bpr", "epoch_bpr_sampled", "train_bpr_sampled", "step_bpr_exact", {"batch_rows_only": True}, True)
+_NGCF = _Family("train_epoch_ngcf", "pop", lambda dev, arrays: _upload(dev, *arrays), _ngcf_native_ok,
+                "epoch", "epoch_sampled", "train_sampled", "step", {}, False)
+
+
+def _train_epoch(fam, stepper, sampler, source, batch_size, pause_gc, edge_dropout, max_steps, step_losses, callbacks, epoch):
+    """One epoch of family `fam` from a device sampler (epoch number `epoch`) or, sampler None, from `source` (fam.to_device), in this
+    order: the sampler's native sampled epoch; the native epoch over the drawn / uploaded tensors; the step loop.  step_losses and
+    callbacks bar both native forms, fam.native_ok the rest.  Returns the epoch's sum of per-batch mean losses (device tensor)."""
+    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
+    dev = stepper.E0.device
+    drop = {"keep_prob": keep_prob, "drop_seed": seed} if fam.edge_dropout else {}
+    native_ok = lambda n, tensors: not callbacks and step_losses is None and n > 0 and fam.native_ok(stepper, stream, tensors)
+    if sampler is not None and fam.tables is not None and getattr(sampler, fam.tables).device != dev:
+        raise ValueError(f"{fam.who}: the sampler's tables live on {getattr(sampler, fam.tables).device}, the stepper on {dev}")
+    acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)     # loss sums of the full batches / of the ragged last one
+    if sampler is not None and native_ok(sampler.n, None):
+        with _gc_paused(pause_gc):
+            getattr(stepper, fam.sampled)(sampler, epoch, batch_size, acc[0], acc[1], max_steps=max_steps, **drop)
+        return _sum_of_batch_means(acc, _samples_done(sampler.n, batch_size, max_steps), batch_size)
+    a, b, c = sampler.draw(epoch) if sampler is not None else fam.to_device(dev, source)
+    n = a.numel()
+    with _gc_paused(pause_gc):
+        # the whole epoch as ONE native call where nothing has to happen on the host between two steps: no per-step loss read-back, no
+        # callback, no host-drawn mask (the reference-stream dropout mask is drawn on the CPU per step; the sampled one is keyed in the kernel)
+        if native_ok(n, (a, b, c)):
+            getattr(stepper, fam.epoch)(a, b, c, batch_size, acc[0], acc[1], max_steps=max_steps, **drop)
+        else:
+            step = getattr(stepper, fam.step)
+            try:
+                for k, s in enumerate(_batch_starts(n, batch_size, max_steps)):
+                    if callbacks and k in callbacks:
+                        callbacks[k]()
+                    e = min(s + batch_size, n)
+                    slot = acc[0] if e - s == batch_size else acc[1]
+                    tmp = torch.zeros(1, dtype=torch.float32, device=dev) if step_losses is not None else None
+                    if stream is not None:
+                        stepper.set_edge_dropout(edge_dropout_mask(stepper.graph, keep_prob, stream, seed, k + 1))
+                    step(a[s:e], b[s:e], c[s:e], loss_acc=slot if tmp is None else tmp, **fam.step_kw)
+                    if tmp is not None:
+                        step_losses.append(tmp.item() / (e - s))
+                        slot += tmp
+            finally:
+                if stream is not None:
+                    stepper.set_edge_dropout(None)
+    return _sum_of_batch_means(acc, _samples_done(n, batch_size, max_steps), batch_size)
+
+
+def _train_epochs_sampled(who, fam, stepper, sampler, n_epochs, batch_size, edge_dropout, after_epoch, max_steps, first_epoch, one_epoch):
+    """The train_epochs* front end `who` over a device sampler, epochs first_epoch .. first_epoch + n_epochs - 1.  Where the family
+    offers a whole-run call (fam.train; fam None: none) and nothing runs between epochs, ONE native call and one synchronisation at its
+    end.  Otherwise one_epoch(e, epoch e's edge_dropout, e + 1 or None behind the last) per epoch, then after_epoch(e - first_epoch,
+    total).  Returns the per-epoch totals: floats from the whole-run call, one_epoch's results from the loop."""
+    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
+    if fam is not None:
+        _refuse_symmetric_handle(who, stepper, stream)
+        if after_epoch is None and n_epochs > 0 and sampler.n > 0 and fam.native_ok(stepper, stream, None):
+            acc = torch.zeros(n_epochs, 2, 1, dtype=torch.float32, device=stepper.E0.device)
+            drop = {"keep_prob": keep_prob, "drop_seed": seed} if fam.edge_dropout else {}
+            with _gc_paused():
+                getattr(stepper, fam.train)(sampler, n_epochs, batch_size, acc, max_steps=max_steps, first_epoch=first_epoch, **drop)
+            n_done = _samples_done(sampler.n, batch_size, max_steps)
+            host = acc.cpu()                                  # the run's one synchronisation
+            return [float(_sum_of_batch_means(host[e], n_done, batch_size)) for e in range(n_epochs)]
+    totals, end = [], first_epoch + n_epochs
+    for e in range(first_epoch, end):
+        # the philox stream is reseeded per epoch; the reference stream (host-drawn masks) keeps its seed
+        drop = None if stream is None else (keep_prob, stream, bpr_epoch_drop_seed(seed, e) if stream == "philox" else seed)
+        total = one_epoch(e, drop, e + 1 if e + 1 < end else None)
+        totals.append(total)
+        if after_epoch is not None:
+            after_epoch(e - first_epoch, total)
+    return totals
+
+
 def train_epochs(stepper, train_data, n_epochs, batch_size=256, edge_dropout=None, after_epoch=None, max_steps=None, first_epoch=0):
     """n_epochs x train_epoch with the NEXT epoch's negatives and shuffle prepared on a second host thread while the GPU trains the
     current one (an Epinion2 epoch: 0.14 s of sampling beside 0.38 s of steps; the NumPy / torch generators drawn in the order of a
@@ -825,35 +953,13 @@ def train_epochs(stepper, train_data, n_epochs, batch_size=256, edge_dropout=Non
     at its end; with it, one native call per epoch.  Under edge dropout epoch e runs with the mask seed bpr_epoch_drop_seed(seed, e)
     either way."""
     if isinstance(train_data, BceDeviceSampler):
-        return _train_epochs_bce_sampled(stepper, train_data, n_epochs, batch_size, edge_dropout, after_epoch, max_steps, int(first_epoch))
+        one_epoch = lambda e, drop, _: train_epoch(stepper, train_data, batch_size=batch_size, edge_dropout=drop, max_steps=max_steps, epoch=e)
+        return [float(t) for t in _train_epochs_sampled("train_epochs", _BCE, stepper, train_data, n_epochs, batch_size, edge_dropout, after_epoch,
+                                                       max_steps, int(first_epoch), one_epoch)]
     totals = _run_epochs(n_epochs, lambda: epoch_arrays(train_data),
                          lambda arrays: train_epoch(stepper, train_data, batch_size=batch_size, edge_dropout=edge_dropout, arrays=arrays,
                                                     max_steps=max_steps),
                          after_epoch, overlap=_edge_dropout_args(edge_dropout)[1] != "reference")
-    return [float(t) for t in totals]
-
-
-def _train_epochs_bce_sampled(stepper, sampler, n_epochs, batch_size, edge_dropout, after_epoch, max_steps, first_epoch):
-    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
-    if stream is not None and stepper.graph_t is stepper.graph:
-        raise ValueError("train_epochs(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation")
-    one_call = (after_epoch is None and n_epochs > 0 and sampler.n > 0 and stream in (None, "philox") and stepper._one_call_shape_ok()
-                and (stream is None or stepper.L >= 2))
-    if one_call:
-        acc = torch.zeros(n_epochs, 2, 1, dtype=torch.float32, device=stepper.E0.device)
-        with _gc_paused():
-            stepper.train_bce_sampled(sampler, n_epochs, batch_size, acc, max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed,
-                                      first_epoch=first_epoch)
-        n_done = min(sampler.n, len(_batch_starts(sampler.n, batch_size, max_steps)) * batch_size)
-        host = acc.cpu()                                  # the run's one synchronisation
-        return [float(_sum_of_batch_means(host[e], n_done, batch_size)) for e in range(n_epochs)]
-    totals = []
-    for e in range(first_epoch, first_epoch + n_epochs):
-        drop = None if stream is None else (keep_prob, stream, bpr_epoch_drop_seed(seed, e) if stream == "philox" else seed)
-        total = train_epoch(stepper, sampler, batch_size=batch_size, edge_dropout=drop, max_steps=max_steps, epoch=e)
-        totals.append(total)
-        if after_epoch is not None:
-            after_epoch(e - first_epoch, total)
     return [float(t) for t in totals]
 
 
@@ -875,49 +981,9 @@ def train_epoch(stepper, train_data, batch_size=256, resample=True, pause_gc=Tru
     sampler = train_data if isinstance(train_data, BceDeviceSampler) else None
     if sampler is None:
         arrays = arrays if arrays is not None else epoch_arrays(train_data, resample)
-    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
-    if stream is not None and stepper.graph_t is stepper.graph:
-        raise ValueError("train_epoch(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id "
-                         "permutation (LightGCN._transposed()): a masked adjacency is not symmetric")
-    dev = stepper.E0.device
-    if sampler is not None:
-        if sampler.rowptr.device != dev:
-            raise ValueError(f"train_epoch: the sampler's tables live on {sampler.rowptr.device}, the stepper on {dev}")
-        if (step_losses is None and stream in (None, "philox") and sampler.n > 0 and stepper._one_call_shape_ok()
-                and (stream is None or stepper.L >= 2)):
-            acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
-            with _gc_paused(pause_gc):
-                stepper.epoch_bce_sampled(sampler, epoch, batch_size, acc[0], acc[1], max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed)
-            return _sum_of_batch_means(acc, min(sampler.n, len(_batch_starts(sampler.n, batch_size, max_steps)) * batch_size), batch_size)
-        users, items, labels = sampler.draw(epoch)
-    else:
-        users, items, labels = _upload(dev, *arrays)
-    n = users.numel()
-    starts = _batch_starts(n, batch_size, max_steps)
-    acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)     # loss sums of the full batches / of the ragged last one
-    # the whole epoch as ONE native call where nothing has to happen on the host between two steps: no per-step loss read-back, no
-    # host-drawn mask (the reference-stream dropout mask is drawn on the CPU per step; the sampled one is keyed in the kernel)
-    native = (step_losses is None and stream in (None, "philox") and n > 0 and stepper._one_call_ok(users[:1], items[:1], labels[:1])
-              and (stream is None or stepper.L >= 2))
-    with _gc_paused(pause_gc):
-        if native:
-            stepper.epoch_bce(users, items, labels, batch_size, acc[0], acc[1], max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed)
-        else:
-            try:
-                for k, s in enumerate(starts):
-                    e = min(s + batch_size, n)
-                    slot = acc[0] if e - s == batch_size else acc[1]
-                    tmp = torch.zeros(1, dtype=torch.float32, device=dev) if step_losses is not None else None
-                    if stream is not None:
-                        stepper.set_edge_dropout(edge_dropout_mask(stepper.graph, keep_prob, stream, seed, k + 1))
-                    stepper.step_bce(users[s:e], items[s:e], labels[s:e], loss_acc=slot if tmp is None else tmp, batch_rows_only=True)
-                    if tmp is not None:
-                        step_losses.append(tmp.item() / (e - s))
-                        slot += tmp
-            finally:
-                if stream is not None:
-                    stepper.set_edge_dropout(None)
-    return _sum_of_batch_means(acc, min(n, len(starts) * batch_size), batch_size)
+    _refuse_symmetric_handle("train_epoch", stepper, _edge_dropout_args(edge_dropout)[1],
+                             " (LightGCN._transposed()): a masked adjacency is not symmetric")
+    return _train_epoch(_BCE, stepper, sampler, arrays, batch_size, pause_gc, edge_dropout, max_steps, step_losses, None, epoch)
 
 
 def bpr_epoch_triples(train_pairs, n_users, n_items, rng):
@@ -1076,10 +1142,6 @@ class BceDeviceSampler:
         return self._buffers
 
 
-def _is_device_triples(x):
-    return isinstance(x, (tuple, list)) and len(x) == 3 and all(torch.is_tensor(t) for t in x)
-
-
 def train_epoch_bpr(stepper, triples_or_sampler, batch_size=2048, pause_gc=True, edge_dropout=None, max_steps=None, step_losses=None,
                     epoch=0):
     """One epoch of exact BPR training (upstream LightGCN: BPR through the propagation, L2 on the batch's E0 rows, Adam) over pre-drawn
@@ -1090,48 +1152,9 @@ def train_epoch_bpr(stepper, triples_or_sampler, batch_size=2048, pause_gc=True,
     Also: a tuple of three device tensors (used where they are), or a BprDeviceSampler — epoch number `epoch` is then drawn AND trained
     in one native call (LightGCNStepper.epoch_bpr_sampled), or drawn by sampler.draw(epoch) for the step-by-step loop."""
     sampler = triples_or_sampler if isinstance(triples_or_sampler, BprDeviceSampler) else None
-    arrays = triples_or_sampler() if callable(triples_or_sampler) else triples_or_sampler
-    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
-    if stream is not None and stepper.graph_t is stepper.graph:
-        raise ValueError("train_epoch_bpr(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation")
-    dev = stepper.E0.device
-    native_ok = (step_losses is None and stream in (None, "philox") and stepper._one_call_shape_ok()
-                 and (stream is None or stepper.L >= 2))
-    if sampler is not None and sampler.n > 0 and native_ok:
-        acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
-        with _gc_paused(pause_gc):
-            stepper.epoch_bpr_sampled(sampler, epoch, batch_size, acc[0], acc[1], max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed)
-        return _sum_of_batch_means(acc, min(sampler.n, len(_batch_starts(sampler.n, batch_size, max_steps)) * batch_size), batch_size)
-    if sampler is not None:
-        users, pos, neg = sampler.draw(epoch)
-    elif _is_device_triples(arrays):
-        users, pos, neg = (t.to(device=dev, dtype=torch.int64).contiguous() for t in arrays)
-    else:
-        users, pos, neg = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev) for a in arrays)
-    n = users.numel()
-    starts = _batch_starts(n, batch_size, max_steps)
-    acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
-    native = (step_losses is None and stream in (None, "philox") and n > 0 and stepper._one_call_bpr_ok(users[:1], pos[:1], neg[:1])
-              and (stream is None or stepper.L >= 2))
-    with _gc_paused(pause_gc):
-        if native:
-            stepper.epoch_bpr(users, pos, neg, batch_size, acc[0], acc[1], max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed)
-        else:
-            try:
-                for k, s in enumerate(starts):
-                    e = min(s + batch_size, n)
-                    slot = acc[0] if e - s == batch_size else acc[1]
-                    tmp = torch.zeros(1, dtype=torch.float32, device=dev) if step_losses is not None else None
-                    if stream is not None:
-                        stepper.set_edge_dropout(edge_dropout_mask(stepper.graph, keep_prob, stream, seed, k + 1))
-                    stepper.step_bpr_exact(users[s:e], pos[s:e], neg[s:e], loss_acc=slot if tmp is None else tmp, batch_rows_only=True)
-                    if tmp is not None:
-                        step_losses.append(tmp.item() / (e - s))
-                        slot += tmp
-            finally:
-                if stream is not None:
-                    stepper.set_edge_dropout(None)
-    return _sum_of_batch_means(acc, min(n, len(starts) * batch_size), batch_size)
+    triples = triples_or_sampler() if callable(triples_or_sampler) else triples_or_sampler
+    _refuse_symmetric_handle("train_epoch_bpr", stepper, _edge_dropout_args(edge_dropout)[1])
+    return _train_epoch(_BPR, stepper, sampler, triples, batch_size, pause_gc, edge_dropout, max_steps, step_losses, None, epoch)
 
 
 def train_epochs_bpr(stepper, sampler, n_epochs, batch_size=2048, edge_dropout=None, after_epoch=None, max_steps=None, first_epoch=0):
@@ -1145,34 +1168,12 @@ def train_epochs_bpr(stepper, sampler, n_epochs, batch_size=2048, edge_dropout=N
     after_epoch the whole run is ONE native call (LightGCNStepper.train_bpr_sampled) and one synchronisation at its end; with it, one
     native call per epoch.  Under edge dropout epoch e runs with the mask seed bpr_epoch_drop_seed(seed, e) either way."""
     if isinstance(sampler, BprDeviceSampler):
-        return _train_epochs_bpr_sampled(stepper, sampler, n_epochs, batch_size, edge_dropout, after_epoch, max_steps, int(first_epoch))
+        one_epoch = lambda e, drop, _: train_epoch_bpr(stepper, sampler, batch_size=batch_size, edge_dropout=drop, max_steps=max_steps, epoch=e)
+        return [float(t) for t in _train_epochs_sampled("train_epochs_bpr", _BPR, stepper, sampler, n_epochs, batch_size, edge_dropout, after_epoch,
+                                                       max_steps, int(first_epoch), one_epoch)]
     totals = _run_epochs(n_epochs, sampler,
                          lambda arrays: train_epoch_bpr(stepper, arrays, batch_size=batch_size, edge_dropout=edge_dropout, max_steps=max_steps),
                          after_epoch, overlap=_edge_dropout_args(edge_dropout)[1] != "reference")
-    return [float(t) for t in totals]
-
-
-def _train_epochs_bpr_sampled(stepper, sampler, n_epochs, batch_size, edge_dropout, after_epoch, max_steps, first_epoch):
-    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
-    if stream is not None and stepper.graph_t is stepper.graph:
-        raise ValueError("train_epochs_bpr(edge_dropout=...): the stepper needs graph_t = the transposed handle with the edge-id permutation")
-    one_call = (after_epoch is None and n_epochs > 0 and sampler.n > 0 and stream in (None, "philox") and stepper._one_call_shape_ok()
-                and (stream is None or stepper.L >= 2))
-    if one_call:
-        acc = torch.zeros(n_epochs, 2, 1, dtype=torch.float32, device=stepper.E0.device)
-        with _gc_paused():
-            stepper.train_bpr_sampled(sampler, n_epochs, batch_size, acc, max_steps=max_steps, keep_prob=keep_prob, drop_seed=seed,
-                                      first_epoch=first_epoch)
-        n_done = min(sampler.n, len(_batch_starts(sampler.n, batch_size, max_steps)) * batch_size)
-        host = acc.cpu()                                  # the run's one synchronisation
-        return [float(_sum_of_batch_means(host[e], n_done, batch_size)) for e in range(n_epochs)]
-    totals = []
-    for e in range(first_epoch, first_epoch + n_epochs):
-        drop = None if stream is None else (keep_prob, stream, bpr_epoch_drop_seed(seed, e) if stream == "philox" else seed)
-        total = train_epoch_bpr(stepper, sampler, batch_size=batch_size, edge_dropout=drop, max_steps=max_steps, epoch=e)
-        totals.append(total)
-        if after_epoch is not None:
-            after_epoch(e - first_epoch, total)
     return [float(t) for t in totals]
 
 
@@ -1450,9 +1451,7 @@ class NGCFStepper:
         (spex_ngcf_train_bce_sampled_f32): no host thread, no synchronisation.  loss_epochs: a contiguous fp32 device tensor of 2 n_epochs
         elements, zeroed by the caller — epoch e's loss sums of the full batches / of the ragged last one accumulate into elements 2 e
         and 2 e + 1.  The message-dropout counter runs on across the epochs, as across per-epoch calls."""
-        if not (loss_epochs.is_cuda and loss_epochs.dtype == torch.float32 and loss_epochs.is_contiguous()
-                and loss_epochs.numel() >= 2 * int(n_epochs) and int(n_epochs) >= 0):
-            raise ValueError("NGCFStepper.train_sampled: loss_epochs needs to be a contiguous fp32 device tensor of 2 n_epochs elements")
+        _check_loss_epochs("NGCFStepper.train_sampled", loss_epochs, n_epochs)
         if int(n_epochs) == 0:
             return
         d, tables, loop, bufs = self._sampled_args(sampler, batch_size, max_steps, "train_sampled")
@@ -1549,34 +1548,14 @@ def train_epochs_ngcf(stepper, data, n_epochs, batch_size=None, after_epoch=None
     the device.  Single-layer stepper with the counter-based dropout stream and no after_epoch: the whole run is ONE native call
     (NGCFStepper.train_sampled) and one synchronisation at its end; otherwise one train_epoch_ngcf per epoch."""
     if isinstance(data, NgcfDeviceSampler):
-        return _train_epochs_ngcf_sampled(stepper, data, n_epochs, batch_size, after_epoch, int(first_epoch), max_steps)
+        bs = batch_size or data.batch_size
+        one_epoch = lambda e, _drop, _next: train_epoch_ngcf(stepper, data, batch_size=bs, max_steps=max_steps, epoch=e)
+        return [float(t) for t in _train_epochs_sampled("train_epochs_ngcf", _NGCF, stepper, data, n_epochs, bs, None, after_epoch, max_steps,
+                                                       int(first_epoch), one_epoch)]
     host_noise = stepper._reference_stream and any(p > 0 for p in stepper.model.mess_dropout[:stepper.L])
     totals = _run_epochs(n_epochs, lambda: epoch_arrays_ngcf(data),
                          lambda arrays: train_epoch_ngcf(stepper, data, batch_size=batch_size, arrays=arrays, max_steps=max_steps), after_epoch,
                          overlap=not host_noise)
-    return [float(t) for t in totals]
-
-
-def _ngcf_native_sampled_ok(stepper, sampler):
-    """The sampled native epoch applies: single-layer model, counter-based message dropout, something to draw."""
-    return stepper.L == 1 and sampler.n > 0 and not (stepper._reference_stream and stepper.model.mess_dropout[0] > 0)
-
-
-def _train_epochs_ngcf_sampled(stepper, sampler, n_epochs, batch_size, after_epoch, first_epoch, max_steps):
-    bs = batch_size or sampler.batch_size
-    if after_epoch is None and n_epochs > 0 and _ngcf_native_sampled_ok(stepper, sampler):
-        acc = torch.zeros(n_epochs, 2, 1, dtype=torch.float32, device=stepper.E0.device)
-        with _gc_paused():
-            stepper.train_sampled(sampler, n_epochs, bs, acc, max_steps=max_steps, first_epoch=first_epoch)
-        n_done = min(sampler.n, len(_batch_starts(sampler.n, bs, max_steps)) * bs)
-        host = acc.cpu()                                  # the run's one synchronisation
-        return [float(_sum_of_batch_means(host[e], n_done, bs)) for e in range(n_epochs)]
-    totals = []
-    for e in range(first_epoch, first_epoch + n_epochs):
-        total = train_epoch_ngcf(stepper, sampler, batch_size=bs, max_steps=max_steps, epoch=e)
-        totals.append(total)
-        if after_epoch is not None:
-            after_epoch(e - first_epoch, total)
     return [float(t) for t in totals]
 
 
@@ -1595,41 +1574,9 @@ def train_epoch_ngcf(stepper, data, batch_size=None, pause_gc=True, callbacks=No
     generator is touched for the samples; arrays is not read."""
     sampler = data if isinstance(data, NgcfDeviceSampler) else None
     bs = batch_size or data.batch_size
-    dev = stepper.E0.device
-    if sampler is not None:
-        if sampler.pop.device != dev:
-            raise ValueError(f"train_epoch_ngcf: the sampler's tables live on {sampler.pop.device}, the stepper on {dev}")
-        if not callbacks and step_losses is None and _ngcf_native_sampled_ok(stepper, sampler):
-            acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
-            with _gc_paused(pause_gc):
-                stepper.epoch_sampled(sampler, epoch, bs, acc[0], acc[1], max_steps=max_steps)
-            return _sum_of_batch_means(acc, min(sampler.n, len(_batch_starts(sampler.n, bs, max_steps)) * bs), bs)
-        users, items, labels = sampler.draw(epoch)
-    else:
+    if sampler is None:
         arrays = arrays if arrays is not None else epoch_arrays_ngcf(data)
-        users, items, labels = _upload(dev, *arrays)
-    n = users.numel()
-    starts = _batch_starts(n, bs, max_steps)
-    acc = torch.zeros(2, 1, dtype=torch.float32, device=dev)
-    native = (not callbacks and step_losses is None and n > 0 and stepper.L == 1 and stepper._one_call_ok(users[:1], items[:1], labels[:1])
-              and not (stepper._reference_stream and stepper.model.mess_dropout[0] > 0))
-    with _gc_paused(pause_gc):
-        if native:
-            stepper.epoch(users, items, labels, bs, acc[0], acc[1], max_steps=max_steps)
-        else:
-            for k, s in enumerate(starts):
-                if callbacks and k in callbacks:
-                    callbacks[k]()
-                e = min(s + bs, n)
-                slot = acc[0] if e - s == bs else acc[1]
-                if step_losses is None:
-                    stepper.step(users[s:e], items[s:e], labels[s:e], loss_acc=slot)
-                else:
-                    tmp = torch.zeros(1, dtype=torch.float32, device=dev)
-                    stepper.step(users[s:e], items[s:e], labels[s:e], loss_acc=tmp)
-                    step_losses.append(tmp.item() / (e - s))
-                    slot += tmp
-    return _sum_of_batch_means(acc, min(n, len(starts) * bs), bs)
+    return _train_epoch(_NGCF, stepper, sampler, arrays, bs, pause_gc, None, max_steps, step_losses, callbacks, epoch)
 
 
 class _DualTaskArena:
@@ -1793,27 +1740,34 @@ class DualTaskStepper(_DualTaskArena):
                      | (_lib.STEP_PIPELINED if self.pipelined and self._side is not None else 0))
         return dsc
 
+    def _check_epoch_args(self, who, batch=None, paths=None, keep_prob=1.0):
+        """The argument checks epoch and epoch_strided share, each where its argument is given (their own checks run between them):
+        the batch tensors, the staged path tensors, edge dropout's needs."""
+        if batch is not None and not _batch_ok(*batch, min_len=0):
+            raise ValueError(f"DualTaskStepper.{who}: users / items (int64) and labels (fp32) must be contiguous device tensors of one length")
+        for t in paths or ():
+            if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
+                raise ValueError(f"DualTaskStepper.{who}: seq / seq_l / targets must be contiguous device int64 tensors")
+        if keep_prob < 1.0 and (self._graph_t is self.model.Graph or self.L < 2):
+            raise ValueError(f"DualTaskStepper.{who}: edge dropout needs the transposed handle (a model built with --dropout 1) and L >= 2")
+
     def epoch(self, users, items, labels, batch_size, seq, seq_l, targets, path_off, max_steps=None, keep_prob=1.0, drop_seed=0):
         """A whole pre-shuffled, device-resident epoch as ONE native call (spex_dual_task_epoch_f32; Train() of
         main_auto_expert_s.py:60-91): batch k = samples [k B, (k+1) B) with the staged paths [path_off[k], path_off[k+1]) (path_off: a
         host int64 array of n_batches + 1 offsets).  Both losses are added to `loss_acc`.  keep_prob < 1: the in-kernel sampled edge
         mask on the rec branch, a fresh one per step (seed (drop_seed << 32) | step)."""
-        if not _batch_ok(users, items, labels, min_len=0):
-            raise ValueError("DualTaskStepper.epoch: users / items (int64) and labels (fp32) must be contiguous device tensors of one length")
+        self._check_epoch_args("epoch", batch=(users, items, labels))
         path_off = np.ascontiguousarray(path_off, dtype=np.int64)
         n_paths = int(path_off[-1])
         if n_paths:
-            for t in (seq, seq_l, targets):
-                if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
-                    raise ValueError("DualTaskStepper.epoch: seq / seq_l / targets must be contiguous device int64 tensors")
+            self._check_epoch_args("epoch", paths=(seq, seq_l, targets))
             if seq.shape[1] != self.path_len or seq.shape[0] < n_paths or seq_l.numel() < n_paths or targets.numel() < n_paths \
                     or int(np.diff(path_off).max()) > self.path_capacity:
                 raise ValueError("DualTaskStepper.epoch: the staged paths do not match path_off / the stepper's capacity")
         n_batches = (users.numel() + int(batch_size) - 1) // int(batch_size)
         if len(path_off) < (n_batches if max_steps is None else min(n_batches, int(max_steps))) + 1:
             raise ValueError("DualTaskStepper.epoch: path_off needs one offset per batch + 1")
-        if keep_prob < 1.0 and (self._graph_t is self.model.Graph or self.L < 2):
-            raise ValueError("DualTaskStepper.epoch: edge dropout needs the transposed handle (a model built with --dropout 1) and L >= 2")
+        self._check_epoch_args("epoch", keep_prob=keep_prob)
         dsc = self._prepare_desc(min(int(batch_size), users.numel()))
         if n_paths and self._side is not None:
             for t in (seq, seq_l, targets):
@@ -1831,8 +1785,7 @@ class DualTaskStepper(_DualTaskArena):
         """`epoch` over paths staged with a fixed stride (spex_dual_task_epoch_strided_f32) — what ops.sample_dual_task_paths writes:
         batch k's paths are the first counts[k] rows from row k * path_stride of seq / seq_l / targets.  counts: a HOST int32 array (or
         CPU tensor) of one count per batch run.  A count outside [0, min(path_stride, path_capacity)] is refused before any launch."""
-        if not _batch_ok(users, items, labels, min_len=0):
-            raise ValueError("DualTaskStepper.epoch_strided: users / items (int64) and labels (fp32) must be contiguous device tensors of one length")
+        self._check_epoch_args("epoch_strided", batch=(users, items, labels))
         counts = counts.numpy() if torch.is_tensor(counts) else np.asarray(counts)
         if counts.dtype != np.int32 or not counts.flags.c_contiguous:
             raise ValueError("DualTaskStepper.epoch_strided: counts must be a contiguous host int32 array")
@@ -1844,14 +1797,11 @@ class DualTaskStepper(_DualTaskArena):
         path_stride = int(path_stride)
         any_paths = n_batches > 0 and bool(counts[:n_batches].any())
         if any_paths:
-            for t in (seq, seq_l, targets):
-                if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
-                    raise ValueError("DualTaskStepper.epoch_strided: seq / seq_l / targets must be contiguous device int64 tensors")
+            self._check_epoch_args("epoch_strided", paths=(seq, seq_l, targets))
             rows = n_batches * path_stride
             if seq.dim() != 2 or seq.shape[1] != self.path_len or seq.shape[0] < rows or seq_l.numel() < rows or targets.numel() < rows:
                 raise ValueError("DualTaskStepper.epoch_strided: the staged paths do not cover n_batches * path_stride rows of the stepper's width")
-        if keep_prob < 1.0 and (self._graph_t is self.model.Graph or self.L < 2):
-            raise ValueError("DualTaskStepper.epoch_strided: edge dropout needs the transposed handle (a model built with --dropout 1) and L >= 2")
+        self._check_epoch_args("epoch_strided", keep_prob=keep_prob)
         dsc = self._prepare_desc(max(1, min(int(batch_size), users.numel())))
         if any_paths and self._side is not None:
             for t in (seq, seq_l, targets):
@@ -2059,6 +2009,50 @@ class DualDeviceSampler:
         return st
 
 
+def _dual_epoch(stepper, tensors, batch_size, max_steps, edge_dropout, cum_every, cum_out, pause_gc, native, paths):
+    """What train_epoch_dual does once the epoch's (users, items, labels, seq, seq_l, targets) are on the device, whichever the source.
+    The whole epoch as ONE native call — native(keep_prob, drop_seed), the source's own — where nothing has to happen on the host
+    between two steps: no running sums asked for, no host-drawn mask, not the pipelined form, whose side stream the loop manages step
+    by step.  Otherwise one DualTaskStepper.step per batch, batch k with the staged paths paths()[k] = (first row, count).  Returns
+    the epoch's (loss1, loss2) sums, both branches joined."""
+    users, items, labels, seq, seq_l, tgt = tensors
+    n = users.numel()
+    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
+    pipelined_env = stepper._side is not None and os.environ.get("SPEX_DUAL_PIPELINED", "0") == "1"
+    stepper.join()
+    stepper.loss_acc.zero_()
+    with _gc_paused(pause_gc):
+        if not cum_every and stream in (None, "philox") and n > 0 and not pipelined_env and not stepper.pipelined:
+            try:
+                native(keep_prob, seed)
+            finally:
+                stepper.join()
+        else:
+            # the epoch's inputs are complete on the device before its first step and nothing but the steps touches the model inside
+            # the loop: the pipelined form's contract (DualTaskStepper.__init__), so the loop MAY run in it — SPEX_DUAL_PIPELINED=1.
+            # It pays when the trust branch is the longer one (round 3's first measurement: 119 -> 102 us per step on Epinion2); with
+            # this round's trust kernel (46 us against the rec branch's ~70) the fork / join form is the faster one again (93 vs
+            # 105 us), so that is the default.  (A pipelined loop's first step forks the side stream from the current one, behind
+            # the uploads / the draw.)
+            was_pipelined = stepper.pipelined
+            stepper.pipelined = was_pipelined or pipelined_env
+            try:
+                for k, (s, (p0, T)) in enumerate(zip(_batch_starts(n, batch_size, max_steps), paths())):
+                    e, p1 = min(s + batch_size, n), p0 + T
+                    if stream is not None:
+                        stepper.set_edge_dropout(edge_dropout_mask(stepper.model.Graph, keep_prob, stream, seed, k + 1))
+                    stepper.step(users[s:e], items[s:e], labels[s:e], seq[p0:p1] if T else None, seq_l[p0:p1], tgt[p0:p1])
+                    if cum_every and cum_out is not None and (k + 1) % cum_every == 0:
+                        stepper.join()
+                        cum_out.append(stepper.loss_acc.clone())
+            finally:
+                stepper.join()
+                if stream is not None:
+                    stepper.set_edge_dropout(None)
+                stepper.pipelined = was_pipelined
+    return stepper.loss_acc.clone()
+
+
 def _train_epoch_dual_sampled(stepper, sampler, epoch, batch_size, pause_gc, max_steps, cum_every, cum_out, n_paths_out, edge_dropout,
                               prefetch=None):
     """train_epoch_dual over a DualDeviceSampler (see there).  prefetch: the epoch to draw, on the sampler's stream into its other
@@ -2071,45 +2065,18 @@ def _train_epoch_dual_sampled(stepper, sampler, epoch, batch_size, pause_gc, max
     if sampler.cap > stepper.path_capacity or sampler.path_len != stepper.path_len:
         raise ValueError(f"train_epoch_dual: the sampler stages {sampler.cap} paths of width {sampler.path_len} per batch, the stepper takes "
                          f"{stepper.path_capacity} of width {stepper.path_len}")
-    B, cap, n = sampler.batch_size, sampler.cap, sampler.n
-    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
     st = sampler.issue(epoch, max_steps)
     cur = torch.cuda.current_stream(dev)
     cur.wait_event(st.drawn)                       # the training stream behind the draw ...
     st.drawn.synchronize()                         # ... and the host behind the counts' copy: the one wait, never on the training stream
     n_run = st.key[1]
     counts = st.count_host.numpy()[:n_run].copy()      # (the set may be drawn into again before the caller reads them)
-    users, items, labels, seq, seq_l, tgt, _ = st.tensors()
-    starts = _batch_starts(n, B, max_steps)
-    pipelined_env = stepper._side is not None and os.environ.get("SPEX_DUAL_PIPELINED", "0") == "1"
-    stepper.join()
-    stepper.loss_acc.zero_()
-    native = not cum_every and stream in (None, "philox") and n > 0 and not pipelined_env and not stepper.pipelined
-    with _gc_paused(pause_gc):
-        if native:
-            try:
-                stepper.epoch_strided(users, items, labels, B, seq, seq_l, tgt, cap, counts, max_steps=max_steps, keep_prob=keep_prob,
-                                      drop_seed=seed)
-            finally:
-                stepper.join()
-        else:                                      # (the loop of train_epoch_dual, over slices at k * cap)
-            was_pipelined = stepper.pipelined
-            stepper.pipelined = was_pipelined or pipelined_env
-            try:
-                for k, s in enumerate(starts):
-                    e, p0, T = min(s + B, n), k * cap, int(counts[k])
-                    if stream is not None:
-                        stepper.set_edge_dropout(edge_dropout_mask(stepper.model.Graph, keep_prob, stream, seed, k + 1))
-                    stepper.step(users[s:e], items[s:e], labels[s:e], seq[p0:p0 + T] if T else None, seq_l[p0:p0 + T], tgt[p0:p0 + T])
-                    if cum_every and cum_out is not None and (k + 1) % cum_every == 0:
-                        stepper.join()
-                        cum_out.append(stepper.loss_acc.clone())
-            finally:
-                stepper.join()
-                if stream is not None:
-                    stepper.set_edge_dropout(None)
-                stepper.pipelined = was_pipelined
-    total = stepper.loss_acc.clone()
+    tensors = st.tensors()[:6]
+    B, cap = sampler.batch_size, sampler.cap
+    total = _dual_epoch(stepper, tensors, B, max_steps, edge_dropout, cum_every, cum_out, pause_gc,
+                        lambda keep_prob, seed: stepper.epoch_strided(*tensors[:3], B, *tensors[3:], cap, counts, max_steps=max_steps,
+                                                                      keep_prob=keep_prob, drop_seed=seed),
+                        lambda: [(k * cap, int(counts[k])) for k in range(len(_batch_starts(sampler.n, B, max_steps)))])
     if st.read is None:
         st.read = torch.cuda.Event()
     st.read.record(cur)                            # the set may be drawn into again behind this epoch (both branches are joined)
@@ -2118,19 +2085,6 @@ def _train_epoch_dual_sampled(stepper, sampler, epoch, batch_size, pause_gc, max
     if n_paths_out is not None:
         n_paths_out.extend(int(c) for c in counts)
     return total
-
-
-def _train_epochs_dual_sampled(stepper, sampler, n_epochs, batch_size, edge_dropout, after_epoch, first_epoch, max_steps):
-    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
-    totals = []
-    for e in range(first_epoch, first_epoch + n_epochs):
-        drop = None if stream is None else (keep_prob, stream, bpr_epoch_drop_seed(seed, e) if stream == "philox" else seed)
-        total = _train_epoch_dual_sampled(stepper, sampler, e, batch_size, True, max_steps, None, None, None, drop,
-                                          prefetch=e + 1 if e + 1 < first_epoch + n_epochs else None)
-        totals.append(total)
-        if after_epoch is not None:
-            after_epoch(e - first_epoch, total)
-    return [t.cpu().numpy() for t in totals]
 
 
 def train_epochs_dual(stepper, train_data, trust_data=None, by_user=None, cap=None, n_epochs=None, batch_size=None, edge_dropout=None,
@@ -2149,7 +2103,10 @@ def train_epochs_dual(stepper, train_data, trust_data=None, by_user=None, cap=No
             n_epochs, trust_data = trust_data, None
         if trust_data is not None or by_user is not None or cap is not None or n_epochs is None:
             raise ValueError("train_epochs_dual(stepper, sampler, n_epochs, ...): the sampler holds the trust data, the path index and cap")
-        return _train_epochs_dual_sampled(stepper, train_data, int(n_epochs), batch_size, edge_dropout, after_epoch, int(first_epoch), max_steps)
+        one_epoch = lambda e, drop, nxt: _train_epoch_dual_sampled(stepper, train_data, e, batch_size, True, max_steps, None, None, None, drop,
+                                                                   prefetch=nxt)
+        return [t.cpu().numpy() for t in _train_epochs_sampled("train_epochs_dual", None, stepper, train_data, int(n_epochs), batch_size, edge_dropout,
+                                                               after_epoch, max_steps, int(first_epoch), one_epoch)]
     if trust_data is None or by_user is None or cap is None or n_epochs is None:
         raise ValueError("train_epochs_dual: trust_data, by_user, cap and n_epochs are optional for a DualDeviceSampler only")
     if first_epoch or max_steps is not None:
@@ -2191,51 +2148,14 @@ def train_epoch_dual(stepper, train_data, trust_data=None, by_user=None, cap=Non
     dev = stepper.dev
     users, items, labels = _upload(dev, users_h, items_h, labels_h)
     seq, seq_l, tgt = torch.from_numpy(seq_h).to(dev), torch.from_numpy(seq_l_h).to(dev), torch.from_numpy(tgt_h).to(dev)
-    n = users.numel()
-    starts = _batch_starts(n, batch_size, max_steps)
     if max_steps is not None:
         chosen = chosen[:max_steps]
-    keep_prob, stream, seed = _edge_dropout_args(edge_dropout)
-    pipelined_env = stepper._side is not None and os.environ.get("SPEX_DUAL_PIPELINED", "0") == "1"
-    stepper.join()
-    stepper.loss_acc.zero_()
-    # the whole epoch as ONE native call where nothing has to happen on the host between two steps (no running sums asked for, no
-    # host-drawn mask, not the pipelined form — whose side stream the loop below manages step by step)
-    native = not cum_every and stream in (None, "philox") and n > 0 and not pipelined_env and not stepper.pipelined
-    with _gc_paused(pause_gc):
-        if native:
-            try:
-                path_off = np.zeros(len(chosen) + 1, dtype=np.int64)
-                np.cumsum([len(c) for c in chosen], out=path_off[1:])
-                stepper.epoch(users, items, labels, batch_size, seq, seq_l, tgt, path_off, max_steps=max_steps, keep_prob=keep_prob,
-                              drop_seed=seed)
-            finally:
-                stepper.join()
-        else:
-            # the epoch's inputs are complete on the device before its first step and nothing but the steps touches the model inside
-            # the loop: the pipelined form's contract (DualTaskStepper.__init__), so the loop MAY run in it — SPEX_DUAL_PIPELINED=1.
-            # It pays when the trust branch is the longer one (round 3's first measurement: 119 -> 102 us per step on Epinion2); with
-            # this round's trust kernel (46 us against the rec branch's ~70) the fork / join form is the faster one again (93 vs
-            # 105 us), so that is the default.  (A pipelined loop's first step forks the side stream from the current one, behind
-            # the uploads above.)
-            was_pipelined = stepper.pipelined
-            stepper.pipelined = was_pipelined or pipelined_env
-            try:
-                p0 = 0
-                for k, (s, c) in enumerate(zip(starts, chosen)):
-                    e, p1 = min(s + batch_size, n), p0 + len(c)
-                    if stream is not None:
-                        stepper.set_edge_dropout(edge_dropout_mask(stepper.model.Graph, keep_prob, stream, seed, k + 1))
-                    stepper.step(users[s:e], items[s:e], labels[s:e], seq[p0:p1] if c else None, seq_l[p0:p1], tgt[p0:p1])
-                    p0 = p1
-                    if cum_every and cum_out is not None and (k + 1) % cum_every == 0:
-                        stepper.join()
-                        cum_out.append(stepper.loss_acc.clone())
-            finally:
-                stepper.join()
-                if stream is not None:
-                    stepper.set_edge_dropout(None)
-                stepper.pipelined = was_pipelined
+    path_off = np.zeros(len(chosen) + 1, dtype=np.int64)
+    np.cumsum([len(c) for c in chosen], out=path_off[1:])
+    total = _dual_epoch(stepper, (users, items, labels, seq, seq_l, tgt), batch_size, max_steps, edge_dropout, cum_every, cum_out, pause_gc,
+                        lambda keep_prob, seed: stepper.epoch(users, items, labels, batch_size, seq, seq_l, tgt, path_off, max_steps=max_steps,
+                                                              keep_prob=keep_prob, drop_seed=seed),
+                        lambda: [(int(path_off[k]), len(c)) for k, c in enumerate(chosen)])
     if n_paths_out is not None:
         n_paths_out.extend(len(c) for c in chosen)
-    return stepper.loss_acc.clone()
+    return total

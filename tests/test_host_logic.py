@@ -770,3 +770,162 @@ def test_ngcf_blocked_sampler_replay_is_random_sample_draw_for_draw(epinion2):
     assert np.array_equal(np.asarray(want), got[1]) and random.getstate() == st
     assert not ld._blocked_replay_applies(list(range(9)), small) and not ld._blocked_replay_applies({"a", "b"}, {0: ["a"]})   # (the loop)
     assert not ld._blocked_replay_applies({1, 2, 3, 10 ** 6}, {0: [1]})          # an id beyond the set's table: it does not iterate ascending
+
+
+# ---- the step loops of train_epoch / train_epoch_bpr / train_epoch_ngcf: 150 samples in batches of 64 (two full ones, a ragged one of 22)
+class _LoopRecorder:
+    """What the recording steppers of the three step loops share: every step's batch, the accumulator it was handed (the tensor itself)
+    and that batch's "loss" — the sum of its first index tensor — added to it; "." in `log` per step."""
+    def __init__(self, log=None):
+        self.E0 = torch.zeros(1)
+        self.graph, self.graph_t = _MaskRecordingGraph(), _MaskRecordingGraph()
+        self.seen, self.accs, self.masks, self.log = [], [], [], log if log is not None else []
+    def _record(self, a, b, c, loss_acc):
+        self.log.append(".")
+        self.seen.append((a.numpy().copy(), b.numpy().copy(), c.numpy().copy()))
+        self.accs.append(loss_acc)
+        loss_acc += float(a.sum())
+    def set_edge_dropout(self, mask=None):
+        self.masks.append(mask)
+
+
+class _RecordingBceStepper(_LoopRecorder):
+    def _one_call_ok(self, *a):
+        return False
+    def step_bce(self, users, items, labels, loss_acc=None, batch_rows_only=False):
+        assert batch_rows_only
+        self._record(users, items, labels, loss_acc)
+
+
+class _RecordingBprStepper(_LoopRecorder):
+    """A LightGCNStepper stand-in for train_epoch_bpr's loop."""
+    def _one_call_shape_ok(self):
+        return False
+    def _one_call_bpr_ok(self, *a):
+        return False
+    def step_bpr_exact(self, users, pos, neg, loss_acc=None, batch_rows_only=False):
+        assert batch_rows_only and users.dtype == pos.dtype == neg.dtype == torch.int64
+        self._record(users, pos, neg, loss_acc)
+
+
+class _RecordingNgcfStepper(_LoopRecorder):
+    """An NGCFStepper stand-in for train_epoch_ngcf's loop."""
+    L, _reference_stream = 2, False
+    class model:
+        mess_dropout = [0.1, 0.1]
+    def _one_call_ok(self, *a):
+        return False
+    def step(self, users, items, labels, loss_acc=None):
+        self._record(users, items, labels, loss_acc)
+
+
+class _NgcfBatchSize:
+    batch_size = 64
+
+
+_LOOP_N, _LOOP_B = 150, 64
+_LOOP_SLICES = [slice(0, 64), slice(64, 128), slice(128, 150)]
+
+
+def _loop_arrays():
+    u = (np.arange(_LOOP_N, dtype=np.int64) * 7 + 3) % 101
+    return u, np.arange(_LOOP_N, dtype=np.int64) + 1000, (np.arange(_LOOP_N) % 3 == 0).astype(np.float32)
+
+
+def _loop_run(family, step_losses=None, max_steps=None, edge_dropout=None, callbacks=None, source="arrays", log=None):
+    """One epoch of `family` over _loop_arrays() through its recording stepper.  Returns (stepper, the epoch's total)."""
+    from spex_amd.trainer import train_epoch, train_epoch_bpr, train_epoch_ngcf
+    arrays = _loop_arrays()
+    if family == "bce":
+        st = _RecordingBceStepper(log)
+        total = train_epoch(st, None, batch_size=_LOOP_B, arrays=arrays, step_losses=step_losses, max_steps=max_steps, edge_dropout=edge_dropout)
+    elif family == "bpr":
+        st = _RecordingBprStepper(log)
+        src = {"arrays": arrays[:2] + (arrays[1] + 1,), "callable": lambda: arrays[:2] + (arrays[1] + 1,),
+               "tensors": (torch.from_numpy(arrays[0]).to(torch.int32), torch.from_numpy(arrays[1]), torch.from_numpy(arrays[1] + 1))}[source]
+        total = train_epoch_bpr(st, src, batch_size=_LOOP_B, step_losses=step_losses, max_steps=max_steps, edge_dropout=edge_dropout)
+    else:
+        st = _RecordingNgcfStepper(log)
+        total = train_epoch_ngcf(st, _NgcfBatchSize(), arrays=arrays, step_losses=step_losses, max_steps=max_steps, callbacks=callbacks)
+    return st, total
+
+
+def _loop_want(n_steps):
+    """(the per-batch loss sums, the epoch's total as _sum_of_batch_means forms it in fp32) of the first n_steps batches."""
+    u = _loop_arrays()[0]
+    sums = [float(u[sl].sum()) for sl in _LOOP_SLICES[:n_steps]]
+    full = torch.tensor(sum(sums[:2]), dtype=torch.float32)
+    total = full / _LOOP_B + (torch.tensor(sums[2], dtype=torch.float32) / 22 if n_steps == 3 else 0.0)
+    return sums, float(total)
+
+
+@pytest.mark.parametrize("family", ["bce", "bpr", "ngcf"])
+def test_step_loops_hand_out_the_batches_the_accumulators_and_the_sum(family):
+    """The step loop of each single-task epoch driver on a recording stepper (no native epoch): the batches are the epoch's slices in
+    order; the two full batches accumulate into one cell and the ragged one into the other (adjacent cells of one [2, 1] tensor); the
+    total is full / 64 + ragged / 22; max_steps = 2 stops before the ragged batch; with step_losses every step gets a fresh 1-element
+    accumulator, the list receives the per-batch means, and the total is unchanged."""
+    arrays = _loop_arrays()
+    third = arrays[1] + 1 if family == "bpr" else arrays[2]
+    st, total = _loop_run(family)
+    assert len(st.seen) == 3 and torch.is_tensor(total)
+    for got, sl in zip(st.seen, _LOOP_SLICES):
+        assert np.array_equal(got[0], arrays[0][sl]) and np.array_equal(got[1], arrays[1][sl]) and np.array_equal(got[2], third[sl])
+    a0, a1, a2 = st.accs
+    assert a0.data_ptr() == a1.data_ptr() and a2.data_ptr() == a0.data_ptr() + 4 and a0.numel() == a2.numel() == 1
+    sums, want = _loop_want(3)
+    assert a0.item() == sums[0] + sums[1] and a2.item() == sums[2] and float(total) == want
+    assert st.masks == []
+    # max_steps
+    st2, total2 = _loop_run(family, max_steps=2)
+    assert len(st2.seen) == 2 and all(np.array_equal(x[0], y[0]) for x, y in zip(st2.seen, st.seen))
+    assert st2.accs[0].data_ptr() == st2.accs[1].data_ptr() and float(total2) == _loop_want(2)[1]
+    # step_losses
+    losses = []
+    st3, total3 = _loop_run(family, step_losses=losses)
+    assert losses == [sums[0] / 64, sums[1] / 64, sums[2] / 22] and float(total3) == want
+    assert [a.item() for a in st3.accs] == sums and all(a.shape == (1,) for a in st3.accs)
+    assert len({a.untyped_storage().data_ptr() for a in st3.accs}) == 3              # a fresh accumulator per step
+    assert all(np.array_equal(x[0], y[0]) for x, y in zip(st3.seen, st.seen))
+
+
+def test_ngcf_step_loop_fires_its_callbacks_in_front_of_their_batches():
+    log = []
+    st, total = _loop_run("ngcf", callbacks={0: lambda: log.append("a"), 2: lambda: log.append("c"), 7: lambda: log.append("never")}, log=log)
+    assert "".join(log) == "a..c." and float(total) == _loop_want(3)[1]
+    log = []
+    _loop_run("ngcf", callbacks={0: lambda: log.append("a"), 2: lambda: log.append("c")}, max_steps=2, log=log)
+    assert "".join(log) == "a.."
+
+
+def test_bpr_step_loop_takes_host_arrays_a_callable_and_device_tensors_alike():
+    runs = [_loop_run("bpr", source=s) for s in ("arrays", "callable", "tensors")]
+    (a, ta) = runs[0]
+    assert len(a.seen) == 3
+    for st, total in runs[1:]:
+        assert len(st.seen) == 3 and float(total) == float(ta)
+        for x, y in zip(st.seen, a.seen):
+            assert all(np.array_equal(p, q) and p.dtype == np.int64 for p, q in zip(x, y))
+
+
+@pytest.mark.parametrize("family", ["bce", "bpr"])
+def test_lightgcn_step_loops_set_a_keyed_mask_per_step_and_clear_it(family):
+    """Edge dropout in the LightGCN step loops: step k wears edge_dropout_mask(graph, keep_prob, "philox", seed, k + 1), set in front of
+    the step and cleared behind the loop — also when a step raises; a stepper whose graph_t is its graph is refused by name."""
+    from spex_amd.trainer import train_epoch, train_epoch_bpr
+    st, _ = _loop_run(family, edge_dropout=(0.5, "philox", 7))
+    assert st.masks == [(2, None, 0.5, (7 << 32) | k) for k in (1, 2, 3)] + [None]
+    arrays = _loop_arrays()
+    rec = {"bce": _RecordingBceStepper, "bpr": _RecordingBprStepper}[family]()
+
+    def boom(*a, **k):
+        raise RuntimeError("step")
+    rec.step_bce = rec.step_bpr_exact = boom
+    run = {"bce": lambda s, **k: train_epoch(s, None, batch_size=64, arrays=arrays, **k),
+           "bpr": lambda s, **k: train_epoch_bpr(s, arrays[:2] + (arrays[1] + 1,), batch_size=64, **k)}[family]
+    with pytest.raises(RuntimeError, match="step"):
+        run(rec, edge_dropout=(0.5, "philox", 7))
+    assert rec.masks == [(2, None, 0.5, (7 << 32) | 1), None]
+    rec.graph_t = rec.graph
+    with pytest.raises(ValueError, match={"bce": r"train_epoch\(edge_dropout", "bpr": r"train_epoch_bpr\(edge_dropout"}[family]):
+        run(rec, edge_dropout=(0.5, "philox", 7))
