@@ -25,7 +25,9 @@
 //   or one of its five same-user negatives: users and positive items arrive in proportion to their degree) carry rows of ~1 000
 //   entries all the time.  Measured on Epinion2, B = 256, us per step on uniform / training-shaped batches: 1 part 81.1 / 86.5,
 //   2 parts (16 runs each) 83.6 / 84.7, 3 parts 81.1 / 83.2, 4 parts 89.5 / 91.4 (1 024 workgroups of 1 024 threads).
-// The two d == 64 kernels' bodies live in batch_kernels.h (batch_bf16.hip instantiates them over a bf16 gather source).
+// The pieces all of these kernels share — the segment gather, the last layer at K rows, the push pipeline, the expert gate — and the
+// two d == 64 kernels' bodies live in batch_kernels.h (batch_bf16.hip instantiates the bodies over a bf16 gather source); the host
+// side is one launcher over a descriptor, spex::batch_launch below.
 #include "batch_kernels.h"
 
 using namespace spex;
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_batch_wide_kernel(
     float grad_scale, float push_scale, float *loss_sum, float *__restrict__ loss_rows, float *g_out, float *G, int runs_per_part,
     float *__restrict__ grad_slots, int B, const float *__restrict__ acc2, const float *__restrict__ acc3, const spex::EdgeDrop drop)
 {
-    typedef typename spex::WideVec<V>::T vec;
+    typedef typename LaneVec<V>::T vec;
     constexpr int kRow = kWave * V;
     __shared__ float s_part[2][kWgWaves][kRow];   // [row: user, item][virtual wave][column block j][lane]
     __shared__ float s_light[2][kRow];            // the two light rows, by column
@@ -95,79 +97,20 @@ __global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_batch_wide_kernel(
         return;
     }
     const int row[2] = {(int)u64, (int)i64 + n_user_rows};
-    const int beg[2] = {rowptr[row[0]], rowptr[row[1]]};
-    const int deg[2] = {rowptr[row[0] + 1] - beg[0], rowptr[row[1] + 1] - beg[1]};
+    const RowSet<2> rows = RowSet<2>::of(rowptr, row[0], row[1]);
     const float y_lab = labels[b];
-    // the running layer sum at the batch's rows — or E^0 (+ E^1 + E^2) of the plain-form forward, added in the fused epilogues' order
     vec run = (vec)(0.0f);
-    if (wave < 2) {
-        const size_t o = (size_t)row[wave] * kRow + lane * V;
-        run = *reinterpret_cast<const vec *>(acc_in + o);
-        vec r2 = (vec)(0.0f), r3 = (vec)(0.0f);
-        if (acc2) r2 = *reinterpret_cast<const vec *>(acc2 + o);
-        if (acc3) r3 = *reinterpret_cast<const vec *>(acc3 + o);
-        if (acc2) run = run + r2;
-        if (acc3) run = run + r3;
-    }
-    // the push's runs of 16 entries (the forward's rows again), dealt over (part, wave); the first kPre are loaded ahead of the forward
-    const int n_run0 = (deg[0] + 15) >> 4, n_runs = n_run0 + ((deg[1] + 15) >> 4);
-    const int want = (n_runs + runs_per_part - 1) / runs_per_part;
-    const int act = !PUSH ? 1 : (want < parts ? (want < 1 ? 1 : want) : parts);
-    if (part >= act) return;
-    const int q_step = act * kWgWaves;
-    int q = part * kWgWaves + wave;
-    int p_col[kPre], p_cnt[kPre], p_side[kPre];
-    float p_val[kPre];
-    auto load_runs = [&](int q0) {
-#pragma unroll
-        for (int p = 0; p < kPre; ++p) {
-            const int qq = q0 + p * q_step;
-            p_col[p] = 0;
-            p_val[p] = 0.0f;
-            p_cnt[p] = 0;
-            p_side[p] = 0;
-            if (qq < n_runs) {
-                const int side = qq >= n_run0, rr = side ? qq - n_run0 : qq;
-                const int base = beg[side] + rr * 16, left = deg[side] - rr * 16;
-                p_side[p] = side;
-                p_cnt[p] = left < 16 ? left : 16;
-                if (lane < p_cnt[p]) {
-                    p_col[p] = col[base + lane];
-                    p_val[p] = val[base + lane];
-                    if (drop.mode != 0) p_val[p] = spex::edge_kept(drop, base + lane) ? p_val[p] / drop.keep_prob : 0.0f;   // the forward's mask
-                }
-            }
-        }
-    };
-    if (PUSH) load_runs(q);
-    // ---- 1. last layer at both rows: segments to virtual waves v = segment mod 16, the two rows' virtual waves dealt to the 16 waves
-    const int nseg[2] = {(deg[0] + kTaskEntries - 1) / kTaskEntries, (deg[1] + kTaskEntries - 1) / kTaskEntries};
-    const int nv0 = nseg[0] < kWgWaves ? nseg[0] : kWgWaves, nv = nv0 + (nseg[1] < kWgWaves ? nseg[1] : kWgWaves);
-    const float *__restrict__ Xl = X + lane * V;
-    for (int j = wave; j < nv; j += kWgWaves) {
-        const int side = j >= nv0, v = side ? j - nv0 : j;
-        vec acc = (vec)(0.0f);
-        for (int sgi = v; sgi < nseg[side]; sgi += kWgWaves) {
-            const int left = deg[side] - sgi * kTaskEntries;
-            const int cnt = left < kTaskEntries ? left : kTaskEntries;
-            if (drop.mode != 0) acc = spex::segment_sum_wide<V, true>(col, val, Xl, beg[side] + sgi * kTaskEntries, cnt, lane, acc, drop);
-            else acc = spex::segment_sum_wide<V, false>(col, val, Xl, beg[side] + sgi * kTaskEntries, cnt, lane, acc, drop);
-        }
-#pragma unroll
-        for (int c = 0; c < V; ++c) s_part[side][v][c * kWave + lane] = acc[c];
-    }
+    if (wave < 2) run = running_sum<V>(acc_in, acc2, acc3, (size_t)row[wave] * kRow + lane * V);
+    PushRuns<2> runs;
+    if (!runs.begin(rows, PUSH, parts, runs_per_part, part, wave)) return;
+    if (PUSH) runs.load(rows, col, val, drop, lane);
+    // ---- 1. last layer at both rows
+    last_layer_partials<2, V>(rows, col, val, X, drop, wave, lane, s_part);
     __syncthreads();
     // ---- 2. layer mean at both rows (waves 0 and 1), the score, both gradient rows
     if (wave < 2) {
-        const int lim = nseg[wave] < kWgWaves ? nseg[wave] : kWgWaves;
-#pragma unroll
-        for (int c = 0; c < V; ++c) {
-            float y = lim > 0 ? s_part[wave][0][c * kWave + lane] : 0.0f;
-            for (int w = 1; w < lim; ++w) y = y + s_part[wave][w][c * kWave + lane];   // segment order
-            float s = run[c] + y;
-            if (acc_div != 1.0f) s = s / acc_div;
-            s_light[wave][lane * V + c] = s;                                  // by column: what follows owns columns lane + 64 c
-        }
+        last_layer_mean<V>(s_part[wave], rows.n_virt(wave), run, acc_div, lane,
+                           [&](int c, float s) { s_light[wave][lane * V + c] = s; });   // by column: what follows owns columns lane + 64 c
     }
     __syncthreads();
     // (from here on a lane owns columns lane, lane + 64, ...: every store and every atomic below covers 256 contiguous bytes)
@@ -202,36 +145,9 @@ __global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_batch_wide_kernel(
         }
     }
     if (!PUSH) return;
-    // ---- 3. push over both rows' entries (lightgcn_batch_kernel's loop: lane 0 of every loaded run is read before the first atomic)
-    float *out_l = G + lane;
+    // ---- 3. push over both rows' entries
     const vec gs2[2] = {push_scale * g2[0], push_scale * g2[1]};
-    for (;;) {
-        int c0[kPre];
-        float v0[kPre];
-#pragma unroll
-        for (int p = 0; p < kPre; ++p) {
-            c0[p] = __builtin_amdgcn_readlane(p_col[p], 0);
-            v0[p] = lane_bcast(p_val[p], 0);
-        }
-#pragma unroll
-        for (int p = 0; p < kPre; ++p) {
-            const vec gs = p_side[p] ? gs2[1] : gs2[0];
-            if (p_cnt[p] > 0) {
-#pragma unroll
-                for (int c = 0; c < V; ++c) atomicAdd(out_l + (size_t)c0[p] * kRow + c * kWave, v0[p] * gs[c]);
-            }
-#pragma unroll 1
-            for (int j = 1; j < p_cnt[p]; ++j) {
-                const int cc = __builtin_amdgcn_readlane(p_col[p], j);
-                const float v = lane_bcast(p_val[p], j);
-#pragma unroll
-                for (int c = 0; c < V; ++c) atomicAdd(out_l + (size_t)cc * kRow + c * kWave, v * gs[c]);
-            }
-        }
-        q += kPre * q_step;
-        if (q >= n_runs) break;
-        load_runs(q);
-    }
+    runs.template push<V>(rows, col, val, drop, G, lane, [&](int side) { return side ? gs2[1] : gs2[0]; });
 }
 
 
@@ -257,9 +173,8 @@ __global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_bpr_batch_wide_kerne
     const float *__restrict__ acc2, const float *__restrict__ acc3, float weight_decay, const float *__restrict__ E0,
     int32_t *row_counts, const spex::EdgeDrop drop)
 {
-    typedef typename spex::WideVec<V>::T vec;
+    typedef typename LaneVec<V>::T vec;
     constexpr int kRow = kWave * V;
-    constexpr int KPRE = kPre;                    // push runs a wave loads ahead
     __shared__ float s_part[3][kWgWaves][kRow];   // [row: user, positive, negative][virtual wave][column block j][lane]
     __shared__ float s_light[3][kRow];            // the three light rows, by column
     __shared__ float s_norm[3];
@@ -277,84 +192,26 @@ __global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_bpr_batch_wide_kerne
         return;
     }
     const int r0 = (int)u64, r1 = (int)p64 + n_user_rows, r2 = (int)n64 + n_user_rows;
-    const int beg0 = rowptr[r0], beg1 = rowptr[r1], beg2 = rowptr[r2];
-    const int deg0 = rowptr[r0 + 1] - beg0, deg1 = rowptr[r1 + 1] - beg1, deg2 = rowptr[r2 + 1] - beg2;
+    const RowSet<3> rows = RowSet<3>::of(rowptr, r0, r1, r2);
     const int my_row = sel3(wave, r0, r1, r2);             // (waves 0 .. 2 own a row each behind the forward)
-    // the running layer sum at the three rows, ((E^0 + E^1) + E^2) + y, and the E^0 rows of the L2 term
+    // the running layer sum at the three rows and the E^0 rows of the L2 term
     vec run = (vec)(0.0f), e0v = (vec)(0.0f);
     if (wave < 3) {
         const size_t o = (size_t)my_row * kRow + lane * V;
-        run = *reinterpret_cast<const vec *>(acc_in + o);
-        vec q2 = (vec)(0.0f), q3 = (vec)(0.0f);
-        if (acc2) q2 = *reinterpret_cast<const vec *>(acc2 + o);
-        if (acc3) q3 = *reinterpret_cast<const vec *>(acc3 + o);
+        run = running_sum<V>(acc_in, acc2, acc3, o);
         if (weight_decay > 0.0f) e0v = *reinterpret_cast<const vec *>(E0 + o);
-        if (acc2) run = run + q2;
-        if (acc3) run = run + q3;
     }
-    // the push's runs of 16 entries, the three rows' runs numbered jointly and dealt over (part, wave)
-    const int n_run0 = (deg0 + 15) >> 4, n_run1 = (deg1 + 15) >> 4, n_run2 = (deg2 + 15) >> 4, n_runs = n_run0 + n_run1 + n_run2;
     const bool push = PUSH && G != nullptr;                 // (G == NULL: the dense form — gradient rows into g_out only, no push)
-    const int want = (n_runs + runs_per_part - 1) / runs_per_part;
-    const int act = !push ? 1 : (want < parts ? (want < 1 ? 1 : want) : parts);
-    if (part >= act) return;
-    const int q_step = act * kWgWaves;
-    int q = part * kWgWaves + wave;
-    int p_col[KPRE], p_cnt[KPRE], p_side[KPRE];
-    float p_val[KPRE];
-    auto load_runs = [&](int q0) {
-#pragma unroll
-        for (int p = 0; p < KPRE; ++p) {
-            const int qq = q0 + p * q_step;
-            p_col[p] = 0;
-            p_val[p] = 0.0f;
-            p_cnt[p] = 0;
-            p_side[p] = 0;
-            if (qq < n_runs) {
-                const int side = (qq >= n_run0) + (qq >= n_run0 + n_run1), rr = qq - sel3(side, 0, n_run0, n_run0 + n_run1);
-                const int base = sel3(side, beg0, beg1, beg2) + rr * 16, left = sel3(side, deg0, deg1, deg2) - rr * 16;
-                p_side[p] = side;
-                p_cnt[p] = left < 16 ? left : 16;
-                if (lane < p_cnt[p]) {
-                    p_col[p] = col[base + lane];
-                    p_val[p] = val[base + lane];
-                    if (drop.mode != 0) p_val[p] = spex::edge_kept(drop, base + lane) ? p_val[p] / drop.keep_prob : 0.0f;   // the forward's mask
-                }
-            }
-        }
-    };
-    if (push) load_runs(q);
-    // ---- 1. last layer at the three rows: segments to virtual waves v = segment mod 16, the three rows' virtual waves dealt to the 16 waves
-    const int nseg0 = (deg0 + kTaskEntries - 1) / kTaskEntries, nseg1 = (deg1 + kTaskEntries - 1) / kTaskEntries,
-              nseg2 = (deg2 + kTaskEntries - 1) / kTaskEntries;
-    const int nv0 = nseg0 < kWgWaves ? nseg0 : kWgWaves, nv1 = nseg1 < kWgWaves ? nseg1 : kWgWaves, nv2 = nseg2 < kWgWaves ? nseg2 : kWgWaves;
-    const int nv = nv0 + nv1 + nv2;
-    const float *__restrict__ Xl = X + lane * V;
-    for (int j = wave; j < nv; j += kWgWaves) {
-        const int side = (j >= nv0) + (j >= nv0 + nv1), v = j - sel3(side, 0, nv0, nv0 + nv1);
-        const int s_beg = sel3(side, beg0, beg1, beg2), s_deg = sel3(side, deg0, deg1, deg2), s_nseg = sel3(side, nseg0, nseg1, nseg2);
-        vec acc = (vec)(0.0f);
-        for (int sgi = v; sgi < s_nseg; sgi += kWgWaves) {
-            const int left = s_deg - sgi * kTaskEntries;
-            const int cnt = left < kTaskEntries ? left : kTaskEntries;
-            if (drop.mode != 0) acc = spex::segment_sum_wide<V, true>(col, val, Xl, s_beg + sgi * kTaskEntries, cnt, lane, acc, drop);
-            else acc = spex::segment_sum_wide<V, false>(col, val, Xl, s_beg + sgi * kTaskEntries, cnt, lane, acc, drop);
-        }
-#pragma unroll
-        for (int c = 0; c < V; ++c) s_part[side][v][c * kWave + lane] = acc[c];
-    }
+    PushRuns<3> runs;
+    if (!runs.begin(rows, push, parts, runs_per_part, part, wave)) return;
+    if (push) runs.load(rows, col, val, drop, lane);
+    // ---- 1. last layer at the three rows
+    last_layer_partials<3, V>(rows, col, val, X, drop, wave, lane, s_part);
     __syncthreads();
     // ---- 2. layer mean at the three rows (waves 0 .. 2), the two scores, the three gradient rows
     if (wave < 3) {
-        const int lim = sel3(wave, nv0, nv1, nv2);
-#pragma unroll
-        for (int c = 0; c < V; ++c) {
-            float y = lim > 0 ? s_part[wave][0][c * kWave + lane] : 0.0f;
-            for (int w = 1; w < lim; ++w) y = y + s_part[wave][w][c * kWave + lane];   // segment order
-            float s = run[c] + y;
-            if (acc_div != 1.0f) s = s / acc_div;
-            s_light[wave][lane * V + c] = s;                                  // by column: what follows owns columns lane + 64 c
-        }
+        last_layer_mean<V>(s_part[wave], rows.n_virt(wave), run, acc_div, lane,
+                           [&](int c, float s) { s_light[wave][lane * V + c] = s; });   // by column: what follows owns columns lane + 64 c
         if (weight_decay > 0.0f) {
             float sq = e0v[0] * e0v[0];
 #pragma unroll
@@ -401,36 +258,9 @@ __global__ __launch_bounds__(kWave *kWgWaves) void lightgcn_bpr_batch_wide_kerne
         }
     }
     if (!push) return;
-    // ---- 3. push over the three rows' entries (lightgcn_batch_kernel's loop: lane 0 of every loaded run is read before the first atomic)
-    float *out_l = G + lane;
+    // ---- 3. push over the three rows' entries
     const vec gsu = push_scale * gu, gsp = push_scale * gp, gsn = push_scale * gn;
-    for (;;) {
-        int c0[KPRE];
-        float v0[KPRE];
-#pragma unroll
-        for (int p = 0; p < KPRE; ++p) {
-            c0[p] = __builtin_amdgcn_readlane(p_col[p], 0);
-            v0[p] = lane_bcast(p_val[p], 0);
-        }
-#pragma unroll
-        for (int p = 0; p < KPRE; ++p) {
-            const vec gs = p_side[p] == 0 ? gsu : (p_side[p] == 1 ? gsp : gsn);
-            if (p_cnt[p] > 0) {
-#pragma unroll
-                for (int c = 0; c < V; ++c) atomicAdd(out_l + (size_t)c0[p] * kRow + c * kWave, v0[p] * gs[c]);
-            }
-#pragma unroll 1
-            for (int j = 1; j < p_cnt[p]; ++j) {
-                const int cc = __builtin_amdgcn_readlane(p_col[p], j);
-                const float v = lane_bcast(p_val[p], j);
-#pragma unroll
-                for (int c = 0; c < V; ++c) atomicAdd(out_l + (size_t)cc * kRow + c * kWave, v * gs[c]);
-            }
-        }
-        q += KPRE * q_step;
-        if (q >= n_runs) break;
-        load_runs(q);
-    }
+    runs.template push<V>(rows, col, val, drop, G, lane, [&](int side) { return side == 0 ? gsu : (side == 1 ? gsp : gsn); });
 }
 
 // The dual-task model's rec branch has the expert gate between the layer mean and the score (utility1/model_expert_s.py:154-168),
@@ -463,52 +293,23 @@ __global__ __launch_bounds__(kWave *kWgWaves) void gated_batch_fwd_kernel(
         return;
     }
     const int row[2] = {(int)u64, (int)i64 + n_user_rows};
-    const int beg[2] = {rowptr[row[0]], rowptr[row[1]]};
-    const int deg[2] = {rowptr[row[0] + 1] - beg[0], rowptr[row[1] + 1] - beg[1]};
-    float run = 0.0f, a_raw = 0.0f, w00 = 0.0f, w01 = 0.0f, w10 = 0.0f, w11 = 0.0f;
+    const RowSet<2> rows = RowSet<2>::of(rowptr, row[0], row[1]);
+    float run = 0.0f, a_raw = 0.0f;
+    GateW w;
     if (wave < 2) {                       // the gate's operands, requested with everything else
-        const float *att = wave ? att_i : att_u;
-        run = acc_in[(size_t)row[wave] * kWave + lane];
-        float r2 = 0.0f, r3 = 0.0f;                          // (plain-form forward layers: see lightgcn_batch_kernel)
-        if (acc2) r2 = acc2[(size_t)row[wave] * kWave + lane];
-        if (acc3) r3 = acc3[(size_t)row[wave] * kWave + lane];
-        if (acc2) run = run + r2;
-        if (acc3) run = run + r3;
-        a_raw = raw[(size_t)row[wave] * kWave + lane];
-        w00 = att[2 * lane]; w01 = att[2 * lane + 1];
-        w10 = att[2 * (kWave + lane)]; w11 = att[2 * (kWave + lane) + 1];
+        const size_t o = (size_t)row[wave] * kWave + lane;
+        run = running_sum<1>(acc_in, acc2, acc3, o);
+        a_raw = raw[o];
+        w.load(wave ? att_i : att_u, lane);
     }
-    const int nseg[2] = {(deg[0] + kTaskEntries - 1) / kTaskEntries, (deg[1] + kTaskEntries - 1) / kTaskEntries};
-    const int nv0 = nseg[0] < kWgWaves ? nseg[0] : kWgWaves, nv = nv0 + (nseg[1] < kWgWaves ? nseg[1] : kWgWaves);
-    const float *__restrict__ Xl = X + lane;
-    for (int j = wave; j < nv; j += kWgWaves) {
-        const int side = j >= nv0, v = side ? j - nv0 : j;
-        float acc = 0.0f;
-        for (int sgi = v; sgi < nseg[side]; sgi += kWgWaves) {
-            const int left = deg[side] - sgi * kTaskEntries;
-            if (drop.mode != 0)             // edge dropout: the handle's keep rule, as in lightgcn_batch_kernel
-                acc = segment_sum_masked(col, val, Xl, beg[side] + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc, drop);
-            else
-                acc = segment_sum(col, val, Xl, beg[side] + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc);
-        }
-        s_part[side][v][lane] = acc;
-    }
+    last_layer_partials<2, 1>(rows, col, val, X, drop, wave, lane, s_part);
     __syncthreads();
     if (wave < 2) {
-        const int lim = nseg[wave] < kWgWaves ? nseg[wave] : kWgWaves;
-        float y = lim > 0 ? s_part[wave][0][lane] : 0.0f;
-        for (int w = 1; w < lim; ++w) y = y + s_part[wave][w][lane];          // segment order
-        float s = run + y;
-        if (acc_div != 1.0f) s = s / acc_div;
+        float s = 0.0f;
+        last_layer_mean<1>(s_part[wave], rows.n_virt(wave), run, acc_div, lane, [&](int, float v) { s = v; });
         lo_batch[(size_t)row[wave] * kWave + lane] = s;                        // (a row named twice is written twice with the same value)
-        // the gate, as expert_gate_rows_kernel computes it
-        float z0 = fmaf(s, w10, fmaf(a_raw, w00, 0.0f)), z1 = fmaf(s, w11, fmaf(a_raw, w01, 0.0f));
-        z0 = wave_sum_f32(z0);
-        z1 = wave_sum_f32(z1);
-        const float mx = fmaxf(z0, z1);
-        const float e0 = expf(z0 - mx), e1 = expf(z1 - mx);
-        const float a0 = e0 / (e0 + e1), a1 = e1 / (e0 + e1);
-        s_mixed[wave][lane] = a_raw * a0 + s * a1;
+        float a0, a1;
+        s_mixed[wave][lane] = gate_forward(w, a_raw, s, a0, a1);
     }
     __syncthreads();
     if (wave < 2) {
@@ -556,85 +357,27 @@ __global__ __launch_bounds__(kWave *kWgWaves) void gated_batch_push_kernel(
         return;
     }
     const int row[2] = {(int)u64, (int)i64 + n_user_rows};
-    const int beg[2] = {rowptr[row[0]], rowptr[row[1]]};
-    const int deg[2] = {rowptr[row[0] + 1] - beg[0], rowptr[row[1] + 1] - beg[1]};
-    float run = 0.0f, a_raw = 0.0f, w00 = 0.0f, w01 = 0.0f, w10 = 0.0f, w11 = 0.0f;
+    const RowSet<2> rows = RowSet<2>::of(rowptr, row[0], row[1]);
+    float run = 0.0f, a_raw = 0.0f;
+    GateW w;
     if (wave < 2) {                       // the gate's operands, requested with everything else
-        const float *att = wave ? att_i : att_u;
         const size_t o = (size_t)row[wave] * kWave + lane;
-        run = acc_in[o];
-        float r2 = 0.0f, r3 = 0.0f;                          // (plain-form forward layers: see lightgcn_batch_kernel)
-        if (acc2) r2 = acc2[o];
-        if (acc3) r3 = acc3[o];
-        if (acc2) run = run + r2;
-        if (acc3) run = run + r3;
+        run = running_sum<1>(acc_in, acc2, acc3, o);
         a_raw = raw[o];
-        w00 = att[2 * lane]; w01 = att[2 * lane + 1];
-        w10 = att[2 * (kWave + lane)]; w11 = att[2 * (kWave + lane) + 1];
+        w.load(wave ? att_i : att_u, lane);
     }
     // the push's runs (the forward's rows again: A^T g in push form walks the rows of A), shared by up to `parts` workgroups
-    const int n_run0 = (deg[0] + 15) >> 4, n_runs = n_run0 + ((deg[1] + 15) >> 4);
-    const int want = (n_runs + runs_per_part - 1) / runs_per_part;
-    const int act = want < parts ? (want < 1 ? 1 : want) : parts;
-    if (part >= act) return;
-    const int q_step = act * kWgWaves;
-    int q = part * kWgWaves + wave;
-    int p_col[kPre], p_cnt[kPre], p_side[kPre];
-    float p_val[kPre];
-    auto load_runs = [&](int q0) {
-#pragma unroll
-        for (int p = 0; p < kPre; ++p) {
-            const int qq = q0 + p * q_step;
-            p_col[p] = 0;
-            p_val[p] = 0.0f;
-            p_cnt[p] = 0;
-            p_side[p] = 0;
-            if (qq < n_runs) {
-                const int side = qq >= n_run0, rr = side ? qq - n_run0 : qq;
-                const int base = beg[side] + rr * 16, left = deg[side] - rr * 16;
-                p_side[p] = side;
-                p_cnt[p] = left < 16 ? left : 16;
-                if (lane < p_cnt[p]) {
-                    p_col[p] = col[base + lane];
-                    p_val[p] = val[base + lane];
-                    if (drop.mode != 0) p_val[p] = spex::edge_kept(drop, base + lane) ? p_val[p] / drop.keep_prob : 0.0f;   // the forward's mask
-                }
-            }
-        }
-    };
-    load_runs(q);
+    PushRuns<2> runs;
+    if (!runs.begin(rows, true, parts, runs_per_part, part, wave)) return;
+    runs.load(rows, col, val, drop, lane);
     // ---- 1. last layer at both rows (gated_batch_fwd_kernel's / the row-list kernel's order of sums)
-    const int nseg[2] = {(deg[0] + kTaskEntries - 1) / kTaskEntries, (deg[1] + kTaskEntries - 1) / kTaskEntries};
-    const int nv0 = nseg[0] < kWgWaves ? nseg[0] : kWgWaves, nv = nv0 + (nseg[1] < kWgWaves ? nseg[1] : kWgWaves);
-    const float *__restrict__ Xl = X + lane;
-    for (int j = wave; j < nv; j += kWgWaves) {
-        const int side = j >= nv0, v = side ? j - nv0 : j;
-        float acc = 0.0f;
-        for (int sgi = v; sgi < nseg[side]; sgi += kWgWaves) {
-            const int left = deg[side] - sgi * kTaskEntries;
-            if (drop.mode != 0)             // edge dropout: the handle's keep rule, as in lightgcn_batch_kernel
-                acc = segment_sum_masked(col, val, Xl, beg[side] + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc, drop);
-            else
-                acc = segment_sum(col, val, Xl, beg[side] + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc);
-        }
-        s_part[side][v][lane] = acc;
-    }
+    last_layer_partials<2, 1>(rows, col, val, X, drop, wave, lane, s_part);
     __syncthreads();
     // ---- 2. layer mean + gate (waves 0 / 1: the user / the item row)
     float s = 0.0f, a0 = 0.0f, a1 = 0.0f;
     if (wave < 2) {
-        const int lim = nseg[wave] < kWgWaves ? nseg[wave] : kWgWaves;
-        float y = lim > 0 ? s_part[wave][0][lane] : 0.0f;
-        for (int w = 1; w < lim; ++w) y = y + s_part[wave][w][lane];          // segment order
-        s = run + y;
-        if (acc_div != 1.0f) s = s / acc_div;
-        float z0 = fmaf(s, w10, fmaf(a_raw, w00, 0.0f)), z1 = fmaf(s, w11, fmaf(a_raw, w01, 0.0f));
-        z0 = wave_sum_f32(z0);
-        z1 = wave_sum_f32(z1);
-        const float mx = fmaxf(z0, z1);
-        const float e0 = expf(z0 - mx), e1 = expf(z1 - mx);
-        a0 = e0 / (e0 + e1); a1 = e1 / (e0 + e1);
-        s_mixed[wave][lane] = a_raw * a0 + s * a1;
+        last_layer_mean<1>(s_part[wave], rows.n_virt(wave), run, acc_div, lane, [&](int, float v) { s = v; });
+        s_mixed[wave][lane] = gate_forward(w, a_raw, s, a0, a1);
     }
     __syncthreads();
     // ---- 3. score, loss, d loss / d gated rows, and the gate's backward for this sample's two rows
@@ -643,53 +386,22 @@ __global__ __launch_bounds__(kWave *kWgWaves) void gated_batch_push_kernel(
         const float x = wave_sum_f32(fmaf(mu, mi, 0.0f));
         const float dg = (sigmoid_f(x) - y_lab) * grad_scale;
         const float gg = dg * (wave ? mu : mi);
-        const float da0 = wave_sum_f32(gg * a_raw), da1 = wave_sum_f32(gg * s);
-        const float dot = a0 * da0 + a1 * da1;
-        const float dz0 = a0 * (da0 - dot), dz1 = a1 * (da1 - dot);
-        const float d_raw = a0 * gg + dz0 * w00 + dz1 * w01, d_prop = a1 * gg + dz0 * w10 + dz1 * w11;
+        float d_raw, d_prop, dz0, dz1;
+        gate_backward(w, a_raw, s, a0, a1, gg, d_raw, d_prop, dz0, dz1);
         s_dprop[wave][lane] = d_prop;
         if (part == 0) {
             const size_t o = (size_t)row[wave] * kWave + lane;
             if (g_prop) atomicAdd(g_prop + o, d_prop);                    // (NULL: nobody reads it — the L == 3 step)
             atomicAdd(G + o, push_scale * d_prop);
             atomicAdd(g_raw + o, d_raw);
-            // (every sample adds to the same 512 words: 256 x 64 lane-atomics per cache line serialise in L2 — 13 us of a 25 us
-            //  launch when all went to ONE copy — so sample b adds into copy b mod n_att_copies and the caller sums the copies)
-            float *ga = g_att + (size_t)(b % n_att_copies) * 512 + wave * 256;
-            atomicAdd(ga + 2 * lane, fmaf(a_raw, dz0, 0.0f));
-            atomicAdd(ga + 2 * lane + 1, fmaf(a_raw, dz1, 0.0f));
-            atomicAdd(ga + 2 * (kWave + lane), fmaf(s, dz0, 0.0f));
-            atomicAdd(ga + 2 * (kWave + lane) + 1, fmaf(s, dz1, 0.0f));
+            gate_att_add(g_att + (size_t)(b % n_att_copies) * 512 + wave * 256, lane, a_raw, s, dz0, dz1);
             if (wave == 0 && lane == 0) atomicAdd(loss_sum, fmaxf(x, 0.0f) - x * y_lab + log1pf(expf(-fabsf(x))));
         }
     }
     __syncthreads();
-    // ---- 4. push over both rows' entries (lightgcn_batch_kernel's loop)
+    // ---- 4. push over both rows' entries
     const float g2[2] = {push_scale * s_dprop[0][lane], push_scale * s_dprop[1][lane]};
-    float *out_l = G + lane;
-    for (;;) {
-        int c0[kPre];
-        float v0[kPre];
-#pragma unroll
-        for (int p = 0; p < kPre; ++p) {
-            c0[p] = __builtin_amdgcn_readlane(p_col[p], 0);
-            v0[p] = lane_bcast(p_val[p], 0);
-        }
-#pragma unroll
-        for (int p = 0; p < kPre; ++p) {
-            const float gs = p_side[p] ? g2[1] : g2[0];
-            if (p_cnt[p] > 0) atomicAdd(out_l + (size_t)c0[p] * kWave, v0[p] * gs);
-#pragma unroll 1
-            for (int j = 1; j < p_cnt[p]; ++j) {
-                const int c = __builtin_amdgcn_readlane(p_col[p], j);
-                const float v = lane_bcast(p_val[p], j);
-                atomicAdd(out_l + (size_t)c * kWave, v * gs);
-            }
-        }
-        q += kPre * q_step;
-        if (q >= n_runs) break;
-        load_runs(q);
-    }
+    runs.template push<1>(rows, col, val, drop, G, lane, [&](int side) { return side ? g2[1] : g2[0]; });
 }
 
 
@@ -733,9 +445,9 @@ __global__ __launch_bounds__(kWave *kWgWaves) void owned_rows_kernel(
     for (int sgi = wave; sgi < nseg; sgi += kWgWaves) {
         const int left = deg - sgi * kTaskEntries;
         if (drop.mode != 0)
-            acc = segment_sum_masked(col, val, Xl, beg + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc, drop);
+            acc = segment_sum<true>(col, val, Xl, beg + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc, drop);
         else
-            acc = segment_sum(col, val, Xl, beg + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc);
+            acc = segment_sum<false>(col, val, Xl, beg + sgi * kTaskEntries, left < kTaskEntries ? left : kTaskEntries, lane, acc, drop);
     }
     if (nseg > 1) {
         if (wave != 0 && wave < nseg) s_part[wave][lane] = acc;
@@ -786,64 +498,29 @@ __global__ __launch_bounds__(kWave *kWgWaves) void rows_train_push_kernel(
     int beg[2] = {0, 0}, deg[2] = {0, 0};
 #pragma unroll
     for (int w = 0; w < 2; ++w)
-        if (rowptr && p64[w] >= 0 && p64[w] < n_push_rows) {
+        if (rowptr && p64[w] >= 0 && p64[w] < n_push_rows) {      // (a position without a row in the push structure: an empty row)
             beg[w] = rowptr[p64[w]];
             deg[w] = rowptr[p64[w] + 1] - beg[w];
         }
-    float a_raw = 0.0f, s = 0.0f, w00 = 0.0f, w01 = 0.0f, w10 = 0.0f, w11 = 0.0f;
+    const RowSet<2> rows = {beg[0], beg[1], 0, deg[0], deg[1], 0};
+    float a_raw = 0.0f, s = 0.0f;
+    GateW w;
     if (wave < 2) {                       // the operands, requested with everything else
         const size_t o = ((size_t)wave * B + b) * kWave + lane;
         s = rows_prop[o];
         if (GATED) {
-            const float *att = wave ? att_i : att_u;
             a_raw = rows_raw[o];
-            w00 = att[2 * lane]; w01 = att[2 * lane + 1];
-            w10 = att[2 * (kWave + lane)]; w11 = att[2 * (kWave + lane) + 1];
+            w.load(wave ? att_i : att_u, lane);
         }
     }
-    const int n_run0 = (deg[0] + 15) >> 4, n_runs = n_run0 + ((deg[1] + 15) >> 4);
-    const int want = (n_runs + runs_per_part - 1) / runs_per_part;
-    const int act = want < parts ? (want < 1 ? 1 : want) : parts;
-    if (part >= act) return;
-    const int q_step = act * kWgWaves;
-    int q = part * kWgWaves + wave;
-    int p_col[kPre], p_cnt[kPre], p_side[kPre];
-    float p_val[kPre];
-    auto load_runs = [&](int q0) {
-#pragma unroll
-        for (int p = 0; p < kPre; ++p) {
-            const int qq = q0 + p * q_step;
-            p_col[p] = 0;
-            p_val[p] = 0.0f;
-            p_cnt[p] = 0;
-            p_side[p] = 0;
-            if (qq < n_runs) {
-                const int side = qq >= n_run0, rr = side ? qq - n_run0 : qq;
-                const int base = beg[side] + rr * 16, left = deg[side] - rr * 16;
-                p_side[p] = side;
-                p_cnt[p] = left < 16 ? left : 16;
-                if (lane < p_cnt[p]) {
-                    p_col[p] = col[base + lane];
-                    p_val[p] = val[base + lane];
-                    if (drop.mode != 0) p_val[p] = spex::edge_kept(drop, base + lane) ? p_val[p] / drop.keep_prob : 0.0f;   // the forward's mask
-                }
-            }
-        }
-    };
-    load_runs(q);
+    PushRuns<2> runs;
+    if (!runs.begin(rows, true, parts, runs_per_part, part, wave)) return;
+    runs.load(rows, col, val, drop, lane);
     // ---- gate (GATED) -> the rows that are scored
     float a0 = 0.0f, a1 = 0.0f;
     if (wave < 2) {
         float mixed = s;
-        if (GATED) {
-            float z0 = fmaf(s, w10, fmaf(a_raw, w00, 0.0f)), z1 = fmaf(s, w11, fmaf(a_raw, w01, 0.0f));
-            z0 = wave_sum_f32(z0);
-            z1 = wave_sum_f32(z1);
-            const float mx = fmaxf(z0, z1);
-            const float e0 = expf(z0 - mx), e1 = expf(z1 - mx);
-            a0 = e0 / (e0 + e1); a1 = e1 / (e0 + e1);
-            mixed = a_raw * a0 + s * a1;
-        }
+        if (GATED) mixed = gate_forward(w, a_raw, s, a0, a1);
         s_mixed[wave][lane] = mixed;
     }
     __syncthreads();
@@ -854,13 +531,7 @@ __global__ __launch_bounds__(kWave *kWgWaves) void rows_train_push_kernel(
         const float dg = (sigmoid_f(x) - y_lab) * grad_scale;
         const float gg = dg * (wave ? mu : mi);
         float d_raw = 0.0f, d_prop = gg, dz0 = 0.0f, dz1 = 0.0f;
-        if (GATED) {
-            const float da0 = wave_sum_f32(gg * a_raw), da1 = wave_sum_f32(gg * s);
-            const float dot = a0 * da0 + a1 * da1;
-            dz0 = a0 * (da0 - dot); dz1 = a1 * (da1 - dot);
-            d_raw = a0 * gg + dz0 * w00 + dz1 * w01;
-            d_prop = a1 * gg + dz0 * w10 + dz1 * w11;
-        }
+        if (GATED) gate_backward(w, a_raw, s, a0, a1, gg, d_raw, d_prop, dz0, dz1);
         s_dprop[wave][lane] = d_prop;
         if (part == 0) {
             const int64_t r64 = p64[wave] - lo;
@@ -870,58 +541,18 @@ __global__ __launch_bounds__(kWave *kWgWaves) void rows_train_push_kernel(
                 atomicAdd(P + o, push_scale * d_prop);
                 if (GATED) atomicAdd(g_raw + o, d_raw);
             }
-            if (GATED) {
-                float *ga = g_att + (size_t)(b % n_att_copies) * 512 + wave * 256;   // (copies: see gated_batch_push_kernel)
-                atomicAdd(ga + 2 * lane, fmaf(a_raw, dz0, 0.0f));
-                atomicAdd(ga + 2 * lane + 1, fmaf(a_raw, dz1, 0.0f));
-                atomicAdd(ga + 2 * (kWave + lane), fmaf(s, dz0, 0.0f));
-                atomicAdd(ga + 2 * (kWave + lane) + 1, fmaf(s, dz1, 0.0f));
-            }
+            if (GATED) gate_att_add(g_att + (size_t)(b % n_att_copies) * 512 + wave * 256, lane, a_raw, s, dz0, dz1);
             if (wave == 0 && lane == 0) atomicAdd(loss_sum, fmaxf(x, 0.0f) - x * y_lab + log1pf(expf(-fabsf(x))));
         }
     }
-    if (n_runs == 0) return;                                               // (workgroup-uniform)
+    if (runs.n_runs == 0) return;                                          // (workgroup-uniform)
     __syncthreads();
-    // ---- push over both rows' entries in the rank's columns (lightgcn_batch_kernel's loop)
+    // ---- push over both rows' entries in the rank's columns
     const float g2[2] = {push_scale * s_dprop[0][lane], push_scale * s_dprop[1][lane]};
-    float *out_l = P + lane;
-    for (;;) {
-        int c0[kPre];
-        float v0[kPre];
-#pragma unroll
-        for (int p = 0; p < kPre; ++p) {
-            c0[p] = __builtin_amdgcn_readlane(p_col[p], 0);
-            v0[p] = lane_bcast(p_val[p], 0);
-        }
-#pragma unroll
-        for (int p = 0; p < kPre; ++p) {
-            const float gs = p_side[p] ? g2[1] : g2[0];
-            if (p_cnt[p] > 0) atomicAdd(out_l + (size_t)c0[p] * kWave, v0[p] * gs);
-#pragma unroll 1
-            for (int j = 1; j < p_cnt[p]; ++j) {
-                const int c = __builtin_amdgcn_readlane(p_col[p], j);
-                const float v = lane_bcast(p_val[p], j);
-                atomicAdd(out_l + (size_t)c * kWave, v * gs);
-            }
-        }
-        q += kPre * q_step;
-        if (q >= n_runs) break;
-        load_runs(q);
-    }
+    runs.template push<1>(rows, col, val, drop, P, lane, [&](int side) { return side ? g2[1] : g2[0]; });
 }
 
 }  // namespace
-
-// The wide batch kernels move rows as dwordx2 / dwordx4 per lane: their source tables must be 16-byte aligned.
-static bool wide_aligned(const float *a, const float *b, const float *c, const float *d)
-{
-    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
-}
-
-static spex::EdgeDrop edge_drop_of(const spex_graph_t *g)
-{
-    return spex::EdgeDrop{g->keep, g->edge_id, g->mask_mode, g->keep_prob, (uint32_t)g->seed, (uint32_t)(g->seed >> 32)};
-}
 
 extern "C" int spex_gated_batch_fwd_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div, const float *raw,
                                        const float *att_u, const float *att_i, const int64_t *users, const int64_t *items,
@@ -999,40 +630,139 @@ extern "C" int spex_debug_batch_stamps(unsigned long long *out)
 }
 #endif
 
+// ---- the one launcher of the sample / triple kernels of both translation units: checks the descriptor — each
+//      family of exports keeps the order, status codes and texts of its checks —, picks the grid and the kernel, launches.
+
+// The wide batch kernels move rows as dwordx2 / dwordx4 per lane: their source tables must be 16-byte aligned.
+static bool wide_aligned(const void *a, const float *b, const float *c, const float *d)
+{
+    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & 15) == 0;
+}
+
+static const char *entry_name(const spex::BatchLaunch &L)      // the export that takes this form
+{
+    static const char *const names[2][2][3] = {                // [bpr][push][fp32 d == 64 | fp32 d = 128, 256 | bf16]
+        {{"spex_lightgcn_batch_slots_f32", "spex_lightgcn_batch_slots_f32", "spex_lightgcn_batch_slots_bf16_f32"},
+         {"spex_lightgcn_batch_f32", "spex_lightgcn_batch_f32", "spex_lightgcn_batch_bf16_f32"}},
+        {{"spex_lightgcn_bpr_batch_slots_f32", "spex_lightgcn_bpr_batch_slots_wide_f32", "spex_lightgcn_bpr_batch_slots_bf16_f32"},
+         {"spex_lightgcn_bpr_batch_f32", "spex_lightgcn_bpr_batch_wide_f32", "spex_lightgcn_bpr_batch_bf16_f32"}}};
+    return names[L.bpr][L.push][L.x_bf16 ? 2 : (L.d == kWave ? 0 : 1)];
+}
+
+template <bool PUSH>
+static void launch_f32(const spex::BatchLaunch &L, int parts, int runs_per_part)
+{
+    if (!L.bpr) {
+        if (L.d == kWave) launch_two_rows<float>(lightgcn_batch_kernel<PUSH>, L, parts, runs_per_part);
+        else if (L.d == 2 * kWave) launch_two_rows<float>(lightgcn_batch_wide_kernel<PUSH, 2>, L, parts, runs_per_part);
+        else launch_two_rows<float>(lightgcn_batch_wide_kernel<PUSH, 4>, L, parts, runs_per_part);
+    } else {
+        if (L.d == kWave) launch_three_rows<float>(lightgcn_bpr_batch_kernel<PUSH>, L, parts, runs_per_part);
+        else if (L.d == 2 * kWave) launch_three_rows<float>(lightgcn_bpr_batch_wide_kernel<PUSH, 2>, L, parts, runs_per_part);
+        else launch_three_rows<float>(lightgcn_bpr_batch_wide_kernel<PUSH, 4>, L, parts, runs_per_part);
+    }
+}
+
+int spex::batch_launch(const BatchLaunch &L)
+{
+    const char *who = L.who ? L.who : entry_name(L);
+    const spex_graph_t *g = L.g;
+    const int32_t n = L.n, n_u = L.n_user_rows, d = L.d;
+    const bool idx = L.a && L.b && (L.bpr ? L.c != nullptr : L.labels != nullptr), loss = L.loss_sum || L.loss_rows;
+    const bool l2_ok = L.weight_decay >= 0.0f && (L.weight_decay == 0.0f || L.E0), any_width = d == kWave || d == 2 * kWave || d == 4 * kWave;
+    if (L.x_bf16) {            // (the kernels walk the handle's CSR arrays, not its chunk tables: any handle will do)
+        if (d != kWave) {
+            spex::set_error("%s: bf16 gather tables are built for d == 64 only (d = %d): use the fp32 entries", who, d);
+            return SPEX_ERR_UNSUPPORTED;
+        }
+        SPEX_CHECK_ARG(g && L.X && L.acc_in && n >= 0 && L.acc_div != 0.0f && (!L.acc3 || L.acc2),
+                       "%s: NULL argument, a negative count, acc_div == 0 or acc3 without acc2", who);
+        SPEX_CHECK_ARG(n_u >= 0 && n_u <= g->n_rows && g->n_rows == g->n_cols, "%s: n_user_rows=%d on a %d x %d graph", who, n_u, g->n_rows, g->n_cols);
+        SPEX_CHECK_ARG((((uintptr_t)L.X) & 1) == 0 && L.X != (const void *)L.acc_in, "%s: X16 misaligned or aliasing acc_in", who);
+        if (!L.push) SPEX_CHECK_ARG((n == 0 || idx) && loss && L.slots, "%s: NULL argument", who);
+        else if (!L.bpr) SPEX_CHECK_ARG((n == 0 || idx) && loss && L.G && L.G != L.g_out, "%s: NULL argument (or G == g_out)", who);
+        else
+            SPEX_CHECK_ARG((n == 0 || idx) && loss && (L.G || L.g_out) && L.G != L.g_out,
+                           "%s: needs loss_sum or loss_per_sample, G and / or g_out (two tables)", who);
+        if (L.bpr) SPEX_CHECK_ARG(l2_ok, "%s: weight_decay %g needs E0 (and must not be negative)", who, (double)L.weight_decay);
+    } else if (L.bpr) {
+        SPEX_CHECK_ARG(g && L.X && L.acc_in && n >= 0 && (n == 0 || idx), "%s: NULL argument or T < 0", who);
+        SPEX_CHECK_ARG(n_u >= 0 && n_u <= g->n_rows && g->n_rows == g->n_cols, "%s: n_user_rows=%d on a %d x %d graph", who, n_u, g->n_rows, g->n_cols);
+        SPEX_CHECK_ARG(l2_ok, "%s: weight_decay %g needs E0 (and must not be negative)", who, (double)L.weight_decay);
+        // (the narrow exports promised d == 64 only — their callers' tables are 64 wide: a larger d would gather out of bounds — so
+        //  the wide kernel has exports of its own)
+        if (L.widths == BatchLaunch::kNarrow && d != kWave) {
+            spex::set_error("%s: d == 64 only (got %d); d = 128 / 256 take the _wide entry point", who, d);
+            return SPEX_ERR_UNSUPPORTED;
+        }
+        if (L.widths == BatchLaunch::kWide && d != 2 * kWave && d != 4 * kWave) {
+            spex::set_error("%s: d = 128 or 256 only (got %d); d == 64 takes the narrow entry point (the name without _wide)", who, d);
+            return SPEX_ERR_UNSUPPORTED;
+        }
+        if (!any_width) {
+            spex::set_error("%s: d = 64, 128 or 256 only (got %d)", who, d);
+            return SPEX_ERR_UNSUPPORTED;
+        }
+        if (!L.push)
+            SPEX_CHECK_ARG(loss && L.slots && L.acc_div != 0.0f && (!L.acc3 || L.acc2),
+                           "%s: needs loss_sum or loss_per_sample, grad_slots, acc_div != 0 (and acc2 with acc3)", who);
+        else
+            SPEX_CHECK_ARG(loss && (L.G || L.g_out) && L.G != L.g_out && L.acc_div != 0.0f && (!L.acc3 || L.acc2),
+                           "%s: needs loss_sum or loss_per_sample, G and / or g_out (two tables), acc_div != 0 (and acc2 with acc3)", who);
+        SPEX_CHECK_ARG(d == kWave || (wide_aligned(L.X, L.acc_in, L.acc2, L.acc3) && wide_aligned(L.E0, nullptr, nullptr, nullptr)),
+                       "%s: X / acc_in / E0 must be 16-byte aligned at d > 64", who);
+    } else {
+        SPEX_CHECK_ARG(g && L.X && L.acc_in && idx && loss && (L.push ? L.G : L.slots), "%s: NULL argument", who);
+        SPEX_CHECK_ARG(n >= 0 && n_u >= 0 && n_u <= g->n_rows, "%s: B=%d n_user_rows=%d", who, n, n_u);
+        SPEX_CHECK_ARG(g->n_rows == g->n_cols, "%s: square graph", who);
+        if (!any_width) {
+            spex::set_error("%s: d = 64, 128 or 256 only (got %d)", who, d);
+            return SPEX_ERR_UNSUPPORTED;
+        }
+        SPEX_CHECK_ARG(d == kWave || wide_aligned(L.X, L.acc_in, L.acc2, L.acc3), "%s: X / acc_in must be 16-byte aligned at d > 64", who);
+    }
+    if (n == 0 || g->n_rows == 0) return SPEX_OK;
+    // the slots form and the BPR form without a push (G == NULL): one workgroup per sample
+    const int parts = !L.push ? 1 : (L.bpr ? (L.G ? kBprBatchParts : 1) : kBatchParts);
+    const int runs_per_part = !L.push ? 1 : (L.bpr ? kBprBatchRunsPerPart : kBatchRunsPerPart);
+    SPEX_CHECK_ARG((int64_t)n * parts < (int64_t)1 << 31, "%s: %c=%d is too many %s for one launch", who, L.bpr ? 'T' : 'B', n,
+                   L.bpr ? "triples" : "samples");
+    if (L.x_bf16) return spex::batch_launch_bf16(L, parts, runs_per_part);
+    if (L.push) launch_f32<true>(L, parts, runs_per_part);
+    else launch_f32<false>(L, parts, runs_per_part);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
+}
+
+// ---- the ten exports: fillers of the descriptor.  (acc2 / acc3 stay NULL: the exports take one running sum.)
+static spex::BatchLaunch entry(const char *who, const spex_graph_t *g, const void *X, const float *acc_in, float acc_div, const int64_t *a,
+                               const int64_t *b, int32_t n, int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample,
+                               int32_t d, void *stream)
+{
+    spex::BatchLaunch L;
+    L.who = who; L.g = g; L.X = X; L.acc_in = acc_in; L.acc_div = acc_div; L.a = a; L.b = b; L.n = n; L.n_user_rows = n_user_rows;
+    L.grad_scale = grad_scale; L.loss_sum = loss_sum; L.loss_rows = loss_per_sample; L.d = d; L.stream = stream;
+    return L;
+}
+static void triples(spex::BatchLaunch &L, const int64_t *neg, float weight_decay, const float *E0, int32_t *row_counts,
+                    spex::BatchLaunch::Widths widths)
+{
+    L.bpr = true; L.c = neg; L.weight_decay = weight_decay; L.E0 = E0; L.row_counts = row_counts; L.widths = widths;
+}
+static void pushes(spex::BatchLaunch &L, float push_scale, float *g_out, float *G)
+{
+    L.push = true; L.push_scale = push_scale; L.g_out = g_out; L.G = G;
+}
+
 extern "C" int spex_lightgcn_batch_slots_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div,
                                              const int64_t *users, const int64_t *items, const float *labels, int32_t B,
                                              int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample,
                                              float *grad_slots, int32_t d, void *stream)
 {
-    return spex::lightgcn_batch_slots_layers(g, X, acc_in, nullptr, nullptr, acc_div, users, items, labels, B, n_user_rows, grad_scale,
-                                             loss_sum, loss_per_sample, grad_slots, d, stream);
-}
-
-int spex::lightgcn_batch_slots_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
-                                      float acc_div, const int64_t *users, const int64_t *items, const float *labels, int32_t B,
-                                      int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample, float *grad_slots,
-                                      int32_t d, void *stream)
-{
-    SPEX_CHECK_ARG(g && X && acc_in && users && items && labels && (loss_sum || loss_per_sample) && grad_slots,
-                   "spex_lightgcn_batch_slots_f32: NULL argument");
-    SPEX_CHECK_ARG(B >= 0 && n_user_rows >= 0 && n_user_rows <= g->n_rows, "spex_lightgcn_batch_slots_f32: B=%d n_user_rows=%d", B, n_user_rows);
-    SPEX_CHECK_ARG(g->n_rows == g->n_cols, "spex_lightgcn_batch_slots_f32: square graph");
-    if (d != kWave && d != 2 * kWave && d != 4 * kWave) {
-        spex::set_error("spex_lightgcn_batch_slots_f32: d = 64, 128 or 256 only (got %d)", d);
-        return SPEX_ERR_UNSUPPORTED;
-    }
-    SPEX_CHECK_ARG(d == kWave || wide_aligned(X, acc_in, acc2, acc3), "spex_lightgcn_batch_slots_f32: X / acc_in must be 16-byte aligned at d > 64");
-    if (B == 0 || g->n_rows == 0) return SPEX_OK;
-#define SPEX_GO(KERNEL)                                                                                                                    \
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)B), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val, g->n_rows,   \
-                       n_user_rows, X, acc_in, acc_div, users, items, labels, 1, grad_scale, 0.0f, loss_sum, loss_per_sample, nullptr,    \
-                       nullptr, 1, grad_slots, B, acc2, acc3, edge_drop_of(g))
-    if (d == kWave) SPEX_GO(lightgcn_batch_kernel<false>);
-    else if (d == 2 * kWave) SPEX_GO((lightgcn_batch_wide_kernel<false, 2>));
-    else SPEX_GO((lightgcn_batch_wide_kernel<false, 4>));
-#undef SPEX_GO
-    SPEX_HIP(hipGetLastError());
-    return SPEX_OK;
+    spex::BatchLaunch L = entry("spex_lightgcn_batch_slots_f32", g, X, acc_in, acc_div, users, items, B, n_user_rows, grad_scale, loss_sum,
+                                loss_per_sample, d, stream);
+    L.labels = labels; L.slots = grad_slots;
+    return spex::batch_launch(L);
 }
 
 extern "C" int spex_lightgcn_batch_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div,
@@ -1041,113 +771,11 @@ extern "C" int spex_lightgcn_batch_f32(const spex_graph_t *g, const float *X, co
                                        float *g_out, float *G, int32_t d, void *stream)
 {
     SPEX_CHECK_ARG(g_out, "spex_lightgcn_batch_f32: NULL g_out");
-    return spex::lightgcn_batch_layers(g, X, acc_in, nullptr, nullptr, acc_div, users, items, labels, B, n_user_rows, grad_scale, push_scale,
-                                       loss_sum, loss_per_sample, g_out, G, d, stream);
-}
-
-int spex::lightgcn_batch_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
-                                float acc_div, const int64_t *users, const int64_t *items, const float *labels, int32_t B,
-                                int32_t n_user_rows, float grad_scale, float push_scale, float *loss_sum, float *loss_per_sample, float *g_out,
-                                float *G, int32_t d, void *stream)
-{
-    SPEX_CHECK_ARG(g && X && acc_in && users && items && labels && (loss_sum || loss_per_sample) && G,
-                   "spex_lightgcn_batch_f32: NULL argument");
-    SPEX_CHECK_ARG(B >= 0 && n_user_rows >= 0 && n_user_rows <= g->n_rows, "spex_lightgcn_batch_f32: B=%d n_user_rows=%d", B, n_user_rows);
-    SPEX_CHECK_ARG(g->n_rows == g->n_cols, "spex_lightgcn_batch_f32: square graph");
-    if (d != kWave && d != 2 * kWave && d != 4 * kWave) {
-        spex::set_error("spex_lightgcn_batch_f32: d = 64, 128 or 256 only (got %d)", d);
-        return SPEX_ERR_UNSUPPORTED;
-    }
-    SPEX_CHECK_ARG(d == kWave || wide_aligned(X, acc_in, acc2, acc3), "spex_lightgcn_batch_f32: X / acc_in must be 16-byte aligned at d > 64");
-    if (B == 0 || g->n_rows == 0) return SPEX_OK;
-    constexpr int runs_per_part = kBatchRunsPerPart, parts = kBatchParts;
-#define SPEX_GO(KERNEL)                                                                                                                    \
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)B * parts), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val,      \
-                       g->n_rows, n_user_rows, X, acc_in, acc_div, users, items, labels, parts, grad_scale, push_scale, loss_sum,          \
-                       loss_per_sample, g_out, G, runs_per_part, nullptr, B, acc2, acc3, edge_drop_of(g))
-    if (d == kWave) SPEX_GO(lightgcn_batch_kernel<true>);
-    else if (d == 2 * kWave) SPEX_GO((lightgcn_batch_wide_kernel<true, 2>));
-    else SPEX_GO((lightgcn_batch_wide_kernel<true, 4>));
-#undef SPEX_GO
-    SPEX_HIP(hipGetLastError());
-    return SPEX_OK;
-}
-
-// ---- the BPR triple form.  The narrow exports promised d == 64 only (their callers' tables are 64 wide: a larger d would gather out
-//      of bounds), so the wide kernel has exports of its own; the internal *_layers forms dispatch on d (what the step calls).
-enum BprWidths { kBprNarrow, kBprWide, kBprAny };
-static int bpr_batch_check(const char *who, const spex_graph_t *g, const float *X, const float *acc_in, const int64_t *users,
-                           const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows, float weight_decay, const float *E0,
-                           int32_t d, BprWidths widths = kBprAny)
-{
-    SPEX_CHECK_ARG(g && X && acc_in && T >= 0 && (T == 0 || (users && pos && neg)), "%s: NULL argument or T < 0", who);
-    SPEX_CHECK_ARG(n_user_rows >= 0 && n_user_rows <= g->n_rows && g->n_rows == g->n_cols, "%s: n_user_rows=%d on a %d x %d graph", who,
-                   n_user_rows, g->n_rows, g->n_cols);
-    SPEX_CHECK_ARG(weight_decay >= 0.0f && (weight_decay == 0.0f || E0), "%s: weight_decay %g needs E0 (and must not be negative)", who,
-                   (double)weight_decay);
-    if (widths == kBprNarrow && d != kWave) {
-        spex::set_error("%s: d == 64 only (got %d); d = 128 / 256 take the _wide entry point", who, d);
-        return SPEX_ERR_UNSUPPORTED;
-    }
-    if (widths == kBprWide && d != 2 * kWave && d != 4 * kWave) {
-        spex::set_error("%s: d = 128 or 256 only (got %d); d == 64 takes the narrow entry point (the name without _wide)", who, d);
-        return SPEX_ERR_UNSUPPORTED;
-    }
-    if (d != kWave && d != 2 * kWave && d != 4 * kWave) {
-        spex::set_error("%s: d = 64, 128 or 256 only (got %d)", who, d);
-        return SPEX_ERR_UNSUPPORTED;
-    }
-    return SPEX_OK;
-}
-
-static int bpr_batch_slots_go(const char *who, BprWidths widths, const spex_graph_t *g, const float *X, const float *acc_in,
-                              const float *acc2, const float *acc3, float acc_div, const int64_t *users, const int64_t *pos,
-                              const int64_t *neg, int32_t T, int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0,
-                              int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream)
-{
-    int rc = bpr_batch_check(who, g, X, acc_in, users, pos, neg, T, n_user_rows, weight_decay, E0, d, widths);
-    if (rc != SPEX_OK) return rc;
-    SPEX_CHECK_ARG((loss_sum || loss_per_sample) && grad_slots && acc_div != 0.0f && (!acc3 || acc2),
-                   "%s: needs loss_sum or loss_per_sample, grad_slots, acc_div != 0 (and acc2 with acc3)", who);
-    SPEX_CHECK_ARG(d == kWave || (wide_aligned(X, acc_in, acc2, acc3) && wide_aligned(E0, nullptr, nullptr, nullptr)),
-                   "%s: X / acc_in / E0 must be 16-byte aligned at d > 64", who);
-    if (T == 0 || g->n_rows == 0) return SPEX_OK;
-#define SPEX_GO(KERNEL)                                                                                                                    \
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)T), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val, g->n_rows,   \
-                       n_user_rows, X, acc_in, acc_div, users, pos, neg, 1, grad_scale, 0.0f, loss_sum, loss_per_sample, nullptr, nullptr, \
-                       1, grad_slots, T, acc2, acc3, weight_decay, E0, row_counts, edge_drop_of(g))
-    if (d == kWave) SPEX_GO(lightgcn_bpr_batch_kernel<false>);
-    else if (d == 2 * kWave) SPEX_GO((lightgcn_bpr_batch_wide_kernel<false, 2>));
-    else SPEX_GO((lightgcn_bpr_batch_wide_kernel<false, 4>));
-#undef SPEX_GO
-    SPEX_HIP(hipGetLastError());
-    return SPEX_OK;
-}
-
-static int bpr_batch_go(const char *who, BprWidths widths, const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2,
-                        const float *acc3, float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
-                        int32_t n_user_rows, float grad_scale, float push_scale, float weight_decay, const float *E0, int32_t *row_counts,
-                        float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream)
-{
-    int rc = bpr_batch_check(who, g, X, acc_in, users, pos, neg, T, n_user_rows, weight_decay, E0, d, widths);
-    if (rc != SPEX_OK) return rc;
-    SPEX_CHECK_ARG((loss_sum || loss_per_sample) && (G || g_out) && G != g_out && acc_div != 0.0f && (!acc3 || acc2),
-                   "%s: needs loss_sum or loss_per_sample, G and / or g_out (two tables), acc_div != 0 (and acc2 with acc3)", who);
-    SPEX_CHECK_ARG(d == kWave || (wide_aligned(X, acc_in, acc2, acc3) && wide_aligned(E0, nullptr, nullptr, nullptr)),
-                   "%s: X / acc_in / E0 must be 16-byte aligned at d > 64", who);
-    if (T == 0 || g->n_rows == 0) return SPEX_OK;
-    const int parts = G ? kBprBatchParts : 1, runs_per_part = kBprBatchRunsPerPart;     // (no push: one workgroup per triple)
-    SPEX_CHECK_ARG((int64_t)T * parts < (int64_t)1 << 31, "%s: T=%d is too many triples for one launch", who, T);
-#define SPEX_GO(KERNEL)                                                                                                                    \
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)T * parts), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val,      \
-                       g->n_rows, n_user_rows, X, acc_in, acc_div, users, pos, neg, parts, grad_scale, push_scale, loss_sum,               \
-                       loss_per_sample, g_out, G, runs_per_part, nullptr, T, acc2, acc3, weight_decay, E0, row_counts, edge_drop_of(g))
-    if (d == kWave) SPEX_GO(lightgcn_bpr_batch_kernel<true>);
-    else if (d == 2 * kWave) SPEX_GO((lightgcn_bpr_batch_wide_kernel<true, 2>));
-    else SPEX_GO((lightgcn_bpr_batch_wide_kernel<true, 4>));
-#undef SPEX_GO
-    SPEX_HIP(hipGetLastError());
-    return SPEX_OK;
+    spex::BatchLaunch L = entry("spex_lightgcn_batch_f32", g, X, acc_in, acc_div, users, items, B, n_user_rows, grad_scale, loss_sum,
+                                loss_per_sample, d, stream);
+    L.labels = labels;
+    pushes(L, push_scale, g_out, G);
+    return spex::batch_launch(L);
 }
 
 extern "C" int spex_lightgcn_bpr_batch_slots_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div,
@@ -1156,8 +784,11 @@ extern "C" int spex_lightgcn_bpr_batch_slots_f32(const spex_graph_t *g, const fl
                                                  int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *grad_slots,
                                                  int32_t d, void *stream)
 {
-    return bpr_batch_slots_go("spex_lightgcn_bpr_batch_slots_f32", kBprNarrow, g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg, T,
-                              n_user_rows, grad_scale, weight_decay, E0, row_counts, loss_sum, loss_per_sample, grad_slots, d, stream);
+    spex::BatchLaunch L = entry("spex_lightgcn_bpr_batch_slots_f32", g, X, acc_in, acc_div, users, pos, T, n_user_rows, grad_scale, loss_sum,
+                                loss_per_sample, d, stream);
+    triples(L, neg, weight_decay, E0, row_counts, spex::BatchLaunch::kNarrow);
+    L.slots = grad_slots;
+    return spex::batch_launch(L);
 }
 
 extern "C" int spex_lightgcn_bpr_batch_slots_wide_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div,
@@ -1166,18 +797,11 @@ extern "C" int spex_lightgcn_bpr_batch_slots_wide_f32(const spex_graph_t *g, con
                                                       int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *grad_slots,
                                                       int32_t d, void *stream)
 {
-    return bpr_batch_slots_go("spex_lightgcn_bpr_batch_slots_wide_f32", kBprWide, g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg,
-                              T, n_user_rows, grad_scale, weight_decay, E0, row_counts, loss_sum, loss_per_sample, grad_slots, d, stream);
-}
-
-int spex::lightgcn_bpr_batch_slots_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
-                                          float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
-                                          int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0, int32_t *row_counts,
-                                          float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream)
-{
-    return bpr_batch_slots_go(d == kWave ? "spex_lightgcn_bpr_batch_slots_f32" : "spex_lightgcn_bpr_batch_slots_wide_f32", kBprAny, g, X,
-                              acc_in, acc2, acc3, acc_div, users, pos, neg, T, n_user_rows, grad_scale, weight_decay, E0, row_counts,
-                              loss_sum, loss_per_sample, grad_slots, d, stream);
+    spex::BatchLaunch L = entry("spex_lightgcn_bpr_batch_slots_wide_f32", g, X, acc_in, acc_div, users, pos, T, n_user_rows, grad_scale,
+                                loss_sum, loss_per_sample, d, stream);
+    triples(L, neg, weight_decay, E0, row_counts, spex::BatchLaunch::kWide);
+    L.slots = grad_slots;
+    return spex::batch_launch(L);
 }
 
 extern "C" int spex_lightgcn_bpr_batch_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div, const int64_t *users,
@@ -1185,8 +809,11 @@ extern "C" int spex_lightgcn_bpr_batch_f32(const spex_graph_t *g, const float *X
                                            float push_scale, float weight_decay, const float *E0, int32_t *row_counts, float *loss_sum,
                                            float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream)
 {
-    return bpr_batch_go("spex_lightgcn_bpr_batch_f32", kBprNarrow, g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg, T, n_user_rows,
-                        grad_scale, push_scale, weight_decay, E0, row_counts, loss_sum, loss_per_sample, g_out, G, d, stream);
+    spex::BatchLaunch L = entry("spex_lightgcn_bpr_batch_f32", g, X, acc_in, acc_div, users, pos, T, n_user_rows, grad_scale, loss_sum,
+                                loss_per_sample, d, stream);
+    triples(L, neg, weight_decay, E0, row_counts, spex::BatchLaunch::kNarrow);
+    pushes(L, push_scale, g_out, G);
+    return spex::batch_launch(L);
 }
 
 extern "C" int spex_lightgcn_bpr_batch_wide_f32(const spex_graph_t *g, const float *X, const float *acc_in, float acc_div,
@@ -1195,19 +822,62 @@ extern "C" int spex_lightgcn_bpr_batch_wide_f32(const spex_graph_t *g, const flo
                                                 int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *g_out, float *G,
                                                 int32_t d, void *stream)
 {
-    return bpr_batch_go("spex_lightgcn_bpr_batch_wide_f32", kBprWide, g, X, acc_in, nullptr, nullptr, acc_div, users, pos, neg, T,
-                        n_user_rows, grad_scale, push_scale, weight_decay, E0, row_counts, loss_sum, loss_per_sample, g_out, G, d, stream);
+    spex::BatchLaunch L = entry("spex_lightgcn_bpr_batch_wide_f32", g, X, acc_in, acc_div, users, pos, T, n_user_rows, grad_scale, loss_sum,
+                                loss_per_sample, d, stream);
+    triples(L, neg, weight_decay, E0, row_counts, spex::BatchLaunch::kWide);
+    pushes(L, push_scale, g_out, G);
+    return spex::batch_launch(L);
 }
 
-int spex::lightgcn_bpr_batch_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
-                                    float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
-                                    int32_t n_user_rows, float grad_scale, float push_scale, float weight_decay, const float *E0,
-                                    int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d,
-                                    void *stream)
+// (the four d == 64 forms with the last layer gathered from a bf16 table X16: kernels and launch in batch_bf16.hip)
+extern "C" int spex_lightgcn_batch_slots_bf16_f32(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, float acc_div,
+                                                  const int64_t *users, const int64_t *items, const float *labels, int32_t B,
+                                                  int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample,
+                                                  float *grad_slots, int32_t d, void *stream)
 {
-    return bpr_batch_go(d == kWave ? "spex_lightgcn_bpr_batch_f32" : "spex_lightgcn_bpr_batch_wide_f32", kBprAny, g, X, acc_in, acc2, acc3,
-                        acc_div, users, pos, neg, T, n_user_rows, grad_scale, push_scale, weight_decay, E0, row_counts, loss_sum,
-                        loss_per_sample, g_out, G, d, stream);
+    spex::BatchLaunch L = entry("spex_lightgcn_batch_slots_bf16_f32", g, X16, acc_in, acc_div, users, items, B, n_user_rows, grad_scale,
+                                loss_sum, loss_per_sample, d, stream);
+    L.x_bf16 = true; L.labels = labels; L.slots = grad_slots;
+    return spex::batch_launch(L);
+}
+
+extern "C" int spex_lightgcn_batch_bf16_f32(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, float acc_div,
+                                            const int64_t *users, const int64_t *items, const float *labels, int32_t B, int32_t n_user_rows,
+                                            float grad_scale, float push_scale, float *loss_sum, float *loss_per_sample, float *g_out,
+                                            float *G, int32_t d, void *stream)
+{
+    SPEX_CHECK_ARG(g_out, "spex_lightgcn_batch_bf16_f32: NULL g_out");
+    spex::BatchLaunch L = entry("spex_lightgcn_batch_bf16_f32", g, X16, acc_in, acc_div, users, items, B, n_user_rows, grad_scale, loss_sum,
+                                loss_per_sample, d, stream);
+    L.x_bf16 = true; L.labels = labels;
+    pushes(L, push_scale, g_out, G);
+    return spex::batch_launch(L);
+}
+
+extern "C" int spex_lightgcn_bpr_batch_slots_bf16_f32(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, float acc_div,
+                                                      const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
+                                                      int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0,
+                                                      int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *grad_slots,
+                                                      int32_t d, void *stream)
+{
+    spex::BatchLaunch L = entry("spex_lightgcn_bpr_batch_slots_bf16_f32", g, X16, acc_in, acc_div, users, pos, T, n_user_rows, grad_scale,
+                                loss_sum, loss_per_sample, d, stream);
+    triples(L, neg, weight_decay, E0, row_counts, spex::BatchLaunch::kAnyWidth);
+    L.x_bf16 = true; L.slots = grad_slots;
+    return spex::batch_launch(L);
+}
+
+extern "C" int spex_lightgcn_bpr_batch_bf16_f32(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, float acc_div,
+                                                const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows,
+                                                float grad_scale, float push_scale, float weight_decay, const float *E0, int32_t *row_counts,
+                                                float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream)
+{
+    spex::BatchLaunch L = entry("spex_lightgcn_bpr_batch_bf16_f32", g, X16, acc_in, acc_div, users, pos, T, n_user_rows, grad_scale, loss_sum,
+                                loss_per_sample, d, stream);
+    triples(L, neg, weight_decay, E0, row_counts, spex::BatchLaunch::kAnyWidth);
+    L.x_bf16 = true;
+    pushes(L, push_scale, g_out, G);
+    return spex::batch_launch(L);
 }
 
 int spex::rows_train_push(const spex_graph_t *push, const float *rows_raw, const float *rows_prop, const float *att_u, const float *att_i,

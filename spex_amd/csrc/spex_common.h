@@ -61,44 +61,32 @@ int trust_head_train(const float *table, int64_t n_rows, const float *params, co
                      const float *scale_dev, float *a2, float *dscore, float *loss_b, float *ws, float *loss_out, int32_t loss_accumulate,
                      float *grad_params, float *grad_table, int32_t split_cap, void *stream);
 
-// batch.hip: the batch kernels with the layer sum formed at the batch's rows from up to three tables (acc_in + acc2 + acc3, in that
-// order; NULL = absent) — what lets the one-call steps run their forward layers in the plain form
-int lightgcn_batch_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3, float acc_div,
-                          const int64_t *users, const int64_t *items, const float *labels, int32_t B, int32_t n_user_rows, float grad_scale,
-                          float push_scale, float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream);
-int lightgcn_batch_slots_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
-                                float acc_div, const int64_t *users, const int64_t *items, const float *labels, int32_t B,
-                                int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d,
-                                void *stream);
-// (the exact BPR step's batch-sized middle, three rows per triple; d = 64, or 128 / 256 through the wide kernel: batch.hip)
-int lightgcn_bpr_batch_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
-                              float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T, int32_t n_user_rows,
-                              float grad_scale, float push_scale, float weight_decay, const float *E0, int32_t *row_counts,
-                              float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d, void *stream);
-int lightgcn_bpr_batch_slots_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3,
-                                    float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
-                                    int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0, int32_t *row_counts,
-                                    float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d, void *stream);
-// batch_bf16.hip: the four d == 64 forms above with the last layer gathered from a bf16 table (X16: rows of 128 bytes); everything
-// else — the layer sum from the fp32 tables, scores, loss, gradient rows, L2 counts, the push into fp32 slots — is the same statement
-int lightgcn_batch_bf16_layers(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, const float *acc2, const float *acc3,
-                               float acc_div, const int64_t *users, const int64_t *items, const float *labels, int32_t B,
-                               int32_t n_user_rows, float grad_scale, float push_scale, float *loss_sum, float *loss_per_sample, float *g_out,
-                               float *G, int32_t d, void *stream);
-int lightgcn_batch_slots_bf16_layers(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, const float *acc2, const float *acc3,
-                                     float acc_div, const int64_t *users, const int64_t *items, const float *labels, int32_t B,
-                                     int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample, float *grad_slots,
-                                     int32_t d, void *stream);
-int lightgcn_bpr_batch_bf16_layers(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, const float *acc2, const float *acc3,
-                                   float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t T,
-                                   int32_t n_user_rows, float grad_scale, float push_scale, float weight_decay, const float *E0,
-                                   int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *g_out, float *G, int32_t d,
-                                   void *stream);
-int lightgcn_bpr_batch_slots_bf16_layers(const spex_graph_t *g, const uint16_t *X16, const float *acc_in, const float *acc2,
-                                         const float *acc3, float acc_div, const int64_t *users, const int64_t *pos, const int64_t *neg,
-                                         int32_t T, int32_t n_user_rows, float grad_scale, float weight_decay, const float *E0,
-                                         int32_t *row_counts, float *loss_sum, float *loss_per_sample, float *grad_slots, int32_t d,
-                                         void *stream);
+// batch.hip: one launch of the batch-sized middle of an exact LightGCN step, described by value.  The layer sum is
+// formed at the batch's rows from up to three tables (acc_in + acc2 + acc3, in that order; NULL = absent) — what lets the one-call
+// steps run their forward layers in the plain form.  The ten spex_lightgcn_[bpr_]batch_* exports and steps.hip fill one of these.
+struct BatchLaunch {
+    enum Widths { kAnyWidth, kNarrow, kWide };     // the narrow / _wide BPR exports promise one width each (their callers' tables)
+    const char *who = nullptr;                     // the entry's name for messages; NULL: the export that takes this form
+    bool bpr = false;                              // triples (a, b, c) = (user, positive, negative), three rows; else samples (a, b, labels)
+    bool push = false;                             // atomics into g_out / G and the push; else per-sample rows into `slots`, no float atomic
+    bool x_bf16 = false;                           // X is a bf16 table (rows of 128 bytes, d == 64: batch_bf16.hip), else fp32
+    Widths widths = kAnyWidth;
+    const spex_graph_t *g = nullptr;
+    const void *X = nullptr;                       // the table the last layer gathers from
+    const float *acc_in = nullptr, *acc2 = nullptr, *acc3 = nullptr;
+    float acc_div = 1.0f;
+    const int64_t *a = nullptr, *b = nullptr, *c = nullptr;
+    const float *labels = nullptr;
+    int32_t n = 0, n_user_rows = 0;                // samples or triples
+    float grad_scale = 0.0f, push_scale = 0.0f, weight_decay = 0.0f;
+    const float *E0 = nullptr;                     // the L2 term's rows (bpr, weight_decay > 0)
+    int32_t *row_counts = nullptr;                 // the L2 gradient's occurrence counts (bpr)
+    float *loss_sum = nullptr, *loss_rows = nullptr, *g_out = nullptr, *G = nullptr, *slots = nullptr;
+    int32_t d = 0;
+    void *stream = nullptr;
+};
+int batch_launch(const BatchLaunch &L);                                   // batch.hip: checks the descriptor, then launches its kernel
+int batch_launch_bf16(const BatchLaunch &L, int parts, int runs_per_part);  // batch_bf16.hip: the launch alone (batch_launch has checked)
 int gated_batch_fwd_layers(const spex_graph_t *g, const float *X, const float *acc_in, const float *acc2, const float *acc3, float acc_div,
                            const float *raw, const float *att_u, const float *att_i, const int64_t *users, const int64_t *items,
                            const float *labels, int32_t B, int32_t n_user_rows, float grad_scale, float *loss_sum, float *loss_per_sample,
@@ -283,7 +271,7 @@ struct WideVec {
     typedef float T __attribute__((ext_vector_type(V)));
 };
 
-// One 64-entry segment [e0, e0 + cnt) of a row at width 64 V — segment_sum / segment_sum_masked of batch.hip with V columns per
+// One 64-entry segment [e0, e0 + cnt) of a row at width 64 V — segment_sum<MASKED> of batch_kernels.h with V columns per
 // lane.  The d == 64 form keeps the segment's 64 gathered floats in registers; at the same 64 result registers a wave here keeps
 // 64 / V gathers in flight (32 rows of 512 B, 16 rows of 1 KB: 16 KB per wave at every width) and walks the segment in V passes —
 // the kernels run 1 024-thread workgroups, i.e. 4 waves per SIMD and at most 128 VGPRs.  Every column's fmaf chain runs in entry
@@ -445,3 +433,10 @@ struct spex_graph {
     uint64_t seed = 0;
     spex_timer *timer = nullptr;  // profiling hook (not owned)
 };
+
+namespace spex {
+inline EdgeDrop edge_drop_of(const spex_graph_t *g)      // the handle's edge-dropout state as the kernels take it
+{
+    return EdgeDrop{g->keep, g->edge_id, g->mask_mode, g->keep_prob, (uint32_t)g->seed, (uint32_t)(g->seed >> 32)};
+}
+}  // namespace spex

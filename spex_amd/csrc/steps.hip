@@ -7,7 +7,7 @@
 // Nothing here computes: every launch is one of the library's own entry points.
 //
 // The BCE and the exact BPR LightGCN steps are ONE schedule, lightgcn_step, built from named pieces: step_check, the optional
-// sparse-Adam clear and frontier lists, step_forward, the kind's batch launch (bce_batch / bpr_batch), the backward behind it
+// sparse-Adam clear and frontier lists, step_forward, the kind's batch launch (step_batch), the backward behind it
 // (bf16_backward_push, frontier_backward, step_backward_pulls) and one closing Adam launch.  What the kinds do NOT share, and the
 // schedule keeps: BCE at L == 1 scores through spex_spmm_rowlist_f32 + spex_score_bce_slots_f32 and one pull product, BPR at L == 1
 // runs the push form with the push target as the gradient; the deterministic BCE step reduces its slots in one call, the BPR step in
@@ -314,39 +314,27 @@ static int step_backward_pulls(const spex_graph *gt, const float *src, int32_t l
 
 // The batch launch of either kind in its forms, from the fp32 or the bf16 table: slots given — per-sample gradient rows, nothing added
 // anywhere (SPEX_STEP_DETERMINISTIC); otherwise atomics into `dense` (NULL: not formed) and, G given, the first backward product
-// (g + A^T g) * push_scale in push form into G.
-static int bce_batch(const spex_lightgcn_step_t *s, const StepBatch &k, const StepTables &f, float push_scale, float *loss_rows, float *slots,
-                     float *dense, float *G, void *stream)
+// (g + A^T g) * push_scale in push form into G.  counts: the BPR kind's L2 occurrence counts (NULL: no L2 term).
+static int step_batch(const spex_lightgcn_step_t *s, const StepBatch &k, const StepTables &f, bool bpr, int32_t *counts, float push_scale,
+                      float *loss_rows, float *slots, float *dense, float *G, void *stream)
 {
-    const spex_graph *g = s->graph;
-    const int32_t n_u = s->n_user_rows, d = s->d;
-    const float n_sum = (float)(s->L + 1), scale = 1.0f / (float)k.n;
-    if (slots)
-        return f.cur16 ? spex::lightgcn_batch_slots_bf16_layers(g, f.cur16, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.labels, k.n, n_u, scale, nullptr,
-                                                                loss_rows, slots, d, stream)
-                       : spex::lightgcn_batch_slots_layers(g, f.cur, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.labels, k.n, n_u, scale, nullptr,
-                                                           loss_rows, slots, d, stream);
-    return f.cur16 ? spex::lightgcn_batch_bf16_layers(g, f.cur16, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.labels, k.n, n_u, scale, push_scale, nullptr,
-                                                      loss_rows, dense, G, d, stream)
-                   : spex::lightgcn_batch_layers(g, f.cur, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.labels, k.n, n_u, scale, push_scale, nullptr,
-                                                 loss_rows, dense, G, d, stream);
-}
-
-static int bpr_batch(const spex_lightgcn_step_t *s, const StepBatch &k, const StepTables &f, int32_t *counts, float push_scale, float *loss_rows,
-                     float *slots, float *dense, float *G, void *stream)
-{
-    const spex_graph *g = s->graph;
-    const int32_t n_u = s->n_user_rows, d = s->d;
-    const float n_sum = (float)(s->L + 1), scale = 1.0f / (float)k.n, wd = s->weight_decay;
-    if (slots)
-        return f.cur16 ? spex::lightgcn_bpr_batch_slots_bf16_layers(g, f.cur16, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.c, k.n, n_u, scale, wd, s->E0,
-                                                                    counts, nullptr, loss_rows, slots, d, stream)
-                       : spex::lightgcn_bpr_batch_slots_layers(g, f.cur, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.c, k.n, n_u, scale, wd, s->E0, counts,
-                                                               nullptr, loss_rows, slots, d, stream);
-    return f.cur16 ? spex::lightgcn_bpr_batch_bf16_layers(g, f.cur16, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.c, k.n, n_u, scale, push_scale, wd, s->E0,
-                                                          counts, nullptr, loss_rows, dense, G, d, stream)
-                   : spex::lightgcn_bpr_batch_layers(g, f.cur, f.sum0, f.sum1, f.sum2, n_sum, k.a, k.b, k.c, k.n, n_u, scale, push_scale, wd, s->E0, counts,
-                                                     nullptr, loss_rows, dense, G, d, stream);
+    spex::BatchLaunch b;
+    b.bpr = bpr; b.push = slots == nullptr; b.x_bf16 = f.cur16 != nullptr;
+    b.g = s->graph; b.X = f.cur16 ? (const void *)f.cur16 : (const void *)f.cur;
+    b.acc_in = f.sum0; b.acc2 = f.sum1; b.acc3 = f.sum2; b.acc_div = (float)(s->L + 1);
+    b.a = k.a; b.b = k.b; b.c = bpr ? k.c : nullptr; b.labels = bpr ? nullptr : k.labels;
+    b.n = k.n; b.n_user_rows = s->n_user_rows; b.grad_scale = 1.0f / (float)k.n;
+    if (bpr) {
+        b.weight_decay = s->weight_decay; b.E0 = s->E0; b.row_counts = counts;
+    }
+    b.loss_rows = loss_rows;
+    if (slots) {
+        b.slots = slots;
+    } else {
+        b.push_scale = push_scale; b.g_out = dense; b.G = G;
+    }
+    b.d = s->d; b.stream = stream;
+    return spex::batch_launch(b);
 }
 
 static int lightgcn_step(spex_lightgcn_step_t *s, const StepBatch &k, void *stream);
@@ -476,8 +464,7 @@ static int lightgcn_step(spex_lightgcn_step_t *s, const StepBatch &k, void *stre
     StepTables f;
     SPEX_TRY(step_forward(s, sz, stream, &f));
     auto batch = [&](float push_scale, float *loss_rows, float *slots, float *dense, float *G) -> int {
-        return bpr ? bpr_batch(s, k, f, counts, push_scale, loss_rows, slots, dense, G, stream)
-                   : bce_batch(s, k, f, push_scale, loss_rows, slots, dense, G, stream);
+        return step_batch(s, k, f, bpr, counts, push_scale, loss_rows, slots, dense, G, stream);
     };
     // the whole backward in pull form from the dense d loss / d light_out
     auto backward_dense = [&]() -> int {
