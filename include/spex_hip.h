@@ -448,6 +448,16 @@ int spex_frontier_rows_i32(const spex_graph_t *g, int32_t *list, const int32_t *
  * pass) strides over the list, the count is read on the device.  d == 64 without edge dropout only: otherwise SPEX_ERR_UNSUPPORTED. */
 int spex_spmm_rowlist_dev_f32(const spex_graph_t *g, const float *X, const int32_t *list, const int32_t *count, int32_t max_count,
                               float *Y, const float *acc_in, float *acc_out, float acc_div, int32_t d, void *stream);
+/* spex_spmm_rowlist_dev_f32 gathering from a bf16 table X16 ([n_cols, 64], rows of 128 bytes; widening is exact): the same kernel body
+ * instantiated for the other element type, so on Xw = float(X16) it returns in Y what spex_spmm_rowlist_dev_f32 returns on Xw, bit for
+ * bit, for EVERY listed row (hubs included: the same segments are added in the same order) — hence spex_spmm_bf16_f32's rows on rows
+ * of up to 1 024 entries.  Outputs, each optional but at least one given: Y (fp32), Y16 = bf16(the same register), round to nearest
+ * even (= spex_cast_bf16_f32(Y) bit for bit), acc_out = (acc_in + y) / acc_div (may alias acc_in).  Rows outside the list are written
+ * in no output; list values outside [0, n_rows) are skipped; *count is cut at max_count.  d != 64 or an edge mask on the handle ->
+ * SPEX_ERR_UNSUPPORTED; a NULL graph / X16 / list / count, no output, acc_out without acc_in, X16 aliasing an output or acc_in, or
+ * Y / Y16 aliasing each other or the running sum -> SPEX_ERR_INVALID. */
+int spex_spmm_rowlist_dev_bf16_f32(const spex_graph_t *g, const uint16_t *X16, const int32_t *list, const int32_t *count, int32_t max_count,
+                                   float *Y, uint16_t *Y16, const float *acc_in, float *acc_out, float acc_div, int32_t d, void *stream);
 /* The same product driven by the batch itself (d = 64, 128 or 256), EVERY slot contributing its own row: for slot k with row
  * r = idx_a[k] + off_a (k < n_a) or idx_b[k - n_a] + off_b:
  *   out[col[e], :] += scale * val[e] * src[k, :]  over the stored entries e of row r;   out[r, :] += scale * add[k, :] (if add)
@@ -972,7 +982,8 @@ enum {
                                          * and L = 2 or 3 only; the descriptor's E0_16 / ws16 fields are read (see spex_lightgcn_step_t) */
     SPEX_STEP_FRONTIER = 128,           /* the one-call LightGCN steps (BCE, exact BPR) and every epoch over them: forward layer L - 1 and the
                                          * backward product behind the batch kernel's push run over the batch's frontier, not the whole
-                                         * graph; d == 64, L >= 2; the descriptor's frontier_* fields are read (see spex_lightgcn_step_t) */
+                                         * graph; d == 64, L >= 2; the descriptor's frontier_* fields are read (see spex_lightgcn_step_t).
+                                         * Combines with SPEX_STEP_BF16_GATHER (then L = 2 or 3): the frontier launches read bf16 tables */
     SPEX_STEP_SPARSE_ADAM = 256,        /* with SPEX_STEP_FRONTIER at L == 2 only: row-sparse ("lazy") Adam — p, m, v change at the rows of the
                                          * batch's two-hop set F2 and nowhere else, the step count is global; no launch of the step but the
                                          * first flagged one passes over a whole fp32 table.  Its own semantics: see spex_lightgcn_step_t */
@@ -1073,9 +1084,10 @@ typedef struct spex_lightgcn_step {
  * SPEX_STEP_GRAD_ROWS_LISTED (see the flag); without the bit it clears the whole table once.  The exact BPR step clears the other
  * parity's row_counts table whole (4 N bytes) instead of in the Adam pass; the tables satisfy the same contract afterwards.
  * g_out and ws_bwd[0] are all-zero after every step, as without the flag.
- * Refused before anything touches the device (t not advanced): SPEX_STEP_SPARSE_ADAM without SPEX_STEP_FRONTIER, or with L != 2 ->
- * SPEX_ERR_INVALID; everything SPEX_STEP_FRONTIER refuses stays refused. */
-/* flags & SPEX_STEP_FRONTIER — the exact steps with one more level taken inward (d == 64, L >= 2, fp32 tables).  With Bset the batch's
+ * Refused before anything touches the device (t not advanced): SPEX_STEP_SPARSE_ADAM without SPEX_STEP_FRONTIER, with L != 2, or
+ * together with SPEX_STEP_BF16_GATHER (the row-sparse pass keeps no bf16 shadow of E0) -> SPEX_ERR_INVALID; everything
+ * SPEX_STEP_FRONTIER refuses stays refused. */
+/* flags & SPEX_STEP_FRONTIER — the exact steps with one more level taken inward (d == 64, L >= 2).  With Bset the batch's
  * distinct rows and F1 = Bset U their stored columns (spex_unique_rows_i32 + spex_frontier_rows_i32 into frontier_list):
  *   forward:   layers 1 .. L - 2 over the whole graph as without the flag; layer L - 1 at the rows of F1 only
  *              (spex_spmm_rowlist_dev_f32, the same table and, at L >= 4, the same running sum, valid at F1); the batch kernel is
@@ -1086,8 +1098,23 @@ typedef struct spex_lightgcn_step {
  *              plain, the Adam pass adds P; L >= 4: with the g_out / (L + 1) term).  The remaining L - 2 products are whole-graph pulls.
  * L == 2 has no whole-graph launch left.  The exact BPR step takes the push form at any T.  Refused before anything touches the device
  * (t not advanced): d != 64 or SPEX_STEP_WIDE -> SPEX_ERR_UNSUPPORTED; L < 2, SPEX_STEP_DETERMINISTIC (the second push uses float
- * atomics), SPEX_STEP_BF16_GATHER, SPEX_STEP_BPR_DENSE, an edge-dropout mask on a handle (also the epochs' keep_prob < 1), a NULL
- * frontier_* field -> SPEX_ERR_INVALID. */
+ * atomics), SPEX_STEP_BPR_DENSE, an edge-dropout mask on a handle (also the epochs' keep_prob < 1), a NULL frontier_* field ->
+ * SPEX_ERR_INVALID.
+ * With SPEX_STEP_BF16_GATHER (L = 2 or 3; that flag's own rules hold on top) the frontier launches read bf16 tables:
+ *   forward:   L == 3: y_1 = A E0_16 over the whole graph (spex_spmm_bf16_f32 into ws_fwd[0] and ws16[0], the bf16 step's own launch),
+ *              then y_2 at the rows of F1 from ws16[0] into ws_fwd[1] and ws16[1] (spex_spmm_rowlist_dev_bf16_f32).  L == 2: y_1 at F1
+ *              from E0_16 into ws_fwd[0] and ws16[0]; no whole-graph launch is left.  The bf16 batch kernels gather from ws16[L - 2];
+ *              everything they read lies in F1, and the layer sum uses the fp32 E0 and ws_fwd rows as without SPEX_STEP_FRONTIER.
+ *   backward:  the frontier push reads the fp32 P.  L == 2: into grad_E0, done; the Adam pass adds g_out / 3.  L == 3: into
+ *              W = ws_bwd[1], then one spex_cast_bf16_f32(W -> ws16[0]) and grad_E0 = A^T bf16(W) by one plain spex_spmm_bf16_f32 on
+ *              graph_t; the Adam pass adds P.  Straight-through with ONE rounding, of W, where the whole-graph bf16 step has two
+ *              (of P and of A^T bf16(P)).
+ *   Adam:      the bf16 step's: E0_16 == bf16(E0) after every step.
+ * Where the pair pays (one-call steps on an MI355X): at L == 3 on graphs that stream from HBM — 30.70 ms per BCE step
+ * (B = 256) on a 2^24-node graph against 41.77 ms with SPEX_STEP_FRONTIER alone and 49.98 ms with SPEX_STEP_BF16_GATHER alone, 1.26 -
+ * 1.39 x / 1.06 - 1.83 x over all L == 3 cells at 2^22 and 2^24 nodes.  Where it loses: at L == 2 it is 0 - 7 % slower than
+ * SPEX_STEP_FRONTIER alone (9.82 against 9.18 ms; no whole-graph launch is left to halve, the Adam pass gains the shadow store), and
+ * on a cache-resident graph (Epinion2) both flags lose to the plain fp32 step, together 186.9 us against 45.6 us. */
 /* flags & SPEX_STEP_BF16_GATHER — the mixed-precision mode of spex_propagate_bf16_f32 carried through the one-call steps, d == 64,
  * L = 2 or 3 (spex_lightgcn_step_bce_f32, spex_lightgcn_step_bpr_adam_f32 and, through them, every epoch, sampled-epoch and
  * train_*_sampled call).  Rounding enters only where a table becomes a gather source; every product, sum and the layer mean stay

@@ -439,109 +439,14 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_rowlist_kernel(
     }
 }
 
-// Row-list SpMM driven by a DEVICE list (a frontier: 10^4 .. 10^5 mostly short rows, median 13 entries): the row-list kernel's
-// arithmetic in another work split.  A 16-wave workgroup takes 16 list slots per pass of a fixed grid that strides over the list (the
-// count is read on the device).  Pass part 1: wave w owns slot w; a row of at most 64 entries is ONE wave task — gathered, finished
-// and written by that wave.  Part 2: the longer rows of the 16 slots are cut into wave tasks of one 64-entry segment — a row beyond
-// 1 024 entries into 16 tasks, task p chaining segments p, p + 16, .. as the row-list kernel's wave p does — the tasks of as many rows
-// as fit kDevTasks LDS slots are dealt round-robin to the 16 waves, and each row's partial sums are added in segment order by one
-// wave: the row-list kernel's summation order for every row, i.e. spex_spmm_f32's bits for rows of up to 1 024 entries.
-// List entries are distinct, so acc_out may alias acc_in; rows outside the list are not written.
-constexpr int kDevTasks = 64;
-constexpr int kDevMaxWgs = 1024;
-
-__device__ __forceinline__ float rowlist_segments(const int32_t *__restrict__ col, const float *__restrict__ val, const float *__restrict__ Xl,
-                                                  int beg, int deg, int first, int nseg, int lane, float acc)
-{
-    for (int sgi = first; sgi < nseg; sgi += kWgWaves) {
-        const int e0 = beg + sgi * kTaskEntries;
-        const int cnt = (deg - sgi * kTaskEntries < kTaskEntries) ? deg - sgi * kTaskEntries : kTaskEntries;
-        int my_col = 0;
-        float my_val = 0.0f;
-        if (lane < cnt) {
-            my_col = col[e0 + lane];
-            my_val = val[e0 + lane];
-        }
-        // entries past the segment's end: value 0 on the segment's last real source row (a line already being fetched)
-        const int last_col = __builtin_amdgcn_readlane(my_col, (cnt - 1) & 63);
-        if (lane >= cnt) my_col = last_col;
-        for (int c = 0; c * kChunk < cnt; ++c) {
-            float x[kChunk];
-#pragma unroll
-            for (int u = 0; u < kChunk; ++u)
-                x[u] = Xl[(size_t)(uint32_t)__builtin_amdgcn_readlane(my_col, c * kChunk + u) * 64];
-#pragma unroll
-            for (int u = 0; u < kChunk; ++u) acc = fmaf(lane_bcast(my_val, c * kChunk + u), x[u], acc);
-        }
-    }
-    return acc;
-}
-
-__device__ __forceinline__ void rowlist_dev_finish(int r, int lane, float y, float *Y, const float *acc_in, float *acc_out, float acc_div)
-{
-    const size_t o = (size_t)r * 64 + lane;
-    if (Y) Y[o] = y;
-    if (acc_out) {
-        float s = acc_in[o] + y;
-        if (acc_div != 1.0f) s = s / acc_div;
-        acc_out[o] = s;
-    }
-}
-
+// Row-list SpMM driven by a DEVICE list: rowlist_dev_body (spmm_chunk.h, where the work split is described) on a float table;
+// spmm_bf16.hip wraps the same body for a bf16 one.
 __global__ __launch_bounds__(kWave *kWgWaves) void spmm_rowlist_dev_kernel(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
     const float *__restrict__ X, const int32_t *__restrict__ list, const int32_t *__restrict__ count, int32_t max_count,
     int32_t n_rows, float *Y, const float *acc_in, float *acc_out, float acc_div)     // (acc_out may alias acc_in: unqualified)
 {
-    __shared__ float s_part[kDevTasks][kWave];
-    __shared__ int s_nt[kWgWaves];                 // tasks of each of the pass's 16 slots (0: no row, or a row of one segment)
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int n = *count < max_count ? *count : max_count;
-    const float *__restrict__ Xl = X + lane;
-    for (int k0 = blockIdx.x * kWgWaves; k0 < n; k0 += gridDim.x * kWgWaves) {      // workgroup-uniform
-        // ---- part 1: one slot per wave
-        int r = -1, beg = 0, deg = 0;
-        if (k0 + wave < n) {
-            r = list[k0 + wave];
-            if (r < 0 || r >= n_rows) r = -1;      // never index the matrix out of range
-        }
-        if (r >= 0) {
-            beg = rowptr[r];
-            deg = rowptr[r + 1] - beg;
-        }
-        const int nseg = (deg + kTaskEntries - 1) / kTaskEntries;
-        if (lane == 0) s_nt[wave] = nseg > 1 ? (nseg < kWgWaves ? nseg : kWgWaves) : 0;
-        if (r >= 0 && nseg <= 1) rowlist_dev_finish(r, lane, rowlist_segments(col, val, Xl, beg, deg, 0, nseg, lane, 0.0f), Y, acc_in, acc_out, acc_div);
-        __syncthreads();
-        // ---- part 2: the longer rows, as many at a time as their tasks fit the LDS slots (a row has at most 16: at least 4 rows)
-        for (int j0 = 0; j0 < kWgWaves;) {
-            int total = 0, j1 = j0;
-            while (j1 < kWgWaves && total + s_nt[j1] <= kDevTasks) total += s_nt[j1++];
-            if (total > 0) {
-                for (int t = wave; t < total; t += kWgWaves) {
-                    int j = j0, base = 0;
-                    while (t >= base + s_nt[j]) base += s_nt[j++];
-                    const int rj = list[k0 + j];
-                    const int bj = rowptr[rj], dj = rowptr[rj + 1] - bj;
-                    s_part[t][lane] = rowlist_segments(col, val, Xl, bj, dj, t - base, (dj + kTaskEntries - 1) / kTaskEntries, lane, 0.0f);
-                }
-                __syncthreads();
-                for (int j = j0 + wave; j < j1; j += kWgWaves) {
-                    const int nt = s_nt[j];
-                    if (nt == 0) continue;
-                    int base = 0;
-                    for (int i = j0; i < j; ++i) base += s_nt[i];
-                    float y = s_part[base][lane];
-                    for (int p = 1; p < nt; ++p) y = y + s_part[base + p][lane];       // segment order
-                    rowlist_dev_finish(list[k0 + j], lane, y, Y, acc_in, acc_out, acc_div);
-                }
-                __syncthreads();                    // s_part is rewritten by the next group's tasks (workgroup-uniform: total is)
-            }
-            j0 = j1;
-        }
-        __syncthreads();                            // s_nt and s_part are rewritten by the next pass
-    }
+    rowlist_dev_body<float>(rowptr, col, val, X, list, count, max_count, n_rows, Y, nullptr, acc_in, acc_out, acc_div);
 }
 
 // The row-list kernel at d = 64 V (V = 2, 4): a lane owns V consecutive columns, a segment's gathers are in flight 64 / V at a time

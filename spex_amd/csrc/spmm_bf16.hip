@@ -38,6 +38,16 @@ __global__ __launch_bounds__(kWave *kWgWaves) __attribute__((amdgpu_waves_per_eu
                                                      HubFold{nullptr, nullptr, nullptr, 0u}, SnapArgs{});      // (no fold: no tail either)
 }
 
+// The list-driven row-list SpMM (spmm.hip: spmm_rowlist_dev_kernel) gathering from a bf16 table: the same rowlist_dev_body
+// (spmm_chunk.h), so on Xw = float(X16) the fp32 kernel's bits for EVERY listed row — hubs included: the row's segments are added in
+// the same order — and spmm_chunk_bf16_kernel's for rows of up to 1 024 entries.  Y16 = bf16(the register Y gets).
+__global__ __launch_bounds__(kWave *kWgWaves) void spmm_rowlist_dev_bf16_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+    const uint16_t *__restrict__ X16, const int32_t *__restrict__ list, const int32_t *__restrict__ count, int32_t max_count,
+    int32_t n_rows, float *Y, uint16_t *Y16, const float *acc_in, float *acc_out, float acc_div)   // (acc_out may alias acc_in: unqualified)
+{
+    rowlist_dev_body<uint16_t>(rowptr, col, val, X16, list, count, max_count, n_rows, Y, Y16, acc_in, acc_out, acc_div);
+}
 
 // One wave per hub row (more than 1 024 entries): its segments' partial rows added in segment order, then the launch's epilogue.
 __global__ __launch_bounds__(kWave *kWavesPerBlock) void spmm_hub_fixup_bf16_kernel(
@@ -207,6 +217,32 @@ extern "C" int spex_spmm_bf16_f32(const spex_graph_t *g, const uint16_t *X16, fl
     rc = ensure_partial(const_cast<spex_graph *>(g), 64);      // (the hub segments' partial rows; sized with the handle)
     if (rc) return rc;
     return launch_spmm_bf16(g, X16, Y, Y16, add_in, add_div, acc_in, acc_out, acc_div, (hipStream_t)stream);
+}
+
+// spex_spmm_rowlist_dev_f32 on a bf16 table: rows list[0 .. min(*count, max_count)) from the CSR arrays (no task table needed).
+extern "C" int spex_spmm_rowlist_dev_bf16_f32(const spex_graph_t *g, const uint16_t *X16, const int32_t *list, const int32_t *count,
+                                              int32_t max_count, float *Y, uint16_t *Y16, const float *acc_in, float *acc_out, float acc_div,
+                                              int32_t d, void *stream)
+{
+    const char *who = "spex_spmm_rowlist_dev_bf16_f32";
+    SPEX_CHECK_ARG(g && X16 && list && count && max_count >= 0, "%s: NULL graph, X16, list or count, or max_count < 0", who);
+    SPEX_CHECK_ARG(Y || Y16 || acc_out, "%s: no output requested (Y, Y16 and acc_out are all NULL)", who);
+    SPEX_CHECK_ARG(!acc_out || (acc_in && acc_div != 0.0f), "%s: acc_out needs acc_in and acc_div != 0", who);
+    SPEX_CHECK_ARG(X16 != Y16 && (const void *)X16 != (const void *)Y && (const void *)X16 != (const void *)acc_out &&
+                       (const void *)X16 != (const void *)acc_in, "%s: X16 must not alias an output or acc_in", who);
+    SPEX_CHECK_ARG((!Y16 || ((const void *)Y16 != (const void *)Y && (const void *)Y16 != (const void *)acc_out &&
+                             (const void *)Y16 != (const void *)acc_in)) && (!Y || (Y != acc_out && Y != acc_in)),
+                   "%s: Y and Y16 must not alias each other, acc_in or acc_out (acc_out may be acc_in)", who);
+    if (d != 64 || g->mask_mode != 0) {
+        spex::set_error("%s: d == 64 without edge dropout only (d = %d, mask mode %d)", who, d, g->mask_mode);
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    if (max_count == 0 || g->n_rows == 0) return SPEX_OK;
+    const int64_t wgs = ((int64_t)max_count + kWgWaves - 1) / kWgWaves;
+    hipLaunchKernelGGL(spmm_rowlist_dev_bf16_kernel, dim3((unsigned)(wgs < kDevMaxWgs ? wgs : kDevMaxWgs)), dim3(kWave * kWgWaves), 0,
+                       (hipStream_t)stream, g->rowptr, g->col, g->val, X16, list, count, max_count, g->n_rows, Y, Y16, acc_in, acc_out, acc_div);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
 }
 
 extern "C" int spex_propagate_bf16_f32(const spex_graph_t *g, const float *E0, float *mean_out, uint16_t *ws16, int32_t L, int32_t d,

@@ -8,7 +8,7 @@
 //
 // The BCE and the exact BPR LightGCN steps are ONE schedule, lightgcn_step, built from named pieces: step_check, the optional
 // sparse-Adam clear and frontier lists, step_forward, the kind's batch launch (step_batch), the backward behind it
-// (bf16_backward_push, frontier_backward, step_backward_pulls) and one closing Adam launch.  What the kinds do NOT share, and the
+// (bf16_backward_push, frontier_backward [+ frontier_backward_bf16], step_backward_pulls) and one closing Adam launch.  What the kinds do NOT share, and the
 // schedule keeps: BCE at L == 1 scores through spex_spmm_rowlist_f32 + spex_score_bce_slots_f32 and one pull product, BPR at L == 1
 // runs the push form with the push target as the gradient; the deterministic BCE step reduces its slots in one call, the BPR step in
 // two; only BPR has the dense form (from kBprStepDenseMinTriples* triples, never under SPEX_STEP_FRONTIER) and the L2 count tables;
@@ -91,9 +91,9 @@ static int bf16_backward_push(const spex_lightgcn_step_t *s, size_t sz, const fl
     return spex_spmm_bf16_f32(s->graph_t, src, s->grad_E0, nullptr, nullptr, 1.0f, nullptr, nullptr, 1.0f, 64, stream);
 }
 
-// ---- SPEX_STEP_FRONTIER (d == 64, L >= 2, fp32 tables; include/spex_hip.h): forward layer L - 1 and the backward product behind the
-//      batch kernel's push run over the batch's frontier F1.  Everything a flagged descriptor must satisfy, checked before anything
-//      touches the device.
+// ---- SPEX_STEP_FRONTIER (d == 64, L >= 2; with SPEX_STEP_BF16_GATHER: L = 2 or 3, bf16_step_check's rules on top; include/spex_hip.h):
+//      forward layer L - 1 and the backward product behind the batch kernel's push run over the batch's frontier F1.  Everything a
+//      flagged descriptor must satisfy, checked before anything touches the device.
 static int frontier_step_check(const spex_lightgcn_step_t *s, const char *who)
 {
     if (s->d != 64 || (s->flags & SPEX_STEP_WIDE) != 0) {
@@ -104,7 +104,6 @@ static int frontier_step_check(const spex_lightgcn_step_t *s, const char *who)
     SPEX_CHECK_ARG(s->L >= 2, "%s: SPEX_STEP_FRONTIER needs L >= 2 (got %d): at L = 1 the step has no whole-graph launch to replace", who, s->L);
     SPEX_CHECK_ARG((s->flags & SPEX_STEP_DETERMINISTIC) == 0,
                    "%s: SPEX_STEP_FRONTIER does not combine with SPEX_STEP_DETERMINISTIC (the frontier push uses float atomics)", who);
-    SPEX_CHECK_ARG((s->flags & SPEX_STEP_BF16_GATHER) == 0, "%s: SPEX_STEP_FRONTIER does not combine with SPEX_STEP_BF16_GATHER (fp32 tables only)", who);
     SPEX_CHECK_ARG((s->flags & SPEX_STEP_BPR_DENSE) == 0,
                    "%s: SPEX_STEP_FRONTIER does not combine with SPEX_STEP_BPR_DENSE (a frontier step takes the push form at any T)", who);
     SPEX_CHECK_ARG(s->graph->mask_mode == 0 && s->graph_t->mask_mode == 0, "%s: SPEX_STEP_FRONTIER does not combine with edge dropout", who);
@@ -118,6 +117,8 @@ static int frontier_step_check(const spex_lightgcn_step_t *s, const char *who)
 //      in front of frontier_step_check, like it before anything touches the device.
 static int sparse_adam_check(const spex_lightgcn_step_t *s, const char *who)
 {
+    SPEX_CHECK_ARG((s->flags & SPEX_STEP_BF16_GATHER) == 0,
+                   "%s: SPEX_STEP_SPARSE_ADAM does not combine with SPEX_STEP_BF16_GATHER (the row-sparse Adam pass keeps no bf16 shadow of E0)", who);
     SPEX_CHECK_ARG((s->flags & SPEX_STEP_FRONTIER) != 0, "%s: SPEX_STEP_SPARSE_ADAM needs SPEX_STEP_FRONTIER (the row list is the frontier's)", who);
     SPEX_CHECK_ARG(s->L == 2, "%s: SPEX_STEP_SPARSE_ADAM needs L == 2 (got %d): behind a whole-graph pull the gradient is dense", who, s->L);
     return SPEX_OK;
@@ -167,6 +168,33 @@ static int frontier_lists(spex_lightgcn_step_t *s, const int64_t *a, int32_t n_a
                                     s->frontier_counts + 1, stream));
     if (!two_hop) return SPEX_OK;
     return spex_frontier_rows_i32(g, s->frontier_list, s->frontier_counts + 1, g->n_rows, s->frontier_stamp, epoch, s->frontier_counts + 2, stream);
+}
+
+// SPEX_STEP_FRONTIER | SPEX_STEP_BF16_GATHER (L = 2 or 3): y_(L-1) at the rows of F1 from the bf16 table of the layer
+// before — fp32 into ws_fwd[L - 2], bf16 of the same register into ws16[L - 2], the batch kernel's gather source —, behind y_1 over
+// the whole graph from the shadow at L == 3 (the bf16 step's own first launch).  At L == 2 no whole-graph launch is left.
+static int frontier_forward_bf16(const spex_lightgcn_step_t *s, size_t sz, const uint16_t **last16, void *stream)
+{
+    const uint16_t *cur = s->E0_16;
+    const size_t l = (size_t)(s->L - 2);
+    if (s->L == 3) {
+        SPEX_TRY(spex_spmm_bf16_f32(s->graph, cur, s->ws_fwd, s->ws16, nullptr, 1.0f, nullptr, nullptr, 1.0f, 64, stream));
+        cur = s->ws16;
+    }
+    uint16_t *nxt = s->ws16 + l * sz;
+    SPEX_TRY(spex_spmm_rowlist_dev_bf16_f32(s->graph, cur, s->frontier_list, s->frontier_counts + 1, s->graph->n_rows, s->ws_fwd + l * sz, nxt, nullptr,
+                                            nullptr, 1.0f, 64, stream));
+    *last16 = nxt;
+    return SPEX_OK;
+}
+
+// The frontier step's backward at L == 3 behind W = A^T P (the fp32 frontier push of the fp32 P: exact): one cast makes W a gather
+// source (ws16[0]: the forward's y_1 table is dead), then grad_E0 = A^T bf16(W), plain; the Adam pass adds P.  Straight-through with ONE
+// rounding, of W, where bf16_backward_push has two (of P and of A^T bf16(P)).  At L == 2 the push target is grad_E0 itself: nothing here.
+static int frontier_backward_bf16(const spex_lightgcn_step_t *s, size_t sz, const float *W, void *stream)
+{
+    SPEX_TRY(spex_cast_bf16_f32(W, s->ws16, (int64_t)sz, stream));
+    return spex_spmm_bf16_f32(s->graph_t, s->ws16, s->grad_E0, nullptr, nullptr, 1.0f, nullptr, nullptr, 1.0f, 64, stream);
 }
 
 // Forward layer L - 1 at the rows of F1: the table, and for L >= 4 the running sum, at those rows.
@@ -278,7 +306,8 @@ static int step_forward(const spex_lightgcn_step_t *s, size_t sz, void *stream, 
     const bool plain = L >= 2 && L <= 3, fr = (s->flags & SPEX_STEP_FRONTIER) != 0;
     f->cur = s->E0;
     if ((s->flags & SPEX_STEP_BF16_GATHER) != 0) {
-        SPEX_TRY(bf16_forward(s, sz, &f->cur16, stream));
+        if (fr) SPEX_TRY(frontier_forward_bf16(s, sz, &f->cur16, stream));
+        else SPEX_TRY(bf16_forward(s, sz, &f->cur16, stream));
     } else {
         SPEX_TRY(forward_layers(s->graph, s->E0, s->light_out, s->ws_fwd, L, fr ? L - 2 : L - 1, s->d, stream, &f->cur));
         if (fr) {
@@ -506,10 +535,11 @@ static int lightgcn_step(spex_lightgcn_step_t *s, const StepBatch &k, void *stre
         const bool no_dense = L == 3 || L == 1;
         SPEX_TRY(batch(1.0f / (float)(L + 1), s->grad_slots /* per-sample losses, summed by the Adam pass */, nullptr, no_dense ? nullptr : s->g_out, G));
         const float *src = G;
-        if (bf16) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
+        if (bf16 && !fr) SPEX_TRY(bf16_backward_push(s, sz, G, stream));      // (the same products from bf16 roundings of their sources)
         float *W = nullptr;
-        if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream, sp));     // product l = L - 2 over the frontier
+        if (fr) SPEX_TRY(frontier_backward(s, sz, G, &W, stream, sp));     // product l = L - 2 over the frontier (from the fp32 P on either table type)
         if (fr) src = W;
+        if (fr && bf16 && L == 3) SPEX_TRY(frontier_backward_bf16(s, sz, W, stream));
         // (none under SPEX_STEP_SPARSE_ADAM, L == 2: the frontier push has left the whole product in grad_E0, non-zero in F2 only)
         if (!bf16) SPEX_TRY(step_backward_pulls(gt, src, fr ? L - 3 : L - 2, s->g_out, s->ws_bwd, s->grad_E0, L, d, stream));
         if (L == 1) grad = G;

@@ -350,21 +350,34 @@ class SpexGraph:
         _bump(Y, acc_out)
         return Y if Y is not None else acc_out
 
-    def spmm_rows_dev(self, X, rows, Y=None, acc_in=None, acc_out=None, acc_div=1.0, frontier=True):
+    def spmm_rows_dev(self, X, rows, Y=None, acc_in=None, acc_out=None, acc_div=1.0, frontier=True, X16=None, Y16=None):
         """spmm_rows() driven by a device list (an ops.UniqueRows / ops.FrontierRows; frontier=True: the whole expanded list): the
         listed rows only, other rows of Y / acc_out untouched; entries are distinct, so acc_out may be acc_in.  d == 64, no edge
-        dropout.  See spex_spmm_rowlist_dev_f32."""
-        d = X.shape[1]
+        dropout.  See spex_spmm_rowlist_dev_f32.
+        X16 (with X = None): the same launch gathering from a bf16 table, all arithmetic fp32 — bit-identical to
+        spmm_rows_dev(X16.float(), ...) on every listed row; Y16 (bf16, optional, only with X16) = bf16(the value Y gets), the next
+        layer's gather source at the listed rows.  Y, Y16, acc_out: any subset, at least one.  See spex_spmm_rowlist_dev_bf16_f32."""
+        if (X is None) == (X16 is None):
+            raise ValueError("spmm_rows_dev: give either X (fp32) or X16 (bf16)")
+        if Y16 is not None and X16 is None:
+            raise ValueError("spmm_rows_dev: Y16 comes with X16 only (the fp32 launch has no bf16 output)")
+        d = (X if X16 is None else X16).shape[1]
         self._chk(X, self.n_cols, d, "X")
+        self._chk16(X16, self.n_cols, d, "X16")
         for t, nm in ((Y, "Y"), (acc_in, "acc_in"), (acc_out, "acc_out")):
             self._chk(t, self.n_rows, d, nm)
+        self._chk16(Y16, self.n_rows, d, "Y16")
         if rows.n_rows > self.n_rows:
             raise ValueError("spmm_rows_dev: the row list must index rows of the graph")
         count = rows.count_f if frontier and hasattr(rows, "count_f") else rows.count
-        _launch(self.device, "spex_spmm_rowlist_dev_f32", self._h, _ptr(X), _ptr(rows.list), _ptr(count), rows.capacity, _ptr(Y), _ptr(acc_in),
-                _ptr(acc_out), float(acc_div), d)
-        _bump(Y, acc_out)
-        return Y if Y is not None else acc_out
+        if X16 is not None:
+            _launch(self.device, "spex_spmm_rowlist_dev_bf16_f32", self._h, _ptr(X16), _ptr(rows.list), _ptr(count), rows.capacity, _ptr(Y),
+                    _ptr(Y16), _ptr(acc_in), _ptr(acc_out), float(acc_div), d)
+        else:
+            _launch(self.device, "spex_spmm_rowlist_dev_f32", self._h, _ptr(X), _ptr(rows.list), _ptr(count), rows.capacity, _ptr(Y), _ptr(acc_in),
+                    _ptr(acc_out), float(acc_div), d)
+        _bump(Y, Y16, acc_out)
+        return Y if Y is not None else (acc_out if acc_out is not None else Y16)
 
     def propagate(self, E0, n_layers, mean_out=None, layers_out=None, ws=None, gather_dtype=None):
         """LightGCN.computer() (model.py:66-97) on a whole graph: returns mean(E0..EL).

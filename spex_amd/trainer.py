@@ -69,7 +69,8 @@ class LightGCNStepper:
         semantics, an opt-in like gather_dtype.  The Adam pass, the clears and the loss sum then cost |F2| rows, not N: pays where F2
         is a small share of a graph that streams from HBM, loses on small graphs.  `stepper.sparse_adam` may be switched off and on
         between steps; while `frontier` is switched off it is ignored (the whole-graph steps run dense Adam).
-        frontier=True (width 64, n_layers >= 2, fp32 tables, no edge dropout, not deterministic; ValueError otherwise): step_bce,
+        frontier=True (width 64, n_layers >= 2, no edge dropout, not deterministic, gather_dtype not in the constructor — set
+        `stepper.gather_dtype = torch.bfloat16` afterwards for frontier steps on bf16 tables, n_layers 2 or 3; ValueError otherwise): step_bce,
         step_bpr_exact, the native epochs and the sampled epochs take one more level inward (SPEX_STEP_FRONTIER) —
         forward layer L - 1 only at the batch's frontier F1 (its rows and their stored columns), the backward product behind the
         batch kernel's push as a push over the same list; at n_layers 2 no whole-graph launch is left in the step.  Exact semantics
@@ -82,6 +83,7 @@ class LightGCNStepper:
         DESIGN.md 4.19).  The stepper keeps `E0_16`, a bf16 shadow of E0 that the one-call step's Adam pass writes beside E0; the
         stepper's own other paths re-cast it when needed.  A caller that writes `stepper.E0` itself calls refresh_gather_table()
         before the next step.  Pays on graphs that stream from HBM; slower on cache-resident ones.  step_bpr_sgd stays fp32.
+        `stepper.gather_dtype` may be switched between steps (one set of moments: a precision schedule, or an A/B on one arena).
         weight_decay: the L2 coefficient of step_bpr_exact / epoch_bpr (upstream LightGCN's `decay`: weight_decay / 2 * the squared
         norms of the batch's E0 rows, over T, added to the mean BPR loss); the BCE steps do not read it.
         deterministic (default: SPEX_DETERMINISTIC=1 in the environment): the step takes every sum in a fixed order — no float
@@ -116,18 +118,13 @@ class LightGCNStepper:
         self.grad_slots = None        # per-sample gradient rows (_slots), allocated for the largest batch seen
         self._desc = None             # the one-call step's descriptor (_prepare_desc)
         self._ws0_clean = False       # ws_bwd[0] is all-zero (the one-call step's push target)
-        self.gather_dtype = torch.bfloat16 if _gather_bf16(gather_dtype) else None
-        self.E0_16 = self.ws16 = None
-        if self.gather_dtype is not None:
-            if d != 64 or self.L not in (2, 3):
-                raise ValueError(f"LightGCNStepper(gather_dtype=torch.bfloat16): bf16 gather tables take an embedding width of 64 and "
-                                 f"n_layers 2 or 3 (got width {d}, n_layers {self.L})")
-            self.E0_16 = torch.empty((n, d), dtype=torch.bfloat16, device=dev)       # bf16(E0): see _shadow_current
-            self.ws16 = torch.zeros((2, n, d), dtype=torch.bfloat16, device=dev)     # the later layers' gather tables, then the backward's
+        self._gather_dtype = None     # None or torch.bfloat16: the `gather_dtype` property
+        self.E0_16 = self.ws16 = None # bf16(E0) (see _shadow_current); the later layers' gather tables, then the backward's: on first use
         self._shadow_current = False  # E0_16 == bf16(E0) (kept so by the bf16 one-call step's Adam pass; every other writer of E0 clears it)
         self._frontier = False
         self._front = None            # the batch's frontier list (ops.FrontierRows): list, counts and stamp table of both step forms
         self._sparse_adam = False
+        self.gather_dtype = gather_dtype
         self._grad_listed = False     # grad_E0 is zero outside the frontier list's F2 (SPEX_STEP_GRAD_ROWS_LISTED) ...
         self._grad_ver = self._list_ver = -1      # ... as long as nobody has written grad_E0 or the list since (torch's version counters)
         if sparse_adam and not (frontier and self.L == 2):
@@ -137,7 +134,8 @@ class LightGCNStepper:
             if self.deterministic:
                 raise ValueError("LightGCNStepper(frontier=True): not with deterministic=True — the frontier push adds with float atomics")
             if self.gather_dtype is not None:
-                raise ValueError("LightGCNStepper(frontier=True): not with gather_dtype — the frontier form reads fp32 tables only")
+                raise ValueError("LightGCNStepper(frontier=True): not with gather_dtype in the constructor — build the stepper with "
+                                 "frontier=True and set `stepper.gather_dtype` after construction (the frontier steps then read bf16 tables)")
             if d != 64 or self.L < 2:
                 raise ValueError(f"LightGCNStepper(frontier=True): takes an embedding width of 64 and n_layers >= 2 (got width {d}, "
                                  f"n_layers {self.L})")
@@ -170,7 +168,39 @@ class LightGCNStepper:
     def sparse_adam(self, on):
         if on and (self._front is None or self.L != 2):
             raise ValueError("LightGCNStepper.sparse_adam = True: only on a stepper built with frontier=True and n_layers == 2")
+        if on and self._gather_dtype is not None:
+            raise ValueError("LightGCNStepper.sparse_adam = True: not while gather_dtype is torch.bfloat16 — the row-sparse Adam pass keeps "
+                             "no bf16 shadow of E0 (SPEX_STEP_SPARSE_ADAM does not combine with SPEX_STEP_BF16_GATHER)")
         self._sparse_adam = bool(on)
+
+    @property
+    def gather_dtype(self):
+        """None (fp32 gather tables) or torch.bfloat16 (see __init__).  May be set between steps on any stepper of width 64 and
+        n_layers 2 or 3 — also on one built with frontier=True, whose frontier steps then read bf16 tables (SPEX_STEP_FRONTIER |
+        SPEX_STEP_BF16_GATHER).  E0, m, v and t are shared by both settings.  Switching bf16 on allocates E0_16 and ws16
+        on first use and has the next step re-cast the shadow; switching it off keeps the buffers.  ValueError, nothing changed: another
+        width or depth, or switching bf16 on while `sparse_adam` is on."""
+        return self._gather_dtype
+
+    @gather_dtype.setter
+    def gather_dtype(self, dtype):
+        new = torch.bfloat16 if _gather_bf16(dtype) else None
+        if new == self._gather_dtype:
+            return
+        if new is not None:
+            n, d = self.E0.shape
+            if d != 64 or self.L not in (2, 3):
+                raise ValueError(f"LightGCNStepper(gather_dtype=torch.bfloat16): bf16 gather tables take an embedding width of 64 and "
+                                 f"n_layers 2 or 3 (got width {d}, n_layers {self.L})")
+            if self._sparse_adam:
+                raise ValueError("LightGCNStepper.gather_dtype = torch.bfloat16: not while sparse_adam is on — the row-sparse Adam pass "
+                                 "keeps no bf16 shadow of E0 (SPEX_STEP_SPARSE_ADAM does not combine with SPEX_STEP_BF16_GATHER)")
+            if self.E0_16 is None:
+                self.E0_16 = torch.empty((n, d), dtype=torch.bfloat16, device=self.E0.device)
+                self.ws16 = torch.zeros((2, n, d), dtype=torch.bfloat16, device=self.E0.device)
+            self._shadow_current = False      # (fp32 steps may have moved E0 since the shadow was written: the next step re-casts)
+        self._gather_dtype = new
+        self._desc = None                     # (the descriptor carries E0_16 / ws16)
 
     def _sparse(self):
         return self._sparse_adam and self._frontier
@@ -280,6 +310,21 @@ class LightGCNStepper:
         fr = self._front.update(idx_a, idx_b, 0, self.n_u).expand(g)
         if two_hop:                   # (sparse_adam: F2 behind F1, the rows the Adam pass takes)
             fr.expand2(g)
+        if self.lo_batch is None:
+            self.lo_batch = torch.zeros_like(lo)
+        if self.gather_dtype is not None:
+            # bf16 tables (L = 2 or 3): y_1 over the whole graph from the shadow at L == 3, y_(L-1) at F1 from the bf16 table before it —
+            # fp32 into ws_fwd[L - 2], bf16 of the same value into ws16[L - 2] —, the last layer at the batch's distinct rows (the Bset
+            # part of the list) from ws16[L - 2]; the running sum is fp32 from the fp32 E0
+            if not self._shadow_current:
+                self.refresh_gather_table()
+            cur16, acc_in = self.E0_16, self.E0
+            if L == 3:
+                g.spmm_bf16(cur16, Y=self.ws_fwd[0], Y16=self.ws16[0], acc_in=acc_in, acc_out=lo)
+                cur16, acc_in = self.ws16[0], lo
+            g.spmm_rows_dev(None, fr, X16=cur16, Y=self.ws_fwd[L - 2], Y16=self.ws16[L - 2], acc_in=acc_in, acc_out=lo)
+            g.spmm_rows_dev(None, fr, X16=self.ws16[L - 2], acc_in=lo, acc_out=self.lo_batch, acc_div=float(L + 1), frontier=False)
+            return self.lo_batch
         cur = self.E0
         for l in range(L - 1):
             nxt = self.ws_fwd[l & 1]
@@ -289,8 +334,6 @@ class LightGCNStepper:
             else:
                 g.spmm(cur, Y=nxt, acc_in=acc_in, acc_out=lo)
             cur = nxt
-        if self.lo_batch is None:
-            self.lo_batch = torch.zeros_like(lo)
         g.spmm_rows(cur, idx_a, idx_b, 0, self.n_u, acc_in=lo, acc_out=self.lo_batch, acc_div=float(L + 1))
         return self.lo_batch
 
@@ -304,6 +347,15 @@ class LightGCNStepper:
         if not zeroed:
             self._grad_listed = False
             W.zero_()
+        if self.gather_dtype is not None and L == 3:
+            # bf16 tables: W = A^T P by the same push of the fp32 P (plain: no g_out term), one cast makes W a gather source (ws16[0]:
+            # the forward's y_1 table is dead), grad_E0 = A^T bf16(W) + P — straight-through, one rounding.  (L == 2: the push below
+            # leaves the whole gradient in grad_E0 on either table type.)
+            ops.spmm_push_rows(self.graph, self._front, self.ws_bwd[0], W, True, scale=1.0, add_scale=inv, frontier=True)
+            cast_bf16(W, out=self.ws16[0])
+            gt.spmm_bf16(self.ws16[0], Y=self.grad_E0)
+            self.grad_E0.add_(self.ws_bwd[0])
+            return
         ops.spmm_push_rows(self.graph, self._front, self.ws_bwd[0], W, True, add=self.g_out, add_indexed=True, scale=1.0, add_scale=inv,
                            frontier=True)
         cur = W
@@ -350,6 +402,7 @@ class LightGCNStepper:
             self._sparse_adam_rows()
         else:
             ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps, zero=self.g_out)
+            self._shadow_current = False
         return None if loss_acc is not None else loss_sum / B
 
     def _step_bpr_frontier(self, users, pos, neg, loss_acc):
@@ -377,6 +430,7 @@ class LightGCNStepper:
             self._sparse_adam_rows()
         else:
             ops.adam_step(self.E0, self.grad_E0, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps, zero=self.g_out)
+            self._shadow_current = False
         if loss_acc is not None:
             loss_acc += loss_sum
             return None
