@@ -1,7 +1,8 @@
 """Diffnet++ diffusion layers on the HIP kernels against the fp64 CPU restatement
 (oracle/diffnet_oracle.py; parity unpinned — the TensorFlow reference cannot run in this image): scores, loss and the
 gradient of EVERY parameter (embeddings, per-edge attention parameters through softmax + SpMM + SDDMM, attention
-MLPs), then a few Adam steps."""
+MLPs), then a few Adam steps.  U = 220 here: every launch below its grid cap, every softmax at the 512 tile — the same kernels past
+every cap and tile edge, and one model case at U = 4 200, H = 128: tests/test_gpu_edge_regimes.py."""
 import numpy as np
 import pytest
 import torch
