@@ -416,7 +416,9 @@ int spex_ngcf_layer_bwd_rows_f32(const float *ego, const float *side, const floa
  * i.e. out += scale * (A^T scatter(src) + scatter(add)) for the matrix A held by the handle (scale = 1/(L+1) gives the
  * first step of the layer-mean's backward, G = (g + A^T g)/(L+1), in one launch).  out: [n_cols, d], accumulated with
  * 256-byte float atomics — initialise it first (zero, or the term the product is added to).  max_count bounds the launch
- * (one 16-wave workgroup per list slot).  No edge dropout in this form.
+ * (one 16-wave workgroup per list slot).  A mask on the handle (edge dropout) is applied entry by entry (a kernel of its own): a
+ * kept value is val[e] / keep_prob, a dropped entry issues no atomic — out += scale * (A_m^T scatter(src) + scatter(add)) for the
+ * masked matrix A_m, the forward's mask.
  */
 int spex_unique_rows_i32(const int64_t *idx_a, int32_t n_a, int64_t off_a, const int64_t *idx_b, int32_t n_b, int64_t off_b,
                          int32_t n_rows, int32_t *stamp, int32_t epoch, int32_t *list, int32_t *count, void *stream);
@@ -440,12 +442,22 @@ int spex_spmm_push_rows_scaled_f32(const spex_graph_t *g, const int32_t *list, c
  * must be square (the list indexes rows and columns alike); one wave per input row, one counter bump per wave and 64-entry run. */
 int spex_frontier_rows_i32(const spex_graph_t *g, int32_t *list, const int32_t *count_b, int32_t max_b, int32_t *stamp, int32_t epoch,
                            int32_t *count_f, void *stream);
+/* The frontier of a batch under the handle's edge-dropout mask: spex_frontier_rows_i32 with "stored entry" read as "stored entry
+ * that the mask KEEPS" (spex_graph_set_edge_mask's rule, decided per entry by its edge id: the decision every masked product of the
+ * step makes) — F1 = Bset U { col[e] : e a stored and kept entry of a row in Bset }.  A dropped entry does not stamp its column: a
+ * column reached over a dropped and a kept entry is listed.  On a handle without a mask the call is spex_frontier_rows_i32;
+ * spex_frontier_rows_i32 itself lists every stored column whatever the mask.  Same arguments, same errors. */
+int spex_frontier_rows_masked_i32(const spex_graph_t *g, int32_t *list, const int32_t *count_b, int32_t max_b, int32_t *stamp, int32_t epoch,
+                                  int32_t *count_f, void *stream);
 /* spex_spmm_rowlist_f32 driven by such a device list: rows list[k], k < min(*count, max_count), entries distinct (acc_out may
  * therefore alias acc_in); rows outside the list are not written; list values outside [0, n_rows) are skipped.  The same per-row
  * arithmetic and epilogue (Y = y; acc_out = (acc_in + y) / acc_div): bit-identical to spex_spmm_rowlist_f32, and to spex_spmm_f32
  * on rows of up to 1 024 entries.  The work split is the frontier's: a row of at most 64 entries is one wave's task, longer rows are
  * cut into one-segment wave tasks whose sums meet in LDS in segment order; a fixed grid (<= 1 024 workgroups of 16 list slots per
- * pass) strides over the list, the count is read on the device.  d == 64 without edge dropout only: otherwise SPEX_ERR_UNSUPPORTED. */
+ * pass) strides over the list, the count is read on the device.  d == 64 only: otherwise SPEX_ERR_UNSUPPORTED.  A mask on the handle
+ * (edge dropout) is applied entry by entry by a kernel of its own: per row the masked spex_spmm_f32's fmaf chain — a kept value is
+ * val / keep_prob, a dropped entry stays in its place as fmaf(0, 0, acc), its source row is never multiplied — i.e. the masked
+ * spex_spmm_f32's bits on rows of up to 1 024 stored entries; a listed row whose entries are all dropped is written as 0. */
 int spex_spmm_rowlist_dev_f32(const spex_graph_t *g, const float *X, const int32_t *list, const int32_t *count, int32_t max_count,
                               float *Y, const float *acc_in, float *acc_out, float acc_div, int32_t d, void *stream);
 /* spex_spmm_rowlist_dev_f32 gathering from a bf16 table X16 ([n_cols, 64], rows of 128 bytes; widening is exact): the same kernel body
@@ -1068,7 +1080,8 @@ typedef struct spex_lightgcn_step {
  * weight_decay > 0 too, and every epoch, sampled-epoch and train_*_sampled call over them).  The step computes the forward, the loss
  * and the gradient of the SPEX_STEP_FRONTIER step.  At L == 2 that gradient's support is structural: it lies in
  *   F2 = F1 U { col[e] : e a stored entry of a row in F1 },
- * the rows the frontier push can write (a second spex_frontier_rows_i32 over the same list, stamp table and epoch: frontier_list =
+ * the rows the frontier push can write (a second spex_frontier_rows_masked_i32 over the same list, stamp table and epoch — under edge
+ * dropout "stored" reads "stored and kept by this step's mask" in both sets: frontier_list =
  * [Bset | F1 minus Bset | F2 minus F1], frontier_counts[2] = |F2|).  Then
  *   rows in F2:       p, m, v are updated by the dense pass's own expression (spex_adam_step_f32's, shared code: the same roundings)
  *                     with the global step count t in both bias corrections; the BPR step's L2 term is included.  F2 is the structural
@@ -1098,8 +1111,14 @@ typedef struct spex_lightgcn_step {
  *              plain, the Adam pass adds P; L >= 4: with the g_out / (L + 1) term).  The remaining L - 2 products are whole-graph pulls.
  * L == 2 has no whole-graph launch left.  The exact BPR step takes the push form at any T.  Refused before anything touches the device
  * (t not advanced): d != 64 or SPEX_STEP_WIDE -> SPEX_ERR_UNSUPPORTED; L < 2, SPEX_STEP_DETERMINISTIC (the second push uses float
- * atomics), SPEX_STEP_BPR_DENSE, an edge-dropout mask on a handle (also the epochs' keep_prob < 1), a NULL frontier_* field ->
- * SPEX_ERR_INVALID.
+ * atomics), SPEX_STEP_BPR_DENSE, a NULL frontier_* field -> SPEX_ERR_INVALID.
+ * Under edge dropout (a mask on both handles, also the epochs' keep_prob < 1; fp32 tables) the step is the whole-graph
+ * masked step on the masked adjacency A_m: the lists are built behind the step's mask by spex_frontier_rows_masked_i32 — F1 = Bset U
+ * the columns of KEPT entries of Bset's rows, which holds everything the masked batch kernel reads and pushes into —, layer L - 1 and
+ * the push over F1 follow the handle's mask (spex_spmm_rowlist_dev_f32, spex_spmm_push_rows_scaled_f32), and SPEX_STEP_SPARSE_ADAM's F2
+ * is the masked two-hop set: the rows that can receive a gradient under this step's mask.  The rule of every masked step holds:
+ * graph_t is the transposed handle with its edge-id permutation and the same mask, else SPEX_ERR_INVALID.  Together with
+ * SPEX_STEP_BF16_GATHER a mask is refused ("does not combine with edge dropout", SPEX_ERR_INVALID): the bf16 list SpMM has no masked form.
  * With SPEX_STEP_BF16_GATHER (L = 2 or 3; that flag's own rules hold on top) the frontier launches read bf16 tables:
  *   forward:   L == 3: y_1 = A E0_16 over the whole graph (spex_spmm_bf16_f32 into ws_fwd[0] and ws16[0], the bf16 step's own launch),
  *              then y_2 at the rows of F1 from ws16[0] into ws_fwd[1] and ws16[1] (spex_spmm_rowlist_dev_bf16_f32).  L == 2: y_1 at F1

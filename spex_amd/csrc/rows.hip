@@ -12,6 +12,9 @@
 //                             listed row r: src_k = src[r] or src[k]), optionally out[r, :] += scale * add_k — 256-byte float atomics
 //                             (spex_spmm_push_rows_scaled_f32: a factor of its own for the add term)
 //   spex_frontier_rows_i32    behind such a list, the stored columns of its rows not yet stamped this epoch: the batch's frontier
+//                             (spex_frontier_rows_masked_i32: the columns reached over entries the handle's edge dropout keeps)
+// spex_spmm_push_rows_f32 and _scaled_f32 follow the handle's edge-dropout rule (a kept value is val / keep_prob, a dropped entry
+// issues no atomic); spex_spmm_push_batch_f32 takes unmasked handles only.
 // Sums arrive in arbitrary order (atomics): results agree with the pull form to fp32 re-association.
 #include "spex_common.h"
 
@@ -42,9 +45,13 @@ constexpr int kFrontierMaxWgs = 1 << 14;
 
 __global__ void frontier_init_kernel(const int32_t *__restrict__ count_b, int32_t *count_f) { *count_f = *count_b; }
 
-__global__ __launch_bounds__(kWave *kFrontierWaves) void frontier_rows_kernel(
+// MASKED (frontier_rows_masked_kernel): only columns reached over a KEPT edge (the handle's edge-dropout rule, edge_kept) are listed.
+// The keep test comes BEFORE the exchange on the stamp: a dropped edge that stamped its column would hide it from a later kept edge to
+// the same column, which would find it stamped and never list it.
+template <bool MASKED>
+__device__ __forceinline__ void frontier_rows_body(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, int32_t n_rows, const int32_t *__restrict__ count_b,
-    int32_t max_b, int32_t *stamp, int32_t epoch, int32_t *list, int32_t *count_f)
+    int32_t max_b, int32_t *stamp, int32_t epoch, int32_t *list, int32_t *count_f, const EdgeDrop &dr)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int n_in = *count_b < max_b ? *count_b : max_b;
@@ -57,7 +64,7 @@ __global__ __launch_bounds__(kWave *kFrontierWaves) void frontier_rows_kernel(
             const int e = base + lane;
             int c = -1;
             if (e < end) c = col[e];
-            const bool fresh = c >= 0 && c < n_rows && atomicExch(stamp + c, epoch) != epoch;    // first visitor of the row this epoch
+            const bool fresh = c >= 0 && c < n_rows && (!MASKED || edge_kept(dr, e)) && atomicExch(stamp + c, epoch) != epoch;    // first visitor of the row this epoch
             const unsigned long long m = __ballot(fresh);
             if (m == 0) continue;
             const int leader = (int)__builtin_ctzll(m);
@@ -69,14 +76,32 @@ __global__ __launch_bounds__(kWave *kFrontierWaves) void frontier_rows_kernel(
     }
 }
 
+__global__ __launch_bounds__(kWave *kFrontierWaves) void frontier_rows_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, int32_t n_rows, const int32_t *__restrict__ count_b,
+    int32_t max_b, int32_t *stamp, int32_t epoch, int32_t *list, int32_t *count_f)
+{
+    frontier_rows_body<false>(rowptr, col, n_rows, count_b, max_b, stamp, epoch, list, count_f, EdgeDrop{nullptr, nullptr, 0, 1.0f, 0u, 0u});
+}
+
+__global__ __launch_bounds__(kWave *kFrontierWaves) void frontier_rows_masked_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, int32_t n_rows, const int32_t *__restrict__ count_b,
+    int32_t max_b, int32_t *stamp, int32_t epoch, int32_t *list, int32_t *count_f, const EdgeDrop dr)
+{
+    frontier_rows_body<true>(rowptr, col, n_rows, count_b, max_b, stamp, epoch, list, count_f, dr);
+}
+
 // One 16-wave workgroup per listed row: wave w takes the row's entries w, w + 16, ... (a hub row of 1 000 entries is 64
 // atomics per wave, not 1 000 in one).
 constexpr int kPushRowsMaxWgs = 1 << 16;
 
-__global__ __launch_bounds__(kWave *kWgWaves) void spmm_push_rows_kernel(
+// MASKED (spmm_push_rows_masked_kernel): the lanes that hold a run's (col, val) also decide `kept` (edge_kept: the handle's
+// edge-dropout rule, the forward's), a kept value is val / keep_prob, and the entry loop skips a dropped entry on the wave-uniform
+// ballot of the kept lanes: a dropped entry issues no atomic at all.
+template <bool MASKED>
+__device__ __forceinline__ void spmm_push_rows_body(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
     const int32_t *__restrict__ list, const int32_t *__restrict__ count, int n_rows, const float *__restrict__ src,
-    int src_indexed, const float *__restrict__ add, int add_indexed, float scale, float add_scale, float *out, int d)
+    int src_indexed, const float *__restrict__ add, int add_indexed, float scale, float add_scale, float *out, int d, const EdgeDrop &dr)
 {
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int n = *count;
@@ -93,16 +118,23 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_push_rows_kernel(
                 const int cnt = end - base < 16 ? end - base : 16;
                 int my_col = 0;
                 float my_val = 0.0f;
+                bool kept = false;
                 if (lane < cnt) {
                     my_col = col[base + lane];
                     my_val = val[base + lane];
+                    if (MASKED) {
+                        kept = edge_kept(dr, base + lane);
+                        my_val = kept ? my_val / dr.keep_prob : 0.0f;
+                    }
                 }
+                const unsigned long long kbits = MASKED ? __ballot(kept) : ~0ull;      // (wave-uniform)
                 // lane 0 is read before the first atomic and the entry loop is a real loop: see spmm_push_batch_kernel
                 const int cc0 = __builtin_amdgcn_readlane(my_col, 0);
                 const float v0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val), 0));
-                if (col_ok) atomicAdd(out + (size_t)cc0 * d + c, v0 * g);
+                if (col_ok && (!MASKED || (kbits & 1ull))) atomicAdd(out + (size_t)cc0 * d + c, v0 * g);
 #pragma unroll 1
                 for (int j = 1; j < cnt; ++j) {
+                    if (MASKED && !((kbits >> j) & 1ull)) continue;
                     const int cc = __builtin_amdgcn_readlane(my_col, j);
                     const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val), j));
                     if (col_ok) atomicAdd(out + (size_t)cc * d + c, v * g);
@@ -111,6 +143,23 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_push_rows_kernel(
             if (add && wave == 0 && col_ok) atomicAdd(out + (size_t)r * d + c, add_scale * add[(size_t)(add_indexed ? r : k) * d + c]);
         }
     }
+}
+
+__global__ __launch_bounds__(kWave *kWgWaves) void spmm_push_rows_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+    const int32_t *__restrict__ list, const int32_t *__restrict__ count, int n_rows, const float *__restrict__ src,
+    int src_indexed, const float *__restrict__ add, int add_indexed, float scale, float add_scale, float *out, int d)
+{
+    spmm_push_rows_body<false>(rowptr, col, val, list, count, n_rows, src, src_indexed, add, add_indexed, scale, add_scale, out, d,
+                               EdgeDrop{nullptr, nullptr, 0, 1.0f, 0u, 0u});
+}
+
+__global__ __launch_bounds__(kWave *kWgWaves) void spmm_push_rows_masked_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+    const int32_t *__restrict__ list, const int32_t *__restrict__ count, int n_rows, const float *__restrict__ src,
+    int src_indexed, const float *__restrict__ add, int add_indexed, float scale, float add_scale, float *out, int d, const EdgeDrop dr)
+{
+    spmm_push_rows_body<true>(rowptr, col, val, list, count, n_rows, src, src_indexed, add, add_indexed, scale, add_scale, out, d, dr);
 }
 
 // The same product driven by the batch itself, EVERY slot contributing: slot k (row idx_a[k] + off_a, then idx_b[k] + off_b)
@@ -417,10 +466,14 @@ static int push_rows(const char *who, const spex_graph_t *g, const int32_t *list
 {
     SPEX_CHECK_ARG(g && list && count && src && out, "%s: NULL argument", who);
     SPEX_CHECK_ARG(max_count >= 0 && d >= 1, "%s: max_count=%d d=%d", who, max_count, d);
-    SPEX_CHECK_ARG(g->mask_mode == 0, "%s: edge dropout is not supported in push form", who);
     if (max_count == 0 || g->n_rows == 0) return SPEX_OK;
-    hipLaunchKernelGGL(spmm_push_rows_kernel, dim3((unsigned)(max_count < kPushRowsMaxWgs ? max_count : kPushRowsMaxWgs)), dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr,
-                       g->col, g->val, list, count, g->n_rows, src, src_indexed, add, add_indexed, scale, add_scale, out, d);
+    const dim3 grid((unsigned)(max_count < kPushRowsMaxWgs ? max_count : kPushRowsMaxWgs));
+    if (g->mask_mode != 0)      // the handle's edge-dropout rule per entry: a kernel of its own
+        hipLaunchKernelGGL(spmm_push_rows_masked_kernel, grid, dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val, list, count,
+                           g->n_rows, src, src_indexed, add, add_indexed, scale, add_scale, out, d, edge_drop_of(g));
+    else
+        hipLaunchKernelGGL(spmm_push_rows_kernel, grid, dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val, list, count,
+                           g->n_rows, src, src_indexed, add, add_indexed, scale, add_scale, out, d);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }
@@ -453,21 +506,39 @@ extern "C" int spex_spmm_push_rows_scaled_f32(const spex_graph_t *g, const int32
                      stream);
 }
 
-extern "C" int spex_frontier_rows_i32(const spex_graph_t *g, int32_t *list, const int32_t *count_b, int32_t max_b, int32_t *stamp,
-                                      int32_t epoch, int32_t *count_f, void *stream)
+static int frontier_rows(const char *who, bool masked, const spex_graph_t *g, int32_t *list, const int32_t *count_b, int32_t max_b, int32_t *stamp,
+                         int32_t epoch, int32_t *count_f, void *stream)
 {
-    SPEX_CHECK_ARG(g && list && count_b && stamp && count_f && count_f != count_b, "spex_frontier_rows_i32: NULL buffer, or count_f == count_b");
-    SPEX_CHECK_ARG(max_b >= 0 && epoch != 0, "spex_frontier_rows_i32: max_b=%d epoch=%d", max_b, epoch);
-    SPEX_CHECK_ARG(g->n_rows == g->n_cols, "spex_frontier_rows_i32: the list indexes rows and columns alike: a square graph (%d x %d)", g->n_rows,
-                   g->n_cols);
+    SPEX_CHECK_ARG(g && list && count_b && stamp && count_f && count_f != count_b, "%s: NULL buffer, or count_f == count_b", who);
+    SPEX_CHECK_ARG(max_b >= 0 && epoch != 0, "%s: max_b=%d epoch=%d", who, max_b, epoch);
+    SPEX_CHECK_ARG(g->n_rows == g->n_cols, "%s: the list indexes rows and columns alike: a square graph (%d x %d)", who, g->n_rows, g->n_cols);
     hipLaunchKernelGGL(frontier_init_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, count_b, count_f);
     SPEX_HIP(hipGetLastError());
     if (max_b == 0 || g->n_rows == 0) return SPEX_OK;
     const int64_t wgs = ((int64_t)max_b + kFrontierWaves - 1) / kFrontierWaves;
-    hipLaunchKernelGGL(frontier_rows_kernel, dim3((unsigned)(wgs < kFrontierMaxWgs ? wgs : kFrontierMaxWgs)), dim3(kWave * kFrontierWaves), 0,
-                       (hipStream_t)stream, g->rowptr, g->col, g->n_rows, count_b, max_b, stamp, epoch, list, count_f);
+    const dim3 grid((unsigned)(wgs < kFrontierMaxWgs ? wgs : kFrontierMaxWgs));
+    if (masked && g->mask_mode != 0)
+        hipLaunchKernelGGL(frontier_rows_masked_kernel, grid, dim3(kWave * kFrontierWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->n_rows, count_b,
+                           max_b, stamp, epoch, list, count_f, edge_drop_of(g));
+    else
+        hipLaunchKernelGGL(frontier_rows_kernel, grid, dim3(kWave * kFrontierWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->n_rows, count_b, max_b,
+                           stamp, epoch, list, count_f);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
+}
+
+extern "C" int spex_frontier_rows_i32(const spex_graph_t *g, int32_t *list, const int32_t *count_b, int32_t max_b, int32_t *stamp,
+                                      int32_t epoch, int32_t *count_f, void *stream)
+{
+    return frontier_rows("spex_frontier_rows_i32", false, g, list, count_b, max_b, stamp, epoch, count_f, stream);
+}
+
+// spex_frontier_rows_i32 under the handle's edge-dropout rule: only columns reached over a kept entry are listed (mask mode 0: the
+// same list).  The frontier of a masked step.
+extern "C" int spex_frontier_rows_masked_i32(const spex_graph_t *g, int32_t *list, const int32_t *count_b, int32_t max_b, int32_t *stamp,
+                                             int32_t epoch, int32_t *count_f, void *stream)
+{
+    return frontier_rows("spex_frontier_rows_masked_i32", true, g, list, count_b, max_b, stamp, epoch, count_f, stream);
 }
 
 extern "C" int spex_spmm_push_batch_f32(const spex_graph_t *g, const int64_t *idx_a, int32_t n_a, int64_t off_a, const int64_t *idx_b,

@@ -449,6 +449,17 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_rowlist_dev_kernel(
     rowlist_dev_body<float>(rowptr, col, val, X, list, count, max_count, n_rows, Y, nullptr, acc_in, acc_out, acc_div);
 }
 
+// The same body under the handle's edge-dropout rule: per row the masked spex_spmm_f32's fmaf chain, a dropped entry in
+// its place as fmaf(0, 0, acc) — the masked frontier step's forward layer L - 1 at the rows of the masked F1.  A kernel of its own name:
+// spmm_rowlist_dev_kernel keeps its registers.
+__global__ __launch_bounds__(kWave *kWgWaves) void spmm_rowlist_dev_masked_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
+    const float *__restrict__ X, const int32_t *__restrict__ list, const int32_t *__restrict__ count, int32_t max_count,
+    int32_t n_rows, float *Y, const float *acc_in, float *acc_out, float acc_div, const spex::EdgeDrop dr)
+{
+    rowlist_dev_body<float, true>(rowptr, col, val, X, list, count, max_count, n_rows, Y, nullptr, acc_in, acc_out, acc_div, dr);
+}
+
 // The row-list kernel at d = 64 V (V = 2, 4): a lane owns V consecutive columns, a segment's gathers are in flight 64 / V at a time
 // (segment_sum_wide, spex_common.h), the segment sums are added in segment order — for rows of up to 1 024 entries the row
 // spmm_chunk_wide_kernel produces, bit for bit.
@@ -771,14 +782,19 @@ extern "C" int spex_spmm_rowlist_dev_f32(const spex_graph_t *g, const float *X, 
     SPEX_CHECK_ARG(Y || acc_out, "spex_spmm_rowlist_dev_f32: neither Y nor acc_out given");
     SPEX_CHECK_ARG(!acc_out || (acc_in && acc_div != 0.0f), "spex_spmm_rowlist_dev_f32: acc_out needs acc_in and acc_div != 0");
     SPEX_CHECK_ARG(X != Y && X != acc_out, "spex_spmm_rowlist_dev_f32: X must not alias an output");
-    if (d != 64 || g->mask_mode != 0) {
-        spex::set_error("spex_spmm_rowlist_dev_f32: d == 64 without edge dropout only (d = %d, mask mode %d)", d, g->mask_mode);
+    if (d != 64) {
+        spex::set_error("spex_spmm_rowlist_dev_f32: d == 64 only (got %d)", d);
         return SPEX_ERR_UNSUPPORTED;
     }
     if (max_count == 0 || g->n_rows == 0) return SPEX_OK;
     const int64_t wgs = ((int64_t)max_count + kWgWaves - 1) / kWgWaves;
-    hipLaunchKernelGGL(spmm_rowlist_dev_kernel, dim3((unsigned)(wgs < kDevMaxWgs ? wgs : kDevMaxWgs)), dim3(kWave * kWgWaves), 0,
-                       (hipStream_t)stream, g->rowptr, g->col, g->val, X, list, count, max_count, g->n_rows, Y, acc_in, acc_out, acc_div);
+    if (g->mask_mode != 0)      // the handle's edge-dropout rule per entry: a kernel of its own (spmm_rowlist_dev_masked_kernel)
+        hipLaunchKernelGGL(spmm_rowlist_dev_masked_kernel, dim3((unsigned)(wgs < kDevMaxWgs ? wgs : kDevMaxWgs)), dim3(kWave * kWgWaves), 0,
+                           (hipStream_t)stream, g->rowptr, g->col, g->val, X, list, count, max_count, g->n_rows, Y, acc_in, acc_out, acc_div,
+                           spex::edge_drop_of(g));
+    else
+        hipLaunchKernelGGL(spmm_rowlist_dev_kernel, dim3((unsigned)(wgs < kDevMaxWgs ? wgs : kDevMaxWgs)), dim3(kWave * kWgWaves), 0,
+                           (hipStream_t)stream, g->rowptr, g->col, g->val, X, list, count, max_count, g->n_rows, Y, acc_in, acc_out, acc_div);
     SPEX_HIP(hipGetLastError());
     return SPEX_OK;
 }

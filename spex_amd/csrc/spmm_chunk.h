@@ -596,9 +596,13 @@ __device__ __forceinline__ void chunk_body(
 constexpr int kDevTasks = 64;
 constexpr int kDevMaxWgs = 1024;
 
-template <typename XT>
+// MASKED: the handle's edge-dropout rule per lane entry, as segment_sum<MASKED> of batch_kernels.h applies it — a kept value is
+// val / keep_prob, a dropped entry keeps its place in the chain as fmaf(0, 0, acc): its gathered value is REPLACED by 0 (a ballot of
+// the dropped lanes, a wave-uniform select per entry), so a source row it alone names may hold Inf.  The padding lanes count as
+// dropped too: they gather the segment's last real source row, which under a mask may be such a row.
+template <typename XT, bool MASKED>
 __device__ __forceinline__ float rowlist_segments(const int32_t *__restrict__ col, const float *__restrict__ val, const XT *__restrict__ Xl,
-                                                  int beg, int deg, int first, int nseg, int lane, float acc)
+                                                  int beg, int deg, int first, int nseg, int lane, float acc, const EdgeDrop &dr)
 {
     typedef Gather16<XT> G;
     for (int sgi = first; sgi < nseg; sgi += kWgWaves) {
@@ -606,20 +610,31 @@ __device__ __forceinline__ float rowlist_segments(const int32_t *__restrict__ co
         const int cnt = (deg - sgi * kTaskEntries < kTaskEntries) ? deg - sgi * kTaskEntries : kTaskEntries;
         int my_col = 0;
         float my_val = 0.0f;
+        bool dropped = MASKED;                                  // (MASKED: a lane past the segment's end counts as dropped)
         if (lane < cnt) {
             my_col = col[e0 + lane];
             my_val = val[e0 + lane];
+            if (MASKED) {
+                const bool kept = edge_kept(dr, e0 + lane);
+                my_val = kept ? my_val / dr.keep_prob : 0.0f;
+                dropped = !kept;
+            }
         }
+        const unsigned long long dbits = MASKED ? __ballot(dropped) : 0ull;
         // entries past the segment's end: value 0 on the segment's last real source row (a line already being fetched)
         const int last_col = __builtin_amdgcn_readlane(my_col, (cnt - 1) & 63);
         if (lane >= cnt) my_col = last_col;
         for (int c = 0; c * kChunk < cnt; ++c) {
+            const uint32_t db = MASKED ? (uint32_t)(dbits >> (c * kChunk)) & 0xFFFFu : 0u;
             typename G::R x[kChunk / G::kPer];
 #pragma unroll
             for (int u = 0; u < kChunk; ++u)
                 x[u >> G::kShift] = reg_with(x[u >> G::kShift], u & (G::kPer - 1), Xl[(size_t)(uint32_t)__builtin_amdgcn_readlane(my_col, c * kChunk + u) * 64]);
 #pragma unroll
-            for (int u = 0; u < kChunk; ++u) acc = fmaf(lane_bcast(my_val, c * kChunk + u), reg_value(x[u >> G::kShift], u & (G::kPer - 1)), acc);
+            for (int u = 0; u < kChunk; ++u) {
+                const float xv = (MASKED && (db & (1u << u))) ? 0.0f : reg_value(x[u >> G::kShift], u & (G::kPer - 1));
+                acc = fmaf(lane_bcast(my_val, c * kChunk + u), xv, acc);
+            }
         }
     }
     return acc;
@@ -637,11 +652,12 @@ __device__ __forceinline__ void rowlist_dev_finish(int r, int lane, float y, flo
     }
 }
 
-template <typename XT>
+template <typename XT, bool MASKED = false>
 __device__ __forceinline__ void rowlist_dev_body(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
     const XT *__restrict__ X, const int32_t *__restrict__ list, const int32_t *__restrict__ count, int32_t max_count,
-    int32_t n_rows, float *Y, uint16_t *Y16, const float *acc_in, float *acc_out, float acc_div)      // (acc_out may alias acc_in: unqualified)
+    int32_t n_rows, float *Y, uint16_t *Y16, const float *acc_in, float *acc_out, float acc_div,      // (acc_out may alias acc_in: unqualified)
+    const EdgeDrop &dr = EdgeDrop{nullptr, nullptr, 0, 1.0f, 0u, 0u})
 {
     __shared__ float s_part[kDevTasks][kWave];
     __shared__ int s_nt[kWgWaves];                 // tasks of each of the pass's 16 slots (0: no row, or a row of one segment)
@@ -663,7 +679,7 @@ __device__ __forceinline__ void rowlist_dev_body(
         const int nseg = (deg + kTaskEntries - 1) / kTaskEntries;
         if (lane == 0) s_nt[wave] = nseg > 1 ? (nseg < kWgWaves ? nseg : kWgWaves) : 0;
         if (r >= 0 && nseg <= 1)
-            rowlist_dev_finish(r, lane, rowlist_segments<XT>(col, val, Xl, beg, deg, 0, nseg, lane, 0.0f), Y, Y16, acc_in, acc_out, acc_div);
+            rowlist_dev_finish(r, lane, rowlist_segments<XT, MASKED>(col, val, Xl, beg, deg, 0, nseg, lane, 0.0f, dr), Y, Y16, acc_in, acc_out, acc_div);
         __syncthreads();
         // ---- part 2: the longer rows, as many at a time as their tasks fit the LDS slots (a row has at most 16: at least 4 rows)
         for (int j0 = 0; j0 < kWgWaves;) {
@@ -675,7 +691,7 @@ __device__ __forceinline__ void rowlist_dev_body(
                     while (t >= base + s_nt[j]) base += s_nt[j++];
                     const int rj = list[k0 + j];
                     const int bj = rowptr[rj], dj = rowptr[rj + 1] - bj;
-                    s_part[t][lane] = rowlist_segments<XT>(col, val, Xl, bj, dj, t - base, (dj + kTaskEntries - 1) / kTaskEntries, lane, 0.0f);
+                    s_part[t][lane] = rowlist_segments<XT, MASKED>(col, val, Xl, bj, dj, t - base, (dj + kTaskEntries - 1) / kTaskEntries, lane, 0.0f, dr);
                 }
                 __syncthreads();
                 for (int j = j0 + wave; j < j1; j += kWgWaves) {

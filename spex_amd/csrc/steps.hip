@@ -106,7 +106,10 @@ static int frontier_step_check(const spex_lightgcn_step_t *s, const char *who)
                    "%s: SPEX_STEP_FRONTIER does not combine with SPEX_STEP_DETERMINISTIC (the frontier push uses float atomics)", who);
     SPEX_CHECK_ARG((s->flags & SPEX_STEP_BPR_DENSE) == 0,
                    "%s: SPEX_STEP_FRONTIER does not combine with SPEX_STEP_BPR_DENSE (a frontier step takes the push form at any T)", who);
-    SPEX_CHECK_ARG(s->graph->mask_mode == 0 && s->graph_t->mask_mode == 0, "%s: SPEX_STEP_FRONTIER does not combine with edge dropout", who);
+    // (edge dropout, fp32 tables: the lists hold the columns reached over kept entries and the three list-driven launches follow the
+    //  handle's mask — DESIGN.md 4.27; step_check's rule asks for the transposed handle.  The bf16 list SpMM has no masked form.)
+    SPEX_CHECK_ARG((s->flags & SPEX_STEP_BF16_GATHER) == 0 || (s->graph->mask_mode == 0 && s->graph_t->mask_mode == 0),
+                   "%s: SPEX_STEP_FRONTIER | SPEX_STEP_BF16_GATHER does not combine with edge dropout", who);
     SPEX_CHECK_ARG(s->frontier_list && s->frontier_stamp && s->frontier_counts,
                    "%s: SPEX_STEP_FRONTIER needs frontier_list ([N] int32), frontier_stamp ([N] int32, zeroed once) and frontier_counts ([2] int32)", who);
     return SPEX_OK;
@@ -153,7 +156,9 @@ static int sparse_adam_pass(spex_lightgcn_step_t *s, int32_t t_next, int32_t n_l
 }
 
 // Bset, then F1 behind it, of a batch of up to three index lists into frontier_list; frontier_counts = { |Bset|, |F1| }.  two_hop
-// (SPEX_STEP_SPARSE_ADAM): F2 behind F1 by a second pass of the same kernel over [0, |F1|); frontier_counts[2] = |F2|.
+// (SPEX_STEP_SPARSE_ADAM): F2 behind F1 by a second pass of the same kernel over [0, |F1|); frontier_counts[2] = |F2|.  Under edge
+// dropout both hops list the columns reached over KEPT entries only (the handle's mask of this step, set before the call): the masked
+// F1 holds every row the batch kernel reads or pushes into, the masked F2 every row the frontier push can write.
 static int frontier_lists(spex_lightgcn_step_t *s, const int64_t *a, int32_t n_a, const int64_t *b, int32_t n_b, const int64_t *c, int32_t n_c,
                           void *stream, bool two_hop = false)
 {
@@ -164,10 +169,10 @@ static int frontier_lists(spex_lightgcn_step_t *s, const int64_t *a, int32_t n_a
     if (c) SPEX_TRY(spex::unique_rows_more(c, n_c, n_u, nullptr, 0, 0, g->n_rows, s->frontier_stamp, epoch, s->frontier_list, s->frontier_counts, stream));
     s->frontier_epoch = epoch;      // (the stamps are on the device from here on, whatever becomes of the step)
     const int64_t slots = (int64_t)n_a + n_b + (c ? n_c : 0);
-    SPEX_TRY(spex_frontier_rows_i32(g, s->frontier_list, s->frontier_counts, (int32_t)(slots < g->n_rows ? slots : g->n_rows), s->frontier_stamp, epoch,
-                                    s->frontier_counts + 1, stream));
+    SPEX_TRY(spex_frontier_rows_masked_i32(g, s->frontier_list, s->frontier_counts, (int32_t)(slots < g->n_rows ? slots : g->n_rows), s->frontier_stamp,
+                                           epoch, s->frontier_counts + 1, stream));
     if (!two_hop) return SPEX_OK;
-    return spex_frontier_rows_i32(g, s->frontier_list, s->frontier_counts + 1, g->n_rows, s->frontier_stamp, epoch, s->frontier_counts + 2, stream);
+    return spex_frontier_rows_masked_i32(g, s->frontier_list, s->frontier_counts + 1, g->n_rows, s->frontier_stamp, epoch, s->frontier_counts + 2, stream);
 }
 
 // SPEX_STEP_FRONTIER | SPEX_STEP_BF16_GATHER (L = 2 or 3): y_(L-1) at the rows of F1 from the bf16 table of the layer

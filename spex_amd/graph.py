@@ -352,8 +352,9 @@ class SpexGraph:
 
     def spmm_rows_dev(self, X, rows, Y=None, acc_in=None, acc_out=None, acc_div=1.0, frontier=True, X16=None, Y16=None):
         """spmm_rows() driven by a device list (an ops.UniqueRows / ops.FrontierRows; frontier=True: the whole expanded list): the
-        listed rows only, other rows of Y / acc_out untouched; entries are distinct, so acc_out may be acc_in.  d == 64, no edge
-        dropout.  See spex_spmm_rowlist_dev_f32.
+        listed rows only, other rows of Y / acc_out untouched; entries are distinct, so acc_out may be acc_in.  d == 64.  An
+        edge-dropout mask on the handle is applied entry by entry, as spmm() applies it (fp32 tables only).  See
+        spex_spmm_rowlist_dev_f32.
         X16 (with X = None): the same launch gathering from a bf16 table, all arithmetic fp32 — bit-identical to
         spmm_rows_dev(X16.float(), ...) on every listed row; Y16 (bf16, optional, only with X16) = bf16(the value Y gets), the next
         layer's gather source at the listed rows.  Y, Y16, acc_out: any subset, at least one.  See spex_spmm_rowlist_dev_bf16_f32."""

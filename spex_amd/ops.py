@@ -380,7 +380,8 @@ class FrontierRows(UniqueRows):
     """A batch's distinct rows Bset and, behind them in the same list, the rest of its frontier F1 = Bset U the stored columns of
     Bset's rows (spex_unique_rows_i32 + spex_frontier_rows_i32): update(...) then expand(graph).  `list` int32[n_rows] (always
     enough: a row enters at most once per epoch), `count` = |Bset| and `count_f` = |F1|, int32[1] device cells; one stamp table,
-    never cleared.  A FrontierRows passes for a UniqueRows (its Bset part); frontier=True selects the whole list in
+    never cleared.  On a graph with an edge-dropout mask "stored" reads "stored and kept" in both hops: the masked step's frontier
+    (DESIGN.md 4.27).  A FrontierRows passes for a UniqueRows (its Bset part); frontier=True selects the whole list in
     spmm_push_rows / SpexGraph.spmm_rows_dev."""
 
     def __init__(self, n_rows, device):
@@ -394,11 +395,17 @@ class FrontierRows(UniqueRows):
         self.max_b = min(self.n_rows, idx_a.numel() + (0 if idx_b is None else idx_b.numel()))
         return self
 
+    @staticmethod
+    def _entry(graph):
+        # a graph that carries an edge-dropout mask: only columns reached over kept entries belong to the frontier
+        return "spex_frontier_rows_masked_i32" if graph.mask_mode else "spex_frontier_rows_i32"
+
     def expand(self, graph):
-        """Append the columns of the listed rows (call once after update)."""
+        """Append the columns of the listed rows (call once after update).  Under an edge-dropout mask on `graph`: the columns of
+        the entries the mask keeps (spex_frontier_rows_masked_i32) — set the step's mask before the call."""
         if graph.n_rows != self.n_rows or graph.n_cols != self.n_rows:
             raise ValueError(f"FrontierRows.expand: needs a square graph of {self.n_rows} rows (got {graph.n_rows} x {graph.n_cols})")
-        _launch(self.list.device, "spex_frontier_rows_i32", graph._h, _ptr(self.list), _ptr(self.count), self.max_b, _ptr(self.stamp),
+        _launch(self.list.device, self._entry(graph), graph._h, _ptr(self.list), _ptr(self.count), self.max_b, _ptr(self.stamp),
                 self.epoch, _ptr(self.count_f))
         return self
 
@@ -408,7 +415,7 @@ class FrontierRows(UniqueRows):
         layers the rows a frontier step's gradient can touch (SPEX_STEP_SPARSE_ADAM)."""
         if graph.n_rows != self.n_rows or graph.n_cols != self.n_rows:
             raise ValueError(f"FrontierRows.expand2: needs a square graph of {self.n_rows} rows (got {graph.n_rows} x {graph.n_cols})")
-        _launch(self.list.device, "spex_frontier_rows_i32", graph._h, _ptr(self.list), _ptr(self.count_f), self.n_rows, _ptr(self.stamp),
+        _launch(self.list.device, self._entry(graph), graph._h, _ptr(self.list), _ptr(self.count_f), self.n_rows, _ptr(self.stamp),
                 self.epoch, _ptr(self.count_f2))
         return self
 
@@ -453,7 +460,8 @@ def spmm_push_rows(graph, rows, src, out, src_indexed, add=None, add_indexed=Fal
     """out += scale * (A^T scatter(src) + scatter(add)) for the rows of a UniqueRows list, A = the matrix of `graph`
     (spex_spmm_push_rows_f32).  src / add: the table itself (indexed=True) or compact [capacity, d] arrays.
     add_scale: a factor of its own for the add term (spex_spmm_push_rows_scaled_f32).  frontier=True: over the whole list of an
-    expanded FrontierRows, not only its Bset part."""
+    expanded FrontierRows, not only its Bset part.  An edge-dropout mask on `graph` is applied entry by entry (A = the masked,
+    1 / keep_prob-scaled matrix)."""
     _need(src, "src"); _need(out, "out"); _need(add, "add")
     d = out.shape[1]
     if out.shape[0] != graph.n_cols or rows.n_rows > graph.n_rows:

@@ -69,7 +69,8 @@ class LightGCNStepper:
         semantics, an opt-in like gather_dtype.  The Adam pass, the clears and the loss sum then cost |F2| rows, not N: pays where F2
         is a small share of a graph that streams from HBM, loses on small graphs.  `stepper.sparse_adam` may be switched off and on
         between steps; while `frontier` is switched off it is ignored (the whole-graph steps run dense Adam).
-        frontier=True (width 64, n_layers >= 2, no edge dropout, not deterministic, gather_dtype not in the constructor — set
+        frontier=True (width 64, n_layers >= 2, not deterministic; edge dropout only with graph_t = the transposed handle and fp32 gather
+        tables, DESIGN.md 4.27, gather_dtype not in the constructor — set
         `stepper.gather_dtype = torch.bfloat16` afterwards for frontier steps on bf16 tables, n_layers 2 or 3; ValueError otherwise): step_bce,
         step_bpr_exact, the native epochs and the sampled epochs take one more level inward (SPEX_STEP_FRONTIER) —
         forward layer L - 1 only at the batch's frontier F1 (its rows and their stored columns), the backward product behind the
@@ -192,6 +193,9 @@ class LightGCNStepper:
             if d != 64 or self.L not in (2, 3):
                 raise ValueError(f"LightGCNStepper(gather_dtype=torch.bfloat16): bf16 gather tables take an embedding width of 64 and "
                                  f"n_layers 2 or 3 (got width {d}, n_layers {self.L})")
+            if self._frontier and self._masked():
+                raise ValueError("LightGCNStepper.gather_dtype = torch.bfloat16: frontier=True with bf16 gather tables does not combine "
+                                 "with edge dropout, and a mask is on: switch it off first (set_edge_dropout(None))")
             if self._sparse_adam:
                 raise ValueError("LightGCNStepper.gather_dtype = torch.bfloat16: not while sparse_adam is on — the row-sparse Adam pass "
                                  "keeps no bf16 shadow of E0 (SPEX_STEP_SPARSE_ADAM does not combine with SPEX_STEP_BF16_GATHER)")
@@ -215,9 +219,21 @@ class LightGCNStepper:
         if on:
             self._grad_ver, self._list_ver = self.grad_E0._version, self._front.list._version
 
-    def _refuse_frontier_dropout(self, who, keep_prob=1.0):
-        if self.frontier and (keep_prob < 1.0 or getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0):
-            raise ValueError(f"{who}: frontier=True does not combine with edge dropout")
+    def _masked(self):
+        return getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
+
+    def _refuse_frontier_dropout(self, who, keep_prob=1.0, masked=None):
+        """Frontier steps run under edge dropout on a stepper that holds a transposed handle and gathers from fp32
+        tables; the two other cases are refused here, before anything is launched."""
+        masked = self._masked() if masked is None else masked
+        if not (self.frontier and (keep_prob < 1.0 or masked)):
+            return
+        if self.graph_t is self.graph:
+            raise ValueError(f"{who}: frontier=True does not combine with edge dropout on a stepper without graph_t = the transposed "
+                             "handle with the edge-id permutation (LightGCN._transposed()): a masked adjacency is not symmetric")
+        if self.gather_dtype is not None:
+            raise ValueError(f"{who}: frontier=True with gather_dtype=torch.bfloat16 does not combine with edge dropout (the bf16 "
+                             "list SpMM has no masked form): switch gather_dtype to None, or run the whole-graph steps")
 
     def refresh_gather_table(self):
         """Re-cast the bf16 gather table from E0 (one streaming launch).  For callers that write `stepper.E0` themselves — loading a
@@ -334,7 +350,12 @@ class LightGCNStepper:
             else:
                 g.spmm(cur, Y=nxt, acc_in=acc_in, acc_out=lo)
             cur = nxt
-        g.spmm_rows(cur, idx_a, idx_b, 0, self.n_u, acc_in=lo, acc_out=self.lo_batch, acc_div=float(L + 1))
+        if self._masked():
+            # (under edge dropout the last layer runs at the batch's distinct rows — the Bset part of the list — through the list-driven
+            #  kernel, which follows the handle's mask; the batch's row-list kernel takes none)
+            g.spmm_rows_dev(cur, fr, acc_in=lo, acc_out=self.lo_batch, acc_div=float(L + 1), frontier=False)
+        else:
+            g.spmm_rows(cur, idx_a, idx_b, 0, self.n_u, acc_in=lo, acc_out=self.lo_batch, acc_div=float(L + 1))
         return self.lo_batch
 
     def _frontier_backward(self, zeroed=False):
@@ -394,7 +415,10 @@ class LightGCNStepper:
         self._ws0_clean = False
         G = self.ws_bwd[0]
         G.zero_()
-        ops.spmm_push_batch(self.graph, users, items, self.n_u, self.grad_slots, G, add=self.grad_slots, scale=1.0 / float(self.L + 1))
+        if self._masked():      # (the batch-driven push takes no mask: the same product from the dense g_out over the Bset part of the list)
+            ops.spmm_push_rows(self.graph, self._front, self.g_out, G, True, add=self.g_out, add_indexed=True, scale=1.0 / float(self.L + 1))
+        else:
+            ops.spmm_push_batch(self.graph, users, items, self.n_u, self.grad_slots, G, add=self.grad_slots, scale=1.0 / float(self.L + 1))
         self._frontier_backward(sp)
         self._clear_row_counts()
         self.t += 1
@@ -454,8 +478,7 @@ class LightGCNStepper:
 
     def set_edge_dropout(self, mask=None):
         """The next steps' edge-dropout mask on graph and graph_t (an edge_dropout_mask(...) tuple; None: off) — model.py:46-55."""
-        if mask is not None and self.frontier:
-            raise ValueError("LightGCNStepper.set_edge_dropout: frontier=True does not combine with edge dropout")
+        self._refuse_frontier_dropout("LightGCNStepper.set_edge_dropout", masked=mask is not None)
         if mask is not None and self.graph_t is self.graph:
             raise ValueError("LightGCNStepper.set_edge_dropout: needs graph_t = the transposed handle with the edge-id permutation "
                              "(LightGCN._transposed()): a masked adjacency is not symmetric")
@@ -478,7 +501,8 @@ class LightGCNStepper:
                 and users.numel() == pos.numel() == neg.numel() >= 1)
 
     def _check_epoch_dropout(self, who, keep_prob):
-        """The native epochs' keep_prob < 1: refused on a frontier stepper, and the step's own mask rule ahead of the call."""
+        """The native epochs' keep_prob < 1: a frontier stepper's own rule (a transposed handle, fp32 tables), and the step's own mask rule
+        ahead of the call."""
         self._refuse_frontier_dropout(f"LightGCNStepper.{who}", keep_prob)
         if keep_prob < 1.0 and (self.L < 2 or self.graph_t is self.graph):
             raise ValueError(f"LightGCNStepper.{who}: edge dropout needs L >= 2 and graph_t = the transposed handle with the edge-id permutation")

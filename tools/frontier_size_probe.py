@@ -4,8 +4,11 @@ its neighbours (F1, the frontier SPEX_STEP_FRONTIER works on) and of two hops, o
 The batch counted is a BCE batch of B samples as an epoch holds them (draw_batch: one positive to five negatives; a positive is a
 uniformly drawn training pair, so its item is degree-weighted; a negative's item is uniform); the entries of a row set are the gathers
 a row-list launch over it would issue.  One JSON line per (graph, batch); --markdown prints the table of DESIGN.md 4.20.
+--keep-prob P (< 1): beside them the sets of the same batch under edge dropout — every stored entry kept with
+probability P (a seeded Bernoulli draw per entry: the sizes do not depend on which generator draws it), F1 = Bset U the columns of the
+KEPT entries of Bset's rows, F2 likewise from F1; --markdown then prints the masked beside the unmasked rows.
 
-usage: python tools/frontier_size_probe.py [--graphs epinion2,20,22] [--batches 256,2048] [--markdown]"""
+usage: python tools/frontier_size_probe.py [--graphs epinion2,20,22] [--batches 256,2048] [--keep-prob 0.3] [--markdown]"""
 import argparse
 import json
 import os
@@ -29,13 +32,16 @@ def graph(which):
     return np.asarray(rowptr, np.int64), np.asarray(col), n_u
 
 
-def neighbours(rowptr, col, rows):
-    """rows U their stored columns, sorted."""
+def neighbours(rowptr, col, rows, keep=None):
+    """rows U their stored columns (keep given: the columns of their kept entries), sorted."""
     mark = np.zeros(len(rowptr) - 1, bool)
     mark[rows] = True
     lens = (rowptr[rows + 1] - rowptr[rows]).astype(np.int64)
     first = np.repeat(rowptr[rows] - (np.cumsum(lens) - lens), lens)        # entry index = position in the concatenation + this
-    mark[col[first + np.arange(int(lens.sum()), dtype=np.int64)]] = True
+    e = first + np.arange(int(lens.sum()), dtype=np.int64)
+    if keep is not None:
+        e = e[keep[e]]
+    mark[col[e]] = True
     return np.flatnonzero(mark)
 
 
@@ -52,7 +58,7 @@ def draw_batch(rowptr, col, n_u, B, rng, num_ng=5):
     return users, items
 
 
-def probe(which, B, seed=0, loaded=None):
+def probe(which, B, seed=0, loaded=None, keep_prob=1.0):
     rowptr, col, n_u = loaded or graph(which)
     n, nnz = len(rowptr) - 1, int(rowptr[-1])
     deg = np.diff(rowptr)
@@ -61,7 +67,14 @@ def probe(which, B, seed=0, loaded=None):
     f1 = neighbours(rowptr, col, bset)
     f2 = neighbours(rowptr, col, f1)
     ent = lambda rows: int(deg[rows].sum())
-    return {"graph": which, "n": n, "nnz": nnz, "B": B, "Bset_rows": len(bset), "Bset_entries": ent(bset), "F1_rows": len(f1),
+    masked = {}
+    if keep_prob < 1.0:
+        keep = np.random.default_rng(seed + 101).random(nnz) < keep_prob
+        f1m = neighbours(rowptr, col, bset, keep)
+        f2m = neighbours(rowptr, col, f1m, keep)
+        masked = {"keep_prob": keep_prob, "F1_rows_masked": len(f1m), "F1_entries_masked": ent(f1m), "two_hop_rows_masked": len(f2m),
+                  "two_hop_entries_masked": ent(f2m)}
+    return {**masked, "graph": which, "n": n, "nnz": nnz, "B": B, "Bset_rows": len(bset), "Bset_entries": ent(bset), "F1_rows": len(f1),
             "F1_entries": ent(f1), "F1_share_of_nnz": ent(f1) / nnz, "two_hop_rows": len(f2), "two_hop_entries": ent(f2),
             "two_hop_share_of_nnz": ent(f2) / nnz}
 
@@ -70,17 +83,25 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="epinion2,20,22")
     ap.add_argument("--batches", default="256")
+    ap.add_argument("--keep-prob", type=float, default=1.0)
     ap.add_argument("--markdown", action="store_true")
     a = ap.parse_args()
     rows = []
     for g in a.graphs.split(","):
         loaded = graph(g)
-        rows += [probe(g, int(b), loaded=loaded) for b in a.batches.split(",")]
+        rows += [probe(g, int(b), loaded=loaded, keep_prob=a.keep_prob) for b in a.batches.split(",")]
     if not a.markdown:
         for r in rows:
             print(json.dumps(r))
         return
     k = lambda x: f"{x / 1e6:.2f} M" if x >= 1e6 else (f"{x / 1e3:.1f} k" if x >= 1e4 else str(x))
+    if a.keep_prob < 1.0:
+        print(f"| graph | batch | batch rows | F1 rows: unmasked / keep_prob {a.keep_prob:g} | F2 rows: unmasked / keep_prob {a.keep_prob:g} |")
+        print("|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['graph']} (N {r['n']}, nnz {k(r['nnz'])}) | B = {r['B']} | {r['Bset_rows']} | {k(r['F1_rows'])} / {k(r['F1_rows_masked'])} | "
+                  f"{k(r['two_hop_rows'])} / {k(r['two_hop_rows_masked'])} |")
+        return
     print("| graph | batch | batch rows / entries | + their neighbours: rows / entries (share of nnz) | two hops: rows / entries (share of nnz) |")
     print("|---|---|---|---|---|")
     for r in rows:
