@@ -449,6 +449,17 @@ int spex_frontier_rows_i32(const spex_graph_t *g, int32_t *list, const int32_t *
  * spex_frontier_rows_i32 itself lists every stored column whatever the mask.  Same arguments, same errors. */
 int spex_frontier_rows_masked_i32(const spex_graph_t *g, int32_t *list, const int32_t *count_b, int32_t max_b, int32_t *stamp, int32_t epoch,
                                   int32_t *count_f, void *stream);
+/* The push over a LONG device list (a two-hop frontier; SPEX_STEP_FRONTIER_DEEP's second backward product):
+ *   out[col[e], :] += scale * val[e] * src[r, :]  for every stored entry e of every row r = list[k], k < min(*count, max_count)
+ * — spex_spmm_push_rows_f32's product with src indexed by row and no add term, in spex_spmm_rowlist_dev_f32's work split: a fixed grid
+ * (<= 2 048 workgroups of 16 list slots per pass) strides over the list, the count is read on the device, a row of at most 64 entries
+ * is one wave's task and longer rows are cut into 64-entry wave tasks dealt to the workgroup's 16 waves.  Every atomic
+ * wave-instruction adds one contiguous 256-byte row of out.  list values outside [0, n_rows) are skipped; entries should be distinct
+ * (a row listed twice is pushed twice).  out: [n_cols, 64], initialised by the caller; src: [n_rows, 64], not out.  A mask on the
+ * handle (edge dropout) is applied entry by entry by a kernel of its own: a kept value is val / keep_prob, a dropped entry issues no
+ * atomic.  d == 64 only: otherwise SPEX_ERR_UNSUPPORTED.  Sums arrive in arbitrary order (float atomics). */
+int spex_spmm_push_list_f32(const spex_graph_t *g, const int32_t *list, const int32_t *count, int32_t max_count, const float *src,
+                            float scale, float *out, int32_t d, void *stream);
 /* spex_spmm_rowlist_f32 driven by such a device list: rows list[k], k < min(*count, max_count), entries distinct (acc_out may
  * therefore alias acc_in); rows outside the list are not written; list values outside [0, n_rows) are skipped.  The same per-row
  * arithmetic and epilogue (Y = y; acc_out = (acc_in + y) / acc_div): bit-identical to spex_spmm_rowlist_f32, and to spex_spmm_f32
@@ -999,9 +1010,14 @@ enum {
     SPEX_STEP_SPARSE_ADAM = 256,        /* with SPEX_STEP_FRONTIER at L == 2 only: row-sparse ("lazy") Adam — p, m, v change at the rows of the
                                          * batch's two-hop set F2 and nowhere else, the step count is global; no launch of the step but the
                                          * first flagged one passes over a whole fp32 table.  Its own semantics: see spex_lightgcn_step_t */
-    SPEX_STEP_GRAD_ROWS_LISTED = 512    /* state, not a mode: "grad_E0 is zero outside frontier_list[0 .. frontier_counts[2])".  Set in the
-                                         * descriptor by a SPEX_STEP_SPARSE_ADAM step once its launches are queued, cleared by every other
-                                         * step of these entry points; a caller that writes grad_E0 or frontier_list itself clears it */
+    SPEX_STEP_GRAD_ROWS_LISTED = 512,   /* state, not a mode: "grad_E0 is zero outside the list the step that set the bit used":
+                                         * frontier_list[0 .. frontier_counts[2]), or [0 .. frontier_counts[3]) where that step carried
+                                         * SPEX_STEP_FRONTIER_DEEP.  Set in the descriptor by a SPEX_STEP_SPARSE_ADAM step once its launches
+                                         * are queued, cleared by every other step of these entry points; a caller that writes grad_E0 or
+                                         * frontier_list itself clears it */
+    SPEX_STEP_FRONTIER_DEEP = 1024      /* with SPEX_STEP_FRONTIER at L == 3, d == 64, fp32 tables only: EVERY launch of the step runs over a
+                                         * device list (y_1 at F2, y_2 at F1, the pushes over F1 and F2), no whole-graph launch is left;
+                                         * with SPEX_STEP_SPARSE_ADAM on top, row-sparse Adam over F3.  See spex_lightgcn_step_t */
 };
 /* The north-star step — LightGCN L-layer propagation + the fused BPR gather + dot + sigmoid + SGD kernel over T triples — as one
  * call of at most L + 1 launches: EVERY whole-graph layer in the plain form (no epilogue operand, one output stream); the layer-1 launch also sets
@@ -1059,7 +1075,7 @@ typedef struct spex_lightgcn_step {
     float lr, beta1, beta2, eps;
     int32_t t;
     int32_t flags;                           /* SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE / _PUSH, SPEX_STEP_WIDE, SPEX_STEP_BF16_GATHER, SPEX_STEP_FRONTIER,
-                                              * SPEX_STEP_SPARSE_ADAM; SPEX_STEP_GRAD_ROWS_LISTED is written back by the steps */
+                                              * SPEX_STEP_SPARSE_ADAM, SPEX_STEP_FRONTIER_DEEP; SPEX_STEP_GRAD_ROWS_LISTED is written back by the steps */
     /* appended for spex_lightgcn_step_bpr_adam_f32 / spex_lightgcn_epoch_bpr_f32 (the BCE entry points never read them): */
     float weight_decay;                      /* >= 0: upstream LightGCN's L2 term on the E0 rows of the batch */
     int32_t *row_counts;                     /* [2, N] int32, all-zero before the first call: per-row occurrence counts, by step parity.
@@ -1072,10 +1088,30 @@ typedef struct spex_lightgcn_step {
     /* appended for SPEX_STEP_FRONTIER (without the flag no entry point reads them): */
     int32_t *frontier_list;                  /* [N] int32: [Bset | F1 minus Bset] of the current step (SPEX_STEP_SPARSE_ADAM: [.. | F2 minus F1]) */
     int32_t *frontier_stamp;                 /* [N] int32, all-zero before the first call; never cleared afterwards */
-    int32_t *frontier_counts;                /* [2] int32: |Bset|, |F1| of the current step; with SPEX_STEP_SPARSE_ADAM [4] int32: |Bset|, |F1|,
-                                              * |F2|, one spare */
+    int32_t *frontier_counts;                /* [2] int32: |Bset|, |F1| of the current step; with SPEX_STEP_SPARSE_ADAM or SPEX_STEP_FRONTIER_DEEP
+                                              * [4] int32: |Bset|, |F1|, |F2|, |F3| (|F3| is written only by a step that carries both) */
     int32_t frontier_epoch;                  /* the last stamp used (0 at first); advanced by every flagged step */
 } spex_lightgcn_step_t;
+/* flags & SPEX_STEP_FRONTIER_DEEP — the L == 3 frontier step with no whole-graph launch (with SPEX_STEP_FRONTIER, d == 64, fp32 tables;
+ * BCE and exact BPR, weight_decay > 0 too, under edge dropout too, and every epoch, sampled-epoch and train_*_sampled call over them;
+ * DESIGN.md 4.28).  With F2 = F1 U the stored (and, under a mask, kept) columns of F1's rows, F3 likewise behind F2:
+ *   lists:     Bset, F1, F2 as SPEX_STEP_SPARSE_ADAM builds them at L == 2 (frontier_counts[0 .. 2]); with SPEX_STEP_SPARSE_ADAM a third
+ *              spex_frontier_rows_masked_i32 over [0, |F2|) writes |F3| to frontier_counts[3].
+ *   forward:   y_1 = A E0 at the rows of F2 into ws_fwd[0], y_2 = A y_1 at the rows of F1 into ws_fwd[1], both by
+ *              spex_spmm_rowlist_dev_f32 in the plain form; the batch launch is the L == 3 step's own.  It reads y_2 at the columns of
+ *              Bset's rows (in F1); y_2 at F1 reads y_1 at the columns of F1's rows (in F2).  Rows of ws_fwd outside the lists hold
+ *              whatever an earlier step left there: nothing reads them, and a caller must not either.
+ *   backward:  P, the batch launch's push target ws_bwd[0], is supported in F1; W = A^T P is the push over the F1 list into ws_bwd[1]
+ *              (supported in F2); grad_E0 = A^T W is a push over the F2 list (supported in F3; both by spex_spmm_push_list_f32); the Adam
+ *              pass adds P, as in the L == 3 step without the flag.  Dense Adam: both push targets are cleared whole by launches of
+ *              the step.
+ *   with SPEX_STEP_SPARSE_ADAM: that flag's law with F3 in place of F2 — p, m, v change at the rows of F3 and nowhere else; P is
+ *              read, added and cleared below |F1|, W is cleared below |F2|, the L2 occurrence counts stay keyed to Bset, grad_E0
+ *              is cleared by list (frontier_counts[3]) at the next flagged step; then no launch passes over a whole fp32 table.
+ * The results are the L == 3 step's up to the order of the float atomics (two pushes where SPEX_STEP_FRONTIER alone has one).
+ * Refused before anything touches the device (t not advanced): the flag without SPEX_STEP_FRONTIER, L != 3, SPEX_STEP_BF16_GATHER,
+ * SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE -> SPEX_ERR_INVALID; d != 64 or SPEX_STEP_WIDE -> SPEX_ERR_UNSUPPORTED; a mask where
+ * graph_t == graph -> SPEX_ERR_INVALID (the rule of every masked step). */
 /* flags & SPEX_STEP_SPARSE_ADAM — row-sparse Adam for the L == 2 frontier steps (with SPEX_STEP_FRONTIER, d == 64; BCE and exact BPR,
  * weight_decay > 0 too, and every epoch, sampled-epoch and train_*_sampled call over them).  The step computes the forward, the loss
  * and the gradient of the SPEX_STEP_FRONTIER step.  At L == 2 that gradient's support is structural: it lies in
@@ -1097,7 +1133,8 @@ typedef struct spex_lightgcn_step {
  * SPEX_STEP_GRAD_ROWS_LISTED (see the flag); without the bit it clears the whole table once.  The exact BPR step clears the other
  * parity's row_counts table whole (4 N bytes) instead of in the Adam pass; the tables satisfy the same contract afterwards.
  * g_out and ws_bwd[0] are all-zero after every step, as without the flag.
- * Refused before anything touches the device (t not advanced): SPEX_STEP_SPARSE_ADAM without SPEX_STEP_FRONTIER, with L != 2, or
+ * Refused before anything touches the device (t not advanced): SPEX_STEP_SPARSE_ADAM without SPEX_STEP_FRONTIER, with L != 2 (L == 3 is taken together
+ * with SPEX_STEP_FRONTIER_DEEP: see that flag), or
  * together with SPEX_STEP_BF16_GATHER (the row-sparse pass keeps no bf16 shadow of E0) -> SPEX_ERR_INVALID; everything
  * SPEX_STEP_FRONTIER refuses stays refused. */
 /* flags & SPEX_STEP_FRONTIER — the exact steps with one more level taken inward (d == 64, L >= 2).  With Bset the batch's

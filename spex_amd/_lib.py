@@ -108,6 +108,7 @@ SIGNATURES = {
     "spex_spmm_push_rows_scaled_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_i32, c_vp]),
     "spex_frontier_rows_i32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "spex_frontier_rows_masked_i32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "spex_spmm_push_list_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_f32, c_vp, c_i32, c_vp]),
     "spex_adam_rows_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp]),
     "spex_zero_rows_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "spex_spmm_rowlist_dev_f32": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_f32, c_i32, c_vp]),
@@ -216,6 +217,7 @@ STEP_BF16_GATHER = 64           # spex_hip.h: SPEX_STEP_BF16_GATHER (bf16 gather
 STEP_FRONTIER = 128             # spex_hip.h: SPEX_STEP_FRONTIER (layer L - 1 and the second backward product over the batch's frontier, d = 64, L >= 2)
 STEP_SPARSE_ADAM = 256          # spex_hip.h: SPEX_STEP_SPARSE_ADAM (row-sparse Adam over the batch's two-hop set, with STEP_FRONTIER at L = 2)
 STEP_GRAD_ROWS_LISTED = 512     # spex_hip.h: SPEX_STEP_GRAD_ROWS_LISTED (state written back by the steps: grad_E0 is zero outside the frontier list)
+STEP_FRONTIER_DEEP = 1024       # spex_hip.h: SPEX_STEP_FRONTIER_DEEP (every launch of the L = 3 frontier step over a device list; with STEP_SPARSE_ADAM: Adam over F3)
 
 
 class NGCFStepDesc(ctypes.Structure):

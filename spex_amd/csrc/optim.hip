@@ -166,12 +166,15 @@ __global__ __launch_bounds__(256) void adam_shadow_kernel(float *__restrict__ p,
 // not served: the caller clears that table).  The per-sample losses are summed by the first wave in adam_body's order.
 constexpr int kRowsFly = 2;
 
-template <bool L2>
-__global__ __launch_bounds__(256) void adam_rows_kernel(float *__restrict__ p, const float *g, float *__restrict__ m,
-                                                        float *__restrict__ v, const spex::AdamRowList rl, float w1, float beta2,
-                                                        float w2, float bc2_sqrt, float eps, float step_size,
-                                                        const float *__restrict__ loss_rows, int n_loss, float *loss_sum,
-                                                        const spex::L2Rows l2)
+// ADD_RANGE (adam_rows_range_kernel, the SPEX_STEP_FRONTIER_DEEP step's pass over [Bset | F1 minus Bset | F2 minus F1 | F3 minus F2]):
+// the add term has a count cell of its own, *count_a — there it is P, supported in F1, while the L2 counts stay keyed to Bset.  A
+// kernel name of its own around the one body: adam_rows_kernel keeps its arguments and its registers.
+template <bool L2, bool ADD_RANGE>
+__device__ __forceinline__ void adam_rows_body(float *__restrict__ p, const float *g, float *__restrict__ m,
+                                               float *__restrict__ v, const spex::AdamRowList rl, float w1, float beta2,
+                                               float w2, float bc2_sqrt, float eps, float step_size,
+                                               const float *__restrict__ loss_rows, int n_loss, float *loss_sum,
+                                               const spex::L2Rows l2, const int32_t *__restrict__ count_a)
 {
     if (loss_rows && blockIdx.x == 0 && threadIdx.x < spex::kWave) {
         float t = 0.0f;
@@ -182,6 +185,7 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(float *__restrict__ p, c
     const int cnt = *rl.count;
     const int n = cnt < rl.max_count ? cnt : rl.max_count;
     const int nb = rl.count_b ? *rl.count_b : 0, nz = rl.count_z ? *rl.count_z : 0;
+    const int na = ADD_RANGE ? *count_a : nb;
     const int lane = threadIdx.x & (spex::kWave - 1), sub = lane >> 4, c4 = lane & 15;
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t base = wave * (4 * kRowsFly); base < n; base += n_waves * (4 * kRowsFly)) {
@@ -201,6 +205,8 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(float *__restrict__ p, c
             if constexpr (L2)
                 if (head[u] && l2.count) c[u] = l2.scale * (float)l2.count[r];
         }
+        // the add term's rows: below *count_a where it has a range of its own, the counts' rows otherwise (ok[u] holds where this is asked)
+        auto adds = [&](int u) { return (ADD_RANGE ? k[u] < na : head[u]) && rl.add_g; };
 #pragma unroll
         for (int u = 0; u < kRowsFly; ++u) {
             if (!ok[u]) continue;
@@ -208,12 +214,12 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(float *__restrict__ p, c
             G[u] = reinterpret_cast<const float4 *>(g)[at[u]];
             M[u] = reinterpret_cast<float4 *>(m)[at[u]];
             V[u] = reinterpret_cast<float4 *>(v)[at[u]];
-            if (head[u] && rl.add_g) A[u] = reinterpret_cast<const float4 *>(rl.add_g)[at[u]];
+            if (adds(u)) A[u] = reinterpret_cast<const float4 *>(rl.add_g)[at[u]];
         }
 #pragma unroll
         for (int u = 0; u < kRowsFly; ++u) {
             if (!ok[u]) continue;
-            if (head[u] && rl.add_g) {
+            if (adds(u)) {
                 add_share(G[u], A[u], rl.add_div);
                 reinterpret_cast<float4 *>(rl.add_g)[at[u]] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
@@ -228,6 +234,26 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(float *__restrict__ p, c
             if (rl.zero_buf && k[u] < nz) reinterpret_cast<float4 *>(rl.zero_buf)[at[u]] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
     }
+}
+
+template <bool L2>
+__global__ __launch_bounds__(256) void adam_rows_kernel(float *__restrict__ p, const float *g, float *__restrict__ m,
+                                                        float *__restrict__ v, const spex::AdamRowList rl, float w1, float beta2,
+                                                        float w2, float bc2_sqrt, float eps, float step_size,
+                                                        const float *__restrict__ loss_rows, int n_loss, float *loss_sum,
+                                                        const spex::L2Rows l2)
+{
+    adam_rows_body<L2, false>(p, g, m, v, rl, w1, beta2, w2, bc2_sqrt, eps, step_size, loss_rows, n_loss, loss_sum, l2, nullptr);
+}
+
+template <bool L2>
+__global__ __launch_bounds__(256) void adam_rows_range_kernel(float *__restrict__ p, const float *g, float *__restrict__ m,
+                                                              float *__restrict__ v, const spex::AdamRowList rl, float w1, float beta2,
+                                                              float w2, float bc2_sqrt, float eps, float step_size,
+                                                              const float *__restrict__ loss_rows, int n_loss, float *loss_sum,
+                                                              const spex::L2Rows l2, const int32_t *__restrict__ count_a)
+{
+    adam_rows_body<L2, true>(p, g, m, v, rl, w1, beta2, w2, bc2_sqrt, eps, step_size, loss_rows, n_loss, loss_sum, l2, count_a);
 }
 
 // x[list[k], :] = 0 for k < min(*count, max_count): one float4 per thread and pass, a fixed grid striding over the listed rows.
@@ -248,8 +274,10 @@ __global__ __launch_bounds__(256) void zero_rows_kernel(float *__restrict__ x, c
 
 // The row-sparse pass (adam_rows_kernel) with the one-call steps' side jobs.
 int spex::adam_rows(float *p, const float *g, float *m, float *v, const spex::AdamRowList &rl, int32_t t, float lr, float beta1, float beta2,
-                    float eps, void *stream, const float *loss_rows, int32_t n_loss, float *loss_sum, const spex::L2Rows *l2_in)
+                    float eps, void *stream, const float *loss_rows, int32_t n_loss, float *loss_sum, const spex::L2Rows *l2_in,
+                    const int32_t *count_a)
 {
+    SPEX_CHECK_ARG(!count_a || rl.add_g, "spex_adam_rows_f32: a count cell for the add term without the term");
     SPEX_CHECK_ARG(p && g && m && v && rl.list && rl.count, "spex_adam_rows_f32: NULL pointer");
     SPEX_CHECK_ARG(rl.max_count >= 0 && rl.n_rows >= 0 && t >= 1, "spex_adam_rows_f32: max_count=%d n_rows=%d t=%d (t counts from 1)", rl.max_count,
                    rl.n_rows, t);
@@ -275,10 +303,13 @@ int spex::adam_rows(float *p, const float *g, float *m, float *v, const spex::Ad
     constexpr int kSlotsPerBlock = 4 * 4 * kRowsFly;          // four waves of four-row groups
     int64_t blocks = ((int64_t)rl.max_count + kSlotsPerBlock - 1) / kSlotsPerBlock;
     blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-#define SPEX_ROWS_GO(KERNEL)                                                                                                                 \
+#define SPEX_ROWS_GO(KERNEL, ...)                                                                                                            \
     hipLaunchKernelGGL(KERNEL, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, rl, 1.0f - beta1, beta2, 1.0f - beta2, \
-                       bc2_sqrt, eps, step_size, loss_rows, (int)n_loss, loss_sum, l2)
-    if (l2_in) SPEX_ROWS_GO(adam_rows_kernel<true>);
+                       bc2_sqrt, eps, step_size, loss_rows, (int)n_loss, loss_sum, l2, ##__VA_ARGS__)
+    if (count_a) {         // the add term's own range: the kernel of that name
+        if (l2_in) SPEX_ROWS_GO(adam_rows_range_kernel<true>, count_a);
+        else SPEX_ROWS_GO(adam_rows_range_kernel<false>, count_a);
+    } else if (l2_in) SPEX_ROWS_GO(adam_rows_kernel<true>);
     else SPEX_ROWS_GO(adam_rows_kernel<false>);
 #undef SPEX_ROWS_GO
     SPEX_HIP(hipGetLastError());

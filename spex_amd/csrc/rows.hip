@@ -11,6 +11,8 @@
 //   spex_spmm_push_rows_f32   out[col[e], :] += scale * val[e] * src_k  for every stored entry e of every listed row (k-th
 //                             listed row r: src_k = src[r] or src[k]), optionally out[r, :] += scale * add_k — 256-byte float atomics
 //                             (spex_spmm_push_rows_scaled_f32: a factor of its own for the add term)
+//   spex_spmm_push_list_f32   the same product (src by row, no add term) over a LONG device list — a two-hop frontier — in the list
+//                             SpMM's work split: a fixed grid over the list, short rows one wave task each (follows the mask too)
 //   spex_frontier_rows_i32    behind such a list, the stored columns of its rows not yet stamped this epoch: the batch's frontier
 //                             (spex_frontier_rows_masked_i32: the columns reached over entries the handle's edge dropout keeps)
 // spex_spmm_push_rows_f32 and _scaled_f32 follow the handle's edge-dropout rule (a kept value is val / keep_prob, a dropped entry
@@ -160,6 +162,108 @@ __global__ __launch_bounds__(kWave *kWgWaves) void spmm_push_rows_masked_kernel(
     int src_indexed, const float *__restrict__ add, int add_indexed, float scale, float add_scale, float *out, int d, const EdgeDrop dr)
 {
     spmm_push_rows_body<true>(rowptr, col, val, list, count, n_rows, src, src_indexed, add, add_indexed, scale, add_scale, out, d, dr);
+}
+
+// The push over a LONG list (a two-hop frontier F2: 10^5 .. 10^6 rows, median 13 entries) in rowlist_dev_body's work
+// split (spmm_chunk.h): a fixed grid of 16-wave workgroups strides over the list in passes of 16 slots, the count is read on the
+// device.  Part 1: wave w owns slot w; a row of at most 64 entries is ONE wave task — one coalesced (col, val) load, lane j holding
+// entry j, the row's source in lane == column, the atomics back to back.  Part 2: the longer rows of the pass are cut into 64-entry
+// wave tasks (a 1 500-entry hub row: 24), dealt round-robin to the 16 waves.  spmm_push_rows_kernel's one workgroup per row leaves
+// 15 of 16 waves idle on a 13-entry row and serialises a workgroup's rows.  Every atomic wave-instruction is one contiguous 256-byte
+// row of `out`.  d == 64; the source is indexed by row; no add term.
+constexpr int kPushListMaxWgs = 2048;
+
+// One wave task: entries [e0, e0 + cnt), cnt <= 64, of a row whose scaled source value this lane holds in g.  MASKED: the lanes that
+// hold the run decide `kept` (edge_kept: the handle's edge-dropout rule, the forward's), a kept value is val / keep_prob, and the
+// entry loop walks the wave-uniform ballot of the kept lanes: a dropped entry issues no atomic, a run with none kept issues nothing.
+// The first entry is read before the first atomic and the entry loop is a real loop: see spmm_push_batch_kernel.
+template <bool MASKED>
+__device__ __forceinline__ void push_list_task(const int32_t *__restrict__ col, const float *__restrict__ val, int e0, int cnt, int lane, float g,
+                                               float *out_l, const EdgeDrop &dr)
+{
+    int my_col = 0;
+    float my_val = 0.0f;
+    bool kept = false;
+    if (lane < cnt) {
+        my_col = col[e0 + lane];
+        my_val = val[e0 + lane];
+        kept = true;
+        if (MASKED) {
+            kept = edge_kept(dr, e0 + lane);
+            my_val = kept ? my_val / dr.keep_prob : 0.0f;
+        }
+    }
+    unsigned long long todo = MASKED ? __ballot(kept) : (cnt >= kWave ? ~0ull : (1ull << cnt) - 1ull);      // (wave-uniform)
+    if (todo == 0) return;
+    const int j0 = (int)__builtin_ctzll(todo);
+    const int cc0 = __builtin_amdgcn_readlane(my_col, j0);
+    const float v0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val), j0));
+    atomicAdd(out_l + (size_t)(uint32_t)cc0 * kWave, v0 * g);
+    todo &= todo - 1;
+#pragma unroll 1
+    while (todo) {
+        const int j = (int)__builtin_ctzll(todo);
+        todo &= todo - 1;
+        const int cc = __builtin_amdgcn_readlane(my_col, j);
+        const float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_val), j));
+        atomicAdd(out_l + (size_t)(uint32_t)cc * kWave, v * g);
+    }
+}
+
+template <bool MASKED>
+__device__ __forceinline__ void spmm_push_list_body(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, const int32_t *__restrict__ list,
+    const int32_t *__restrict__ count, int32_t max_count, int32_t n_rows, const float *__restrict__ src, float scale, float *out,
+    const EdgeDrop &dr)
+{
+    __shared__ int s_nt[kWgWaves];                 // 64-entry tasks of each of the pass's 16 slots (0: no row, or a row of one task)
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n = *count < max_count ? *count : max_count;
+    float *out_l = out + lane;
+    for (int k0 = blockIdx.x * kWgWaves; k0 < n; k0 += gridDim.x * kWgWaves) {      // workgroup-uniform
+        // ---- part 1: one slot per wave
+        int r = -1, beg = 0, deg = 0;
+        if (k0 + wave < n) {
+            r = list[k0 + wave];
+            if (r < 0 || r >= n_rows) r = -1;      // never index the matrix out of range
+        }
+        if (r >= 0) {
+            beg = rowptr[r];
+            deg = rowptr[r + 1] - beg;
+        }
+        const int nseg = (deg + kTaskEntries - 1) / kTaskEntries;
+        if (lane == 0) s_nt[wave] = nseg > 1 ? nseg : 0;
+        if (r >= 0 && nseg == 1) push_list_task<MASKED>(col, val, beg, deg, lane, scale * src[(size_t)r * kWave + lane], out_l, dr);
+        __syncthreads();
+        // ---- part 2: the longer rows' tasks, round-robin over the 16 waves (s_nt[j] > 0 only for an in-range row)
+        int total = 0;
+        for (int j = 0; j < kWgWaves; ++j) total += s_nt[j];
+        for (int t = wave; t < total; t += kWgWaves) {
+            int j = 0, base = 0;
+            while (t >= base + s_nt[j]) base += s_nt[j++];
+            const int rj = list[k0 + j];
+            const int bj = rowptr[rj], dj = rowptr[rj + 1] - bj, sg = t - base;
+            const int cnt = dj - sg * kTaskEntries < kTaskEntries ? dj - sg * kTaskEntries : kTaskEntries;
+            push_list_task<MASKED>(col, val, bj + sg * kTaskEntries, cnt, lane, scale * src[(size_t)rj * kWave + lane], out_l, dr);
+        }
+        __syncthreads();                            // s_nt is rewritten by the next pass
+    }
+}
+
+__global__ __launch_bounds__(kWave *kWgWaves) void spmm_push_list_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, const int32_t *__restrict__ list,
+    const int32_t *__restrict__ count, int32_t max_count, int32_t n_rows, const float *__restrict__ src, float scale, float *out)
+{
+    spmm_push_list_body<false>(rowptr, col, val, list, count, max_count, n_rows, src, scale, out, EdgeDrop{nullptr, nullptr, 0, 1.0f, 0u, 0u});
+}
+
+__global__ __launch_bounds__(kWave *kWgWaves) void spmm_push_list_masked_kernel(
+    const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val, const int32_t *__restrict__ list,
+    const int32_t *__restrict__ count, int32_t max_count, int32_t n_rows, const float *__restrict__ src, float scale, float *out,
+    const EdgeDrop dr)
+{
+    spmm_push_list_body<true>(rowptr, col, val, list, count, max_count, n_rows, src, scale, out, dr);
 }
 
 // The same product driven by the batch itself, EVERY slot contributing: slot k (row idx_a[k] + off_a, then idx_b[k] + off_b)
@@ -504,6 +608,30 @@ extern "C" int spex_spmm_push_rows_scaled_f32(const spex_graph_t *g, const int32
 {
     return push_rows("spex_spmm_push_rows_scaled_f32", g, list, count, max_count, src, src_indexed, add, add_indexed, scale, add_scale, out, d,
                      stream);
+}
+
+// out[col[e], :] += scale * val[e] * src[r, :] for every stored entry e of every row r = list[k], k < min(*count, max_count), in the
+// long-list work split (spmm_push_list_kernel); follows the handle's edge-dropout rule as spex_spmm_push_rows_f32 does.
+extern "C" int spex_spmm_push_list_f32(const spex_graph_t *g, const int32_t *list, const int32_t *count, int32_t max_count, const float *src,
+                                       float scale, float *out, int32_t d, void *stream)
+{
+    SPEX_CHECK_ARG(g && list && count && src && out, "spex_spmm_push_list_f32: NULL argument");
+    SPEX_CHECK_ARG(max_count >= 0 && src != out, "spex_spmm_push_list_f32: max_count=%d, or src aliases out", max_count);
+    if (d != kWave) {
+        spex::set_error("spex_spmm_push_list_f32: d == 64 only (got %d)", d);
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    if (max_count == 0 || g->n_rows == 0) return SPEX_OK;
+    const int64_t wgs = ((int64_t)max_count + kWgWaves - 1) / kWgWaves;
+    const dim3 grid((unsigned)(wgs < kPushListMaxWgs ? wgs : kPushListMaxWgs));
+    if (g->mask_mode != 0)      // the handle's edge-dropout rule per entry: a kernel of its own
+        hipLaunchKernelGGL(spmm_push_list_masked_kernel, grid, dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val, list, count,
+                           max_count, g->n_rows, src, scale, out, edge_drop_of(g));
+    else
+        hipLaunchKernelGGL(spmm_push_list_kernel, grid, dim3(kWave * kWgWaves), 0, (hipStream_t)stream, g->rowptr, g->col, g->val, list, count,
+                           max_count, g->n_rows, src, scale, out);
+    SPEX_HIP(hipGetLastError());
+    return SPEX_OK;
 }
 
 static int frontier_rows(const char *who, bool masked, const spex_graph_t *g, int32_t *list, const int32_t *count_b, int32_t max_b, int32_t *stamp,

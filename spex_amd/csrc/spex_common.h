@@ -46,7 +46,9 @@ struct AdamRowList {            // the rows of a row-sparse Adam pass and its si
 };
 int adam_rows(float *p, const float *g, float *m, float *v, const AdamRowList &rl, int32_t t, float lr, float beta1, float beta2, float eps,
               void *stream, const float *loss_rows = nullptr, int32_t n_loss = 0, float *loss_sum = nullptr,
-              const L2Rows *l2 = nullptr);    // optim.hip: spex_adam_rows_f32 with the one-call steps' side jobs (d == 64)
+              const L2Rows *l2 = nullptr, const int32_t *count_a = nullptr);
+                                              // optim.hip: spex_adam_rows_f32 with the one-call steps' side jobs (d == 64); count_a: a device
+                                              // cell for the add term's range where it is not count_b's (the deep step: P lives in F1)
 
 int dual_task_adam(float *p, float *m, float *v, const float *g_E0, float *g_raw, float *g_user, float *g_small, float *g_prop,
                    float *push_zero, float *loss, float *loss_acc, float *prec, int64_t n_table, int64_t n_user, int64_t n_trust,

@@ -111,7 +111,7 @@ static int frontier_step_check(const spex_lightgcn_step_t *s, const char *who)
     SPEX_CHECK_ARG((s->flags & SPEX_STEP_BF16_GATHER) == 0 || (s->graph->mask_mode == 0 && s->graph_t->mask_mode == 0),
                    "%s: SPEX_STEP_FRONTIER | SPEX_STEP_BF16_GATHER does not combine with edge dropout", who);
     SPEX_CHECK_ARG(s->frontier_list && s->frontier_stamp && s->frontier_counts,
-                   "%s: SPEX_STEP_FRONTIER needs frontier_list ([N] int32), frontier_stamp ([N] int32, zeroed once) and frontier_counts ([2] int32)", who);
+                   "%s: SPEX_STEP_FRONTIER needs frontier_list ([N] int32), frontier_stamp ([N] int32, zeroed once) and frontier_counts ([2] int32; [4] with SPEX_STEP_SPARSE_ADAM or SPEX_STEP_FRONTIER_DEEP)", who);
     return SPEX_OK;
 }
 
@@ -123,44 +123,80 @@ static int sparse_adam_check(const spex_lightgcn_step_t *s, const char *who)
     SPEX_CHECK_ARG((s->flags & SPEX_STEP_BF16_GATHER) == 0,
                    "%s: SPEX_STEP_SPARSE_ADAM does not combine with SPEX_STEP_BF16_GATHER (the row-sparse Adam pass keeps no bf16 shadow of E0)", who);
     SPEX_CHECK_ARG((s->flags & SPEX_STEP_FRONTIER) != 0, "%s: SPEX_STEP_SPARSE_ADAM needs SPEX_STEP_FRONTIER (the row list is the frontier's)", who);
-    SPEX_CHECK_ARG(s->L == 2, "%s: SPEX_STEP_SPARSE_ADAM needs L == 2 (got %d): behind a whole-graph pull the gradient is dense", who, s->L);
+    SPEX_CHECK_ARG(s->L == 2 || (s->L == 3 && (s->flags & SPEX_STEP_FRONTIER_DEEP) != 0),
+                   "%s: SPEX_STEP_SPARSE_ADAM needs L == 2, or L == 3 with SPEX_STEP_FRONTIER_DEEP (got L = %d): behind a whole-graph pull the gradient is dense",
+                   who, s->L);
     return SPEX_OK;
 }
 
+// ---- SPEX_STEP_FRONTIER_DEEP (with SPEX_STEP_FRONTIER, L == 3, d == 64, fp32 tables; include/spex_hip.h): every launch
+//      of the step runs over a device list — y_1 at F2, y_2 at F1, W = A^T P over F1, grad_E0 = A^T W over F2 — and, with
+//      SPEX_STEP_SPARSE_ADAM, Adam over F3.  Checked in front of the two other checks, like them before anything touches the device.
+static int deep_step_check(const spex_lightgcn_step_t *s, const char *who)
+{
+    if (s->d != 64 || (s->flags & SPEX_STEP_WIDE) != 0) {
+        spex::set_error("%s: SPEX_STEP_FRONTIER_DEEP takes d == 64 only (got d = %d%s): run other widths without the flag", who, s->d,
+                        (s->flags & SPEX_STEP_WIDE) != 0 ? ", SPEX_STEP_WIDE" : "");
+        return SPEX_ERR_UNSUPPORTED;
+    }
+    SPEX_CHECK_ARG((s->flags & SPEX_STEP_FRONTIER) != 0, "%s: SPEX_STEP_FRONTIER_DEEP needs SPEX_STEP_FRONTIER (it takes that form one level further)", who);
+    SPEX_CHECK_ARG(s->L == 3, "%s: SPEX_STEP_FRONTIER_DEEP needs L == 3 (got %d): at L == 2 SPEX_STEP_FRONTIER leaves no whole-graph launch, L >= 4 is not built",
+                   who, s->L);
+    SPEX_CHECK_ARG((s->flags & SPEX_STEP_BF16_GATHER) == 0,
+                   "%s: SPEX_STEP_FRONTIER_DEEP does not combine with SPEX_STEP_BF16_GATHER (fp32 tables only)", who);
+    return SPEX_OK;       // (SPEX_STEP_DETERMINISTIC, SPEX_STEP_BPR_DENSE, NULL list fields: frontier_step_check's refusals)
+}
+
 // The first launch of a flagged step: grad_E0, the frontier push's target, all-zero again — through the list the previous flagged step
-// left (SPEX_STEP_GRAD_ROWS_LISTED: nothing else wrote the table since) or, without the bit, over the whole table once.
+// left (SPEX_STEP_GRAD_ROWS_LISTED: nothing else wrote the table since) or, without the bit, over the whole table once.  The deep
+// step (L == 3) pushes into two tables: with the bit, W is all-zero as well (the flagged step before has cleared it below |F2|).
 static int sparse_adam_begin(spex_lightgcn_step_t *s, size_t sz, void *stream)
 {
     const bool listed = (s->flags & SPEX_STEP_GRAD_ROWS_LISTED) != 0;
     s->flags &= ~SPEX_STEP_GRAD_ROWS_LISTED;        // (set again once every launch of the step is queued)
-    if (listed) return spex_zero_rows_f32(s->grad_E0, s->frontier_list, s->frontier_counts + 2, s->graph->n_rows, s->graph->n_rows, s->d, stream);
+    // (the cell of the step that set the bit: a flagged L == 3 step is a SPEX_STEP_FRONTIER_DEEP step and lists F3, an L == 2 step F2)
+    if (listed) return spex_zero_rows_f32(s->grad_E0, s->frontier_list, s->frontier_counts + s->L, s->graph->n_rows, s->graph->n_rows, s->d, stream);
+    // L == 3: W = ws_bwd[1], the F1 push's target, too — the flagged step before this one has cleared it by list, any other step has not
+    if (s->L == 3) SPEX_TRY(spex::zero_f32(s->ws_bwd + sz, (int64_t)sz, stream));
     return spex::zero_f32(s->grad_E0, (int64_t)sz, stream);
 }
 
 // The row-sparse Adam pass of a flagged step over frontier_list[0 .. |F2|): g_out / 3 read and cleared below |Bset|, the batch
-// kernel's push target ws_bwd[0] cleared below |F1|, the per-sample losses summed in the dense pass's order.
+// kernel's push target ws_bwd[0] cleared below |F1|, the per-sample losses summed in the dense pass's order.  L == 3: over F3, below.
 static int sparse_adam_pass(spex_lightgcn_step_t *s, int32_t t_next, int32_t n_loss, float *loss_sum, const spex::L2Rows *l2, void *stream)
 {
     spex::AdamRowList rl;
+    const int32_t *count_a = nullptr;
     rl.list = s->frontier_list;
-    rl.count = s->frontier_counts + 2;
     rl.max_count = rl.n_rows = s->graph->n_rows;
     rl.count_b = s->frontier_counts;
-    rl.add_g = s->g_out;
-    rl.add_div = (float)(s->L + 1);
-    rl.count_z = s->frontier_counts + 1;
-    rl.zero_buf = s->ws_bwd;
-    SPEX_TRY(spex::adam_rows(s->E0, s->grad_E0, s->m, s->v, rl, t_next, s->lr, s->beta1, s->beta2, s->eps, stream, s->grad_slots, n_loss, loss_sum, l2));
+    if (s->L == 3) {
+        // SPEX_STEP_FRONTIER_DEEP: over frontier_list[0 .. |F3|); the add term is P (the batch launch's push target, support in F1:
+        // read, added and cleared below |F1|), W = ws_bwd[1] is cleared below |F2|; the L2 counts stay keyed to Bset
+        rl.count = s->frontier_counts + 3;
+        rl.add_g = s->ws_bwd;
+        rl.add_div = 1.0f;
+        count_a = s->frontier_counts + 1;
+        rl.count_z = s->frontier_counts + 2;
+        rl.zero_buf = s->ws_bwd + (size_t)s->graph->n_rows * s->d;
+    } else {
+        rl.count = s->frontier_counts + 2;
+        rl.add_g = s->g_out;
+        rl.add_div = (float)(s->L + 1);
+        rl.count_z = s->frontier_counts + 1;
+        rl.zero_buf = s->ws_bwd;
+    }
+    SPEX_TRY(spex::adam_rows(s->E0, s->grad_E0, s->m, s->v, rl, t_next, s->lr, s->beta1, s->beta2, s->eps, stream, s->grad_slots, n_loss, loss_sum, l2, count_a));
     s->flags |= SPEX_STEP_GRAD_ROWS_LISTED;
     return SPEX_OK;
 }
 
-// Bset, then F1 behind it, of a batch of up to three index lists into frontier_list; frontier_counts = { |Bset|, |F1| }.  two_hop
-// (SPEX_STEP_SPARSE_ADAM): F2 behind F1 by a second pass of the same kernel over [0, |F1|); frontier_counts[2] = |F2|.  Under edge
+// Bset, then F1 behind it, of a batch of up to three index lists into frontier_list; frontier_counts = { |Bset|, |F1| }.  hops == 2
+// (SPEX_STEP_SPARSE_ADAM, SPEX_STEP_FRONTIER_DEEP): F2 behind F1 by a second pass of the same kernel over [0, |F1|); frontier_counts[2] = |F2|.  Under edge
 // dropout both hops list the columns reached over KEPT entries only (the handle's mask of this step, set before the call): the masked
 // F1 holds every row the batch kernel reads or pushes into, the masked F2 every row the frontier push can write.
 static int frontier_lists(spex_lightgcn_step_t *s, const int64_t *a, int32_t n_a, const int64_t *b, int32_t n_b, const int64_t *c, int32_t n_c,
-                          void *stream, bool two_hop = false)
+                          void *stream, int hops = 1)
 {
     const spex_graph *g = s->graph;
     const int32_t epoch = s->frontier_epoch % 0x7FFFFFFF + 1;      // never 0
@@ -171,8 +207,11 @@ static int frontier_lists(spex_lightgcn_step_t *s, const int64_t *a, int32_t n_a
     const int64_t slots = (int64_t)n_a + n_b + (c ? n_c : 0);
     SPEX_TRY(spex_frontier_rows_masked_i32(g, s->frontier_list, s->frontier_counts, (int32_t)(slots < g->n_rows ? slots : g->n_rows), s->frontier_stamp,
                                            epoch, s->frontier_counts + 1, stream));
-    if (!two_hop) return SPEX_OK;
-    return spex_frontier_rows_masked_i32(g, s->frontier_list, s->frontier_counts + 1, g->n_rows, s->frontier_stamp, epoch, s->frontier_counts + 2, stream);
+    // (each further hop walks the rows the hop before appended AND those before them, whose columns are stamped already: one kernel,
+    //  one rule.  hops == 3, SPEX_STEP_FRONTIER_DEEP | SPEX_STEP_SPARSE_ADAM: F3 behind F2, the rows the push over F2 can write)
+    for (int h = 2; h <= hops; ++h)
+        SPEX_TRY(spex_frontier_rows_masked_i32(g, s->frontier_list, s->frontier_counts + h - 1, g->n_rows, s->frontier_stamp, epoch, s->frontier_counts + h, stream));
+    return SPEX_OK;
 }
 
 // SPEX_STEP_FRONTIER | SPEX_STEP_BF16_GATHER (L = 2 or 3): y_(L-1) at the rows of F1 from the bf16 table of the layer
@@ -215,6 +254,13 @@ static int frontier_backward(const spex_lightgcn_step_t *s, size_t sz, const flo
 {
     float *W = s->L == 2 ? s->grad_E0 : s->ws_bwd + sz;
     if (!zeroed) SPEX_TRY(spex::zero_f32(W, (int64_t)sz, stream));       // (SPEX_STEP_SPARSE_ADAM: the step's first launch has cleared it)
+    if ((s->flags & SPEX_STEP_FRONTIER_DEEP) != 0) {
+        // the deep step (L == 3: plain, no add term) takes the long-list kernel here too: on the F1 list it ran 1.04 x (unmasked) and
+        // 2.0 x (keep_prob 0.3) the one-workgroup-per-row kernel's rate (profiles/frontier_deep/push_ab.jsonl)
+        SPEX_TRY(spex_spmm_push_list_f32(s->graph, s->frontier_list, s->frontier_counts + 1, s->graph->n_rows, P, 1.0f, W, s->d, stream));
+        *W_out = W;
+        return SPEX_OK;
+    }
     SPEX_TRY(spex_spmm_push_rows_scaled_f32(s->graph, s->frontier_list, s->frontier_counts + 1, s->graph->n_rows, P, 1, s->L >= 4 ? s->g_out : nullptr,
                                             1, 1.0f, 1.0f / (float)(s->L + 1), W, s->d, stream));
     *W_out = W;
@@ -248,6 +294,7 @@ static int step_check(const spex_lightgcn_step_t *s, const StepBatch &k)
     const int32_t L = s->L, d = s->d, n_u = s->n_user_rows;
     SPEX_CHECK_ARG(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_rows, "%s: square graphs of one size", who);
     if ((s->flags & SPEX_STEP_BF16_GATHER) != 0) SPEX_TRY(bf16_step_check(s, who));
+    if ((s->flags & SPEX_STEP_FRONTIER_DEEP) != 0) SPEX_TRY(deep_step_check(s, who));
     if ((s->flags & SPEX_STEP_SPARSE_ADAM) != 0) SPEX_TRY(sparse_adam_check(s, who));
     if ((s->flags & SPEX_STEP_FRONTIER) != 0) SPEX_TRY(frontier_step_check(s, who));
     if (!bpr) {
@@ -313,6 +360,12 @@ static int step_forward(const spex_lightgcn_step_t *s, size_t sz, void *stream, 
     if ((s->flags & SPEX_STEP_BF16_GATHER) != 0) {
         if (fr) SPEX_TRY(frontier_forward_bf16(s, sz, &f->cur16, stream));
         else SPEX_TRY(bf16_forward(s, sz, &f->cur16, stream));
+    } else if ((s->flags & SPEX_STEP_FRONTIER_DEEP) != 0) {
+        // y_1 at the rows of F2 from E0, y_2 at the rows of F1 from that table: everything y_2 at F1 reads of y_1 lies in F2.  Both plain.
+        SPEX_TRY(spex_spmm_rowlist_dev_f32(s->graph, s->E0, s->frontier_list, s->frontier_counts + 2, s->graph->n_rows, s->ws_fwd, nullptr, nullptr, 1.0f,
+                                           s->d, stream));
+        SPEX_TRY(frontier_forward(s, s->ws_fwd, s->ws_fwd + sz, true, stream));
+        f->cur = s->ws_fwd + sz;
     } else {
         SPEX_TRY(forward_layers(s->graph, s->E0, s->light_out, s->ws_fwd, L, fr ? L - 2 : L - 1, s->d, stream, &f->cur));
         if (fr) {
@@ -470,7 +523,7 @@ static int lightgcn_step(spex_lightgcn_step_t *s, const StepBatch &k, void *stre
     const int32_t L = s->L, d = s->d, n_u = s->n_user_rows, n = k.n, t_next = s->t + 1;
     const size_t sz = (size_t)g->n_rows * d;
     const bool bpr = k.rows == 3, bf16 = (s->flags & SPEX_STEP_BF16_GATHER) != 0, det = (s->flags & SPEX_STEP_DETERMINISTIC) != 0;
-    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0, sp = (s->flags & SPEX_STEP_SPARSE_ADAM) != 0;
+    const bool fr = (s->flags & SPEX_STEP_FRONTIER) != 0, sp = (s->flags & SPEX_STEP_SPARSE_ADAM) != 0, deep = (s->flags & SPEX_STEP_FRONTIER_DEEP) != 0;
     // BPR: the L2 term's count tables by step parity — the batch launch counts into one, the Adam pass clears the other
     spex::L2Rows l2_rows;
     const spex::L2Rows *l2 = nullptr;
@@ -494,7 +547,7 @@ static int lightgcn_step(spex_lightgcn_step_t *s, const StepBatch &k, void *stre
     } else {
         s->flags &= ~SPEX_STEP_GRAD_ROWS_LISTED;                       // (this step writes grad_E0 wherever it likes)
     }
-    if (fr) SPEX_TRY(frontier_lists(s, k.a, n, k.b, n, k.c, k.c ? n : 0, stream, sp));      // (the first launches: every argument check is above)
+    if (fr) SPEX_TRY(frontier_lists(s, k.a, n, k.b, n, k.c, k.c ? n : 0, stream, deep ? (sp ? 3 : 2) : (sp ? 2 : 1)));      // (the first launches: every argument check is above)
     StepTables f;
     SPEX_TRY(step_forward(s, sz, stream, &f));
     auto batch = [&](float push_scale, float *loss_rows, float *slots, float *dense, float *G) -> int {
@@ -546,7 +599,12 @@ static int lightgcn_step(spex_lightgcn_step_t *s, const StepBatch &k, void *stre
         if (fr) src = W;
         if (fr && bf16 && L == 3) SPEX_TRY(frontier_backward_bf16(s, sz, W, stream));
         // (none under SPEX_STEP_SPARSE_ADAM, L == 2: the frontier push has left the whole product in grad_E0, non-zero in F2 only)
-        if (!bf16) SPEX_TRY(step_backward_pulls(gt, src, fr ? L - 3 : L - 2, s->g_out, s->ws_bwd, s->grad_E0, L, d, stream));
+        if (deep) {
+            // grad_E0 = A^T W as a push over the F2 list (W's support), the long-list kernel; complete in F3.  The Adam pass adds P.
+            if (!sp) SPEX_TRY(spex::zero_f32(s->grad_E0, (int64_t)sz, stream));      // (SPEX_STEP_SPARSE_ADAM: the step's first launch has cleared it)
+            SPEX_TRY(spex_spmm_push_list_f32(g, s->frontier_list, s->frontier_counts + 2, g->n_rows, W, 1.0f, s->grad_E0, d, stream));
+        } else if (!bf16)
+            SPEX_TRY(step_backward_pulls(gt, src, fr ? L - 3 : L - 2, s->g_out, s->ws_bwd, s->grad_E0, L, d, stream));
         if (L == 1) grad = G;
         if (no_dense) zero1 = nullptr;                                  // (untouched, all-zero)
         add = L == 1 ? nullptr : (L == 3 ? G : s->g_out);

@@ -350,14 +350,15 @@ class SpexGraph:
         _bump(Y, acc_out)
         return Y if Y is not None else acc_out
 
-    def spmm_rows_dev(self, X, rows, Y=None, acc_in=None, acc_out=None, acc_div=1.0, frontier=True, X16=None, Y16=None):
+    def spmm_rows_dev(self, X, rows, Y=None, acc_in=None, acc_out=None, acc_div=1.0, frontier=True, X16=None, Y16=None, count=None):
         """spmm_rows() driven by a device list (an ops.UniqueRows / ops.FrontierRows; frontier=True: the whole expanded list): the
         listed rows only, other rows of Y / acc_out untouched; entries are distinct, so acc_out may be acc_in.  d == 64.  An
         edge-dropout mask on the handle is applied entry by entry, as spmm() applies it (fp32 tables only).  See
         spex_spmm_rowlist_dev_f32.
         X16 (with X = None): the same launch gathering from a bf16 table, all arithmetic fp32 — bit-identical to
         spmm_rows_dev(X16.float(), ...) on every listed row; Y16 (bf16, optional, only with X16) = bf16(the value Y gets), the next
-        layer's gather source at the listed rows.  Y, Y16, acc_out: any subset, at least one.  See spex_spmm_rowlist_dev_bf16_f32."""
+        layer's gather source at the listed rows.  Y, Y16, acc_out: any subset, at least one.  See spex_spmm_rowlist_dev_bf16_f32.
+        count: one of the list's device cells, to drive any prefix of it (e.g. rows.count_f2: the two-hop set)."""
         if (X is None) == (X16 is None):
             raise ValueError("spmm_rows_dev: give either X (fp32) or X16 (bf16)")
         if Y16 is not None and X16 is None:
@@ -370,7 +371,10 @@ class SpexGraph:
         self._chk16(Y16, self.n_rows, d, "Y16")
         if rows.n_rows > self.n_rows:
             raise ValueError("spmm_rows_dev: the row list must index rows of the graph")
-        count = rows.count_f if frontier and hasattr(rows, "count_f") else rows.count
+        if count is None:
+            count = rows.count_f if frontier and hasattr(rows, "count_f") else rows.count
+        elif not (count.is_cuda and count.dtype == torch.int32 and count.numel() >= 1):
+            raise ValueError("spmm_rows_dev: count must be an int32 device cell")
         if X16 is not None:
             _launch(self.device, "spex_spmm_rowlist_dev_bf16_f32", self._h, _ptr(X16), _ptr(rows.list), _ptr(count), rows.capacity, _ptr(Y),
                     _ptr(Y16), _ptr(acc_in), _ptr(acc_out), float(acc_div), d)

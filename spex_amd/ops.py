@@ -386,8 +386,8 @@ class FrontierRows(UniqueRows):
 
     def __init__(self, n_rows, device):
         super().__init__(n_rows, n_rows, device)
-        self.counts = torch.zeros(4, dtype=torch.int32, device=device)       # |Bset|, |F1|, |F2| (after expand2), one spare
-        self.count, self.count_f, self.count_f2 = self.counts[0:1], self.counts[1:2], self.counts[2:3]
+        self.counts = torch.zeros(4, dtype=torch.int32, device=device)       # |Bset|, |F1|, |F2| (after expand2), |F3| (after expand3)
+        self.count, self.count_f, self.count_f2, self.count_f3 = self.counts[0:1], self.counts[1:2], self.counts[2:3], self.counts[3:4]
         self.max_b = 0
 
     def update(self, idx_a, idx_b=None, off_a=0, off_b=0):
@@ -417,6 +417,17 @@ class FrontierRows(UniqueRows):
             raise ValueError(f"FrontierRows.expand2: needs a square graph of {self.n_rows} rows (got {graph.n_rows} x {graph.n_cols})")
         _launch(self.list.device, self._entry(graph), graph._h, _ptr(self.list), _ptr(self.count_f), self.n_rows, _ptr(self.stamp),
                 self.epoch, _ptr(self.count_f2))
+        return self
+
+
+    def expand3(self, graph):
+        """The third hop (call once after expand2): append the columns of F2's rows that the list does not hold yet.  Afterwards the
+        list is [Bset | F1 minus Bset | F2 minus F1 | F3 minus F2] and `count_f3` = |F3| — at three layers the rows a deep frontier
+        step's gradient can touch (SPEX_STEP_FRONTIER_DEEP | SPEX_STEP_SPARSE_ADAM)."""
+        if graph.n_rows != self.n_rows or graph.n_cols != self.n_rows:
+            raise ValueError(f"FrontierRows.expand3: needs a square graph of {self.n_rows} rows (got {graph.n_rows} x {graph.n_cols})")
+        _launch(self.list.device, self._entry(graph), graph._h, _ptr(self.list), _ptr(self.count_f2), self.n_rows, _ptr(self.stamp),
+                self.epoch, _ptr(self.count_f3))
         return self
 
 
@@ -456,12 +467,28 @@ def zero_rows(x, rows, count=None):
     return x
 
 
-def spmm_push_rows(graph, rows, src, out, src_indexed, add=None, add_indexed=False, scale=1.0, add_scale=None, frontier=False):
+def spmm_push_list(graph, rows, src, out, scale=1.0, count=None):
+    """out += scale * A^T scatter(src) over the rows of a device list, src the [graph.n_rows, 64] table itself, in the work split for
+    LONG lists (spex_spmm_push_list_f32: a fixed grid strides over the list, short rows one wave task each, long rows cut into
+    64-entry tasks).  count: the cell that holds the length (default: the whole expanded list of a FrontierRows, rows.count_f; e.g.
+    rows.count_f2).  An edge-dropout mask on `graph` is applied entry by entry, as spmm_push_rows applies it.  Width 64 only."""
+    _need(src, "src"); _need(out, "out")
+    if out.dim() != 2 or out.shape[0] != graph.n_cols or rows.n_rows > graph.n_rows or not out.is_contiguous():
+        raise ValueError("spmm_push_list: out must be a contiguous [graph.n_cols, 64] table and the row list must index rows of the graph")
+    if src.shape != (graph.n_rows, out.shape[1]) or not src.is_contiguous() or src.data_ptr() == out.data_ptr():
+        raise ValueError(f"spmm_push_list: src must be a contiguous [graph.n_rows, {out.shape[1]}] table other than out (got {tuple(src.shape)})")
+    lst, cnt, cap = _row_list(rows, getattr(rows, "count_f", None) if count is None else count, "spmm_push_list")
+    _launch(out.device, "spex_spmm_push_list_f32", graph._h, _ptr(lst), _ptr(cnt), cap, _ptr(src), float(scale), _ptr(out), out.shape[1])
+    _bump(out)
+    return out
+
+
+def spmm_push_rows(graph, rows, src, out, src_indexed, add=None, add_indexed=False, scale=1.0, add_scale=None, frontier=False, count=None):
     """out += scale * (A^T scatter(src) + scatter(add)) for the rows of a UniqueRows list, A = the matrix of `graph`
     (spex_spmm_push_rows_f32).  src / add: the table itself (indexed=True) or compact [capacity, d] arrays.
     add_scale: a factor of its own for the add term (spex_spmm_push_rows_scaled_f32).  frontier=True: over the whole list of an
     expanded FrontierRows, not only its Bset part.  An edge-dropout mask on `graph` is applied entry by entry (A = the masked,
-    1 / keep_prob-scaled matrix)."""
+    1 / keep_prob-scaled matrix).  count: one of the list's device cells, to drive any prefix of it (e.g. rows.count_f2)."""
     _need(src, "src"); _need(out, "out"); _need(add, "add")
     d = out.shape[1]
     if out.shape[0] != graph.n_cols or rows.n_rows > graph.n_rows:
@@ -469,7 +496,7 @@ def spmm_push_rows(graph, rows, src, out, src_indexed, add=None, add_indexed=Fal
     for t, ind, nm in ((src, src_indexed, "src"), (add, add_indexed, "add")):
         if t is not None and (t.shape[1] != d or t.shape[0] < (rows.n_rows if ind else rows.capacity)):
             raise ValueError(f"spmm_push_rows: {nm} has shape {tuple(t.shape)}")
-    count = rows.count_f if frontier else rows.count
+    count = (rows.count_f if frontier else rows.count) if count is None else _row_list(rows, count, "spmm_push_rows")[1]
     if add_scale is None:
         _launch(out.device, "spex_spmm_push_rows_f32", graph._h, _ptr(rows.list), _ptr(count), rows.capacity, _ptr(src),
                 1 if src_indexed else 0, _ptr(add), 1 if add_indexed else 0, float(scale), _ptr(out), d)

@@ -60,9 +60,15 @@ def _drop_desc(stepper):
 
 class LightGCNStepper:
     def __init__(self, graph, E0, n_user_rows, n_layers=3, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, graph_t=None, deterministic=None,
-                 weight_decay=0.0, gather_dtype=None, frontier=False, sparse_adam=False):
-        """sparse_adam=True (only with frontier=True and n_layers == 2; ValueError otherwise): row-sparse ("lazy") Adam for the frontier
-        steps (SPEX_STEP_SPARSE_ADAM).  The forward, the loss and the gradient are the frontier step's; E0, m and v then
+                 weight_decay=0.0, gather_dtype=None, frontier=False, sparse_adam=False, frontier_depth=1):
+        """frontier_depth=2 (only with frontier=True, n_layers == 3, width 64, fp32 gather tables, not deterministic; ValueError
+        otherwise): the frontier form one level further (SPEX_STEP_FRONTIER_DEEP) — layer 1 at the batch's two-hop set
+        F2, layer 2 at F1, both backward products as pushes over the F1 and F2 lists: no launch of the step walks the whole graph.
+        Exact semantics (two pushes add with float atomics).  The layer tables are then valid at those rows only.  With
+        sparse_adam=True on top, Adam runs over the three-hop set F3 and no launch passes over a whole table.  `stepper.frontier_depth`
+        may be switched 1 <-> 2 between steps (one arena, one set of moments); back to 1 is refused while sparse_adam is on.
+        sparse_adam=True (only with frontier=True and n_layers == 2; ValueError otherwise): row-sparse ("lazy") Adam for the frontier
+        steps (SPEX_STEP_SPARSE_ADAM; at n_layers == 3 together with frontier_depth=2, and then with F3 for F2 below).  The forward, the loss and the gradient are the frontier step's; E0, m and v then
         change only at the rows of the batch's two-hop set F2 = F1 U the stored columns of F1's rows — the rows that can receive a
         gradient at two layers — by dense Adam's own expression with the global step count; every other row stands still bit for bit
         and does not coast on its momentum.  torch.optim.SparseAdam's masking law with torch.optim.Adam's placement of eps: its own
@@ -125,10 +131,11 @@ class LightGCNStepper:
         self._frontier = False
         self._front = None            # the batch's frontier list (ops.FrontierRows): list, counts and stamp table of both step forms
         self._sparse_adam = False
+        self._depth = 1               # the `frontier_depth` property
         self.gather_dtype = gather_dtype
         self._grad_listed = False     # grad_E0 is zero outside the frontier list's F2 (SPEX_STEP_GRAD_ROWS_LISTED) ...
-        self._grad_ver = self._list_ver = -1      # ... as long as nobody has written grad_E0 or the list since (torch's version counters)
-        if sparse_adam and not (frontier and self.L == 2):
+        self._grad_ver = self._list_ver = self._ws_ver = -1      # ... as long as nobody has written grad_E0 or the list since (torch's version counters)
+        if sparse_adam and not (frontier and (self.L == 2 or (self.L == 3 and frontier_depth == 2))):
             raise ValueError(f"LightGCNStepper(sparse_adam=True): only with frontier=True and n_layers == 2 (got frontier={bool(frontier)}, "
                              f"n_layers {self.L}): behind a whole-graph launch the gradient is dense")
         if frontier:
@@ -143,7 +150,10 @@ class LightGCNStepper:
             self._front = ops.FrontierRows(n, dev)
             self.frontier = True
             self._refuse_frontier_dropout("LightGCNStepper(frontier=True)")
+            self.frontier_depth = frontier_depth
             self.sparse_adam = bool(sparse_adam)
+        elif frontier_depth != 1:
+            self.frontier_depth = frontier_depth      # (refused: the stepper owns no frontier list)
         self.t = 0
 
     @property
@@ -160,6 +170,37 @@ class LightGCNStepper:
         self._frontier = bool(on)
 
     @property
+    def frontier_depth(self):
+        """1: the frontier form replaces layer L - 1 and the product behind the batch kernel's push.  2 (see __init__): every launch
+        of the n_layers == 3 step runs over a device list.  Switchable between steps on a stepper built with frontier=True,
+        n_layers == 3, width 64; ignored while `frontier` is off.  ValueError, nothing changed: depth 2 on another stepper, with
+        gather_dtype = torch.bfloat16 or deterministic=True; depth 1 while sparse_adam is on."""
+        return self._depth
+
+    @frontier_depth.setter
+    def frontier_depth(self, depth):
+        if depth not in (1, 2):
+            raise ValueError(f"LightGCNStepper.frontier_depth: 1 or 2 (got {depth!r})")
+        if depth == 2:
+            if self._front is None:
+                raise ValueError("LightGCNStepper.frontier_depth = 2: only on a stepper built with frontier=True (it owns the frontier list)")
+            if self.L != 3 or self.E0.shape[1] != 64:
+                raise ValueError(f"LightGCNStepper.frontier_depth = 2: takes n_layers == 3 and an embedding width of 64 (got n_layers "
+                                 f"{self.L}, width {self.E0.shape[1]}): at n_layers 2 frontier=True leaves no whole-graph launch")
+            if self.deterministic:
+                raise ValueError("LightGCNStepper.frontier_depth = 2: not with deterministic=True — the pushes add with float atomics")
+            if self._gather_dtype is not None:
+                raise ValueError("LightGCNStepper.frontier_depth = 2: not while gather_dtype is torch.bfloat16 — the deep frontier step "
+                                 "reads fp32 tables only (SPEX_STEP_FRONTIER_DEEP does not combine with SPEX_STEP_BF16_GATHER)")
+        elif self._sparse_adam and self.L == 3:
+            raise ValueError("LightGCNStepper.frontier_depth = 1: not while sparse_adam is on — at n_layers == 3 the row-sparse Adam pass "
+                             "needs the deep form (behind a whole-graph launch the gradient is dense): switch sparse_adam off first")
+        self._depth = int(depth)
+
+    def _deep(self):
+        return self._depth == 2 and self._frontier
+
+    @property
     def sparse_adam(self):
         """Whether the frontier steps run row-sparse Adam (see __init__).  May be switched off and on between steps on a stepper built
         with frontier=True and n_layers == 2; ignored while `frontier` is off."""
@@ -167,7 +208,7 @@ class LightGCNStepper:
 
     @sparse_adam.setter
     def sparse_adam(self, on):
-        if on and (self._front is None or self.L != 2):
+        if on and (self._front is None or not (self.L == 2 or (self.L == 3 and self._depth == 2))):
             raise ValueError("LightGCNStepper.sparse_adam = True: only on a stepper built with frontier=True and n_layers == 2")
         if on and self._gather_dtype is not None:
             raise ValueError("LightGCNStepper.sparse_adam = True: not while gather_dtype is torch.bfloat16 — the row-sparse Adam pass keeps "
@@ -196,6 +237,9 @@ class LightGCNStepper:
             if self._frontier and self._masked():
                 raise ValueError("LightGCNStepper.gather_dtype = torch.bfloat16: frontier=True with bf16 gather tables does not combine "
                                  "with edge dropout, and a mask is on: switch it off first (set_edge_dropout(None))")
+            if self._depth == 2:
+                raise ValueError("LightGCNStepper.gather_dtype = torch.bfloat16: not while frontier_depth is 2 — the deep frontier step "
+                                 "reads fp32 tables only (SPEX_STEP_FRONTIER_DEEP does not combine with SPEX_STEP_BF16_GATHER)")
             if self._sparse_adam:
                 raise ValueError("LightGCNStepper.gather_dtype = torch.bfloat16: not while sparse_adam is on — the row-sparse Adam pass "
                                  "keeps no bf16 shadow of E0 (SPEX_STEP_SPARSE_ADAM does not combine with SPEX_STEP_BF16_GATHER)")
@@ -210,14 +254,15 @@ class LightGCNStepper:
         return self._sparse_adam and self._frontier
 
     def _listed_ok(self):
-        """grad_E0 is zero outside frontier_list[0 : |F2|): a sparse-Adam step said so and nothing has written either tensor since."""
+        """grad_E0 is zero outside frontier_list[0 : |F2|) (n_layers 3: |F3|, and ws_bwd[1] is all-zero): a sparse-Adam step said so and
+        nothing has written these tensors since."""
         return (self._grad_listed and self._front is not None and self.grad_E0._version == self._grad_ver
-                and self._front.list._version == self._list_ver)
+                and self._front.list._version == self._list_ver and (self.L != 3 or self.ws_bwd._version == self._ws_ver))
 
     def _mark_listed(self, on=True):
         self._grad_listed = bool(on)
         if on:
-            self._grad_ver, self._list_ver = self.grad_E0._version, self._front.list._version
+            self._grad_ver, self._list_ver, self._ws_ver = self.grad_E0._version, self._front.list._version, self.ws_bwd._version
 
     def _masked(self):
         return getattr(self.graph, "mask_mode", 0) != 0 or getattr(self.graph_t, "mask_mode", 0) != 0
@@ -324,10 +369,22 @@ class LightGCNStepper:
             raise ValueError("LightGCNStepper(frontier=True): the batch must be contiguous int64 tensors on the GPU")
         L, g, lo = self.L, self.graph, self.light_out
         fr = self._front.update(idx_a, idx_b, 0, self.n_u).expand(g)
-        if two_hop:                   # (sparse_adam: F2 behind F1, the rows the Adam pass takes)
+        deep = self._deep()
+        if two_hop or deep:           # (sparse_adam: F2 behind F1, the rows the Adam pass takes; frontier_depth 2: the rows of layer 1)
             fr.expand2(g)
+        if two_hop and deep:          # (both: F3 behind F2, the rows the push over F2 can write)
+            fr.expand3(g)
         if self.lo_batch is None:
             self.lo_batch = torch.zeros_like(lo)
+        if deep:
+            # layer 1 at the rows of F2 from E0, layer 2 at the rows of F1 from that table (table and running sum), layer 3 at the batch's rows
+            g.spmm_rows_dev(self.E0, fr, Y=self.ws_fwd[0], acc_in=self.E0, acc_out=lo, count=fr.count_f2)
+            g.spmm_rows_dev(self.ws_fwd[0], fr, Y=self.ws_fwd[1], acc_in=lo, acc_out=lo)
+            if self._masked():
+                g.spmm_rows_dev(self.ws_fwd[1], fr, acc_in=lo, acc_out=self.lo_batch, acc_div=4.0, frontier=False)
+            else:
+                g.spmm_rows(self.ws_fwd[1], idx_a, idx_b, 0, self.n_u, acc_in=lo, acc_out=self.lo_batch, acc_div=4.0)
+            return self.lo_batch
         if self.gather_dtype is not None:
             # bf16 tables (L = 2 or 3): y_1 over the whole graph from the shadow at L == 3, y_(L-1) at F1 from the bf16 table before it —
             # fp32 into ws_fwd[L - 2], bf16 of the same value into ws16[L - 2] —, the last layer at the batch's distinct rows (the Bset
@@ -365,6 +422,17 @@ class LightGCNStepper:
         L, gt = self.L, self.graph_t
         inv = 1.0 / float(L + 1)
         W = self.grad_E0 if L == 2 else self.ws_bwd[1]
+        if self._deep():
+            # frontier_depth 2: W = A^T P as the push over the F1 list, grad_E0 = A^T W as the push over the F2 list, + P.  zeroed
+            # (sparse_adam): _sparse_begin has cleared grad_E0; W is cleared here either way (_sparse_adam_rows clears it by list again)
+            if not zeroed:
+                self._grad_listed = False
+                self.grad_E0.zero_()
+            W.zero_()
+            ops.spmm_push_rows(self.graph, self._front, self.ws_bwd[0], W, True, frontier=True)
+            ops.spmm_push_list(self.graph, self._front, W, self.grad_E0, count=self._front.count_f2)
+            self.grad_E0.add_(self.ws_bwd[0])
+            return
         if not zeroed:
             self._grad_listed = False
             W.zero_()
@@ -389,7 +457,7 @@ class LightGCNStepper:
         """sparse_adam, first thing in a step (before the lists are rebuilt): grad_E0 all-zero again — through the list the last
         sparse-Adam step left where that still describes it, over the whole table otherwise."""
         if self._listed_ok():
-            ops.zero_rows(self.grad_E0, self._front, self._front.count_f2)
+            ops.zero_rows(self.grad_E0, self._front, self._front.count_f3 if self.L == 3 else self._front.count_f2)
         else:
             self.grad_E0.zero_()
         self._grad_listed = False
@@ -398,8 +466,10 @@ class LightGCNStepper:
         """sparse_adam, last thing in a launch-by-launch step: Adam over the F2 list (grad_E0 holds the whole gradient, zero outside
         F2), g_out cleared at the batch's rows — the only ones written."""
         ops.adam_rows(self.E0, self.grad_E0, self.m, self.v, self._front, self.t, self.lr, self.betas[0], self.betas[1], self.eps,
-                      count=self._front.count_f2)
+                      count=self._front.count_f3 if self.L == 3 else self._front.count_f2)
         ops.zero_rows(self.g_out, self._front)
+        if self.L == 3:               # (frontier_depth 2: W, supported in F2, all-zero again for the next step's listed clear)
+            ops.zero_rows(self.ws_bwd[1], self._front, self._front.count_f2)
         self._shadow_current = False
         self._mark_listed()
 
@@ -545,6 +615,8 @@ class LightGCNStepper:
                 raise ValueError("LightGCNStepper(frontier=True): bpr_backward='dense' (SPEX_STEP_BPR_DENSE) is refused — a frontier step "
                                  "takes the push form at any T")
             d.flags |= _lib.STEP_FRONTIER
+            if self._deep():
+                d.flags |= _lib.STEP_FRONTIER_DEEP
             d.frontier_epoch = self._front.epoch        # one stamp table for both step forms: one epoch counter
             if self._sparse():
                 d.flags |= _lib.STEP_SPARSE_ADAM

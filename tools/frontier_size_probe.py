@@ -58,7 +58,7 @@ def draw_batch(rowptr, col, n_u, B, rng, num_ng=5):
     return users, items
 
 
-def probe(which, B, seed=0, loaded=None, keep_prob=1.0):
+def probe(which, B, seed=0, loaded=None, keep_prob=1.0, hops=2):
     rowptr, col, n_u = loaded or graph(which)
     n, nnz = len(rowptr) - 1, int(rowptr[-1])
     deg = np.diff(rowptr)
@@ -67,14 +67,20 @@ def probe(which, B, seed=0, loaded=None, keep_prob=1.0):
     f1 = neighbours(rowptr, col, bset)
     f2 = neighbours(rowptr, col, f1)
     ent = lambda rows: int(deg[rows].sum())
-    masked = {}
+    masked, deep = {}, {}
+    if hops >= 3:               # the three-hop set: the rows a deep frontier step's gradient can touch (SPEX_STEP_FRONTIER_DEEP)
+        f3 = neighbours(rowptr, col, f2)
+        deep.update({"three_hop_rows": len(f3), "three_hop_entries": ent(f3), "three_hop_share_of_rows": len(f3) / n})
     if keep_prob < 1.0:
         keep = np.random.default_rng(seed + 101).random(nnz) < keep_prob
         f1m = neighbours(rowptr, col, bset, keep)
         f2m = neighbours(rowptr, col, f1m, keep)
-        masked = {"keep_prob": keep_prob, "F1_rows_masked": len(f1m), "F1_entries_masked": ent(f1m), "two_hop_rows_masked": len(f2m),
+        if hops >= 3:
+            f3m = neighbours(rowptr, col, f2m, keep)
+            masked.update({"three_hop_rows_masked": len(f3m), "three_hop_entries_masked": ent(f3m)})
+        masked = {**masked, "keep_prob": keep_prob, "F1_rows_masked": len(f1m), "F1_entries_masked": ent(f1m), "two_hop_rows_masked": len(f2m),
                   "two_hop_entries_masked": ent(f2m)}
-    return {**masked, "graph": which, "n": n, "nnz": nnz, "B": B, "Bset_rows": len(bset), "Bset_entries": ent(bset), "F1_rows": len(f1),
+    return {**masked, **deep, "graph": which, "n": n, "nnz": nnz, "B": B, "Bset_rows": len(bset), "Bset_entries": ent(bset), "F1_rows": len(f1),
             "F1_entries": ent(f1), "F1_share_of_nnz": ent(f1) / nnz, "two_hop_rows": len(f2), "two_hop_entries": ent(f2),
             "two_hop_share_of_nnz": ent(f2) / nnz}
 
@@ -84,17 +90,27 @@ def main():
     ap.add_argument("--graphs", default="epinion2,20,22")
     ap.add_argument("--batches", default="256")
     ap.add_argument("--keep-prob", type=float, default=1.0)
+    ap.add_argument("--hops", type=int, default=2, choices=(2, 3), help="3: also |F3|, the three-hop set")
     ap.add_argument("--markdown", action="store_true")
     a = ap.parse_args()
     rows = []
     for g in a.graphs.split(","):
         loaded = graph(g)
-        rows += [probe(g, int(b), loaded=loaded, keep_prob=a.keep_prob) for b in a.batches.split(",")]
+        rows += [probe(g, int(b), loaded=loaded, keep_prob=a.keep_prob, hops=a.hops) for b in a.batches.split(",")]
     if not a.markdown:
         for r in rows:
             print(json.dumps(r))
         return
     k = lambda x: f"{x / 1e6:.2f} M" if x >= 1e6 else (f"{x / 1e3:.1f} k" if x >= 1e4 else str(x))
+    if a.hops >= 3:
+        m = a.keep_prob < 1.0
+        print("| graph | batch | batch rows | F1 rows | F2 rows | F3 rows (share of N) |" + (f" F1 / F2 / F3 rows at keep_prob {a.keep_prob:g} |" if m else ""))
+        print("|---|---|---|---|---|---|" + ("---|" if m else ""))
+        for r in rows:
+            print(f"| {r['graph']} (N {r['n']}, nnz {k(r['nnz'])}) | B = {r['B']} | {r['Bset_rows']} | {k(r['F1_rows'])} | {k(r['two_hop_rows'])} | "
+                  f"{k(r['three_hop_rows'])} ({100 * r['three_hop_share_of_rows']:.0f} %) |"
+                  + (f" {k(r['F1_rows_masked'])} / {k(r['two_hop_rows_masked'])} / {k(r['three_hop_rows_masked'])} |" if m else ""))
+        return
     if a.keep_prob < 1.0:
         print(f"| graph | batch | batch rows | F1 rows: unmasked / keep_prob {a.keep_prob:g} | F2 rows: unmasked / keep_prob {a.keep_prob:g} |")
         print("|---|---|---|---|---|")
