@@ -27,6 +27,18 @@ ADJACENT_ROWS_FROM = (16 << 20) // 256 + 1                # the packer's adjacen
 _cache = {}
 
 
+def csr_of_pairs(pairs):
+    """(rowptr, col, val) of the symmetric bipartite graph over NE rows of distinct (user, item) pairs, 1 / sqrt(deg deg) values."""
+    rows = np.concatenate([pairs[:, 0], pairs[:, 1] + NE_U])
+    cols = np.concatenate([pairs[:, 1] + NE_U, pairs[:, 0]])
+    order = np.lexsort((cols, rows))
+    rows, cols = rows[order], cols[order]
+    deg = np.bincount(rows, minlength=NE)
+    rowptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int32)
+    val = (1.0 / np.sqrt(deg[rows].astype(np.float64) * deg[cols])).astype(np.float32)
+    return rowptr, cols.astype(np.int32), val
+
+
 def graph_e():
     """(rowptr, col, val, train pairs) of graph (e)."""
     if "e" not in _cache:
@@ -42,14 +54,7 @@ def graph_e():
             i = np.concatenate([i, np.arange(WIDE * k, WIDE * (k + 1))])
         u, i = np.concatenate([u, [200]]), np.concatenate([i, [NE_I - 1]])          # the last row is not empty
         pairs = np.unique(np.stack([u, i], 1), axis=0).astype(np.int64)
-        rows = np.concatenate([pairs[:, 0], pairs[:, 1] + NE_U])
-        cols = np.concatenate([pairs[:, 1] + NE_U, pairs[:, 0]])
-        order = np.lexsort((cols, rows))
-        rows, cols = rows[order], cols[order]
-        deg = np.bincount(rows, minlength=NE)
-        rowptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int32)
-        val = (1.0 / np.sqrt(deg[rows].astype(np.float64) * deg[cols])).astype(np.float32)
-        _cache["e"] = (rowptr, cols.astype(np.int32), val, pairs)
+        _cache["e"] = csr_of_pairs(pairs) + (pairs,)
     return _cache["e"]
 
 
